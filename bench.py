@@ -14,9 +14,12 @@ histogram sum, after which every rank builds identical tables -- no RCCL on the 
 
 `--gpus N` without a launcher starts the N ranks itself (child processes, before anything touches the
 GPU); under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it is one rank.
-Prints ONE JSON line (rank 0).  `value` = 5 * bases * steps / wall over all ranks, in GB/s.  At N=1 the
-line also carries, under "other_workloads", the lognormal-length dexqv run and the dexta / dexar
-(BASELINE configs[1]/[2]) runs with their own roofline and CPU baseline (skip: --only-main).
+Prints ONE JSON line (rank 0).  `value` = 5 * bases * steps / wall over all ranks, in GB/s.  A plain run
+sets up, warms up, times the steps and prints the line; `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy.  Everything else is behind `--full`: the CPU baseline, the full-size
+on-device decode (round trip), the text front end and the per-kernel roofline; at N=1 also, under
+"other_workloads", the lognormal-length dexqv run and the dexta / dexar (BASELINE configs[1]/[2]) runs
+with their own roofline and CPU baseline (skip: --only-main); at N>1 the cross-rank table check.
 """
 import argparse
 import json
@@ -78,7 +81,13 @@ def parse():
     ap.add_argument("--no-walk-index", action="store_true",
                     help="dexqv: skip the decode of the batch with the HOST walk's group index (brings the 14 GB stream to the host and walks it)")
     ap.add_argument("--only-main", action="store_true",
-                    help="N=1: only the headline workload, without the lognormal / dexta / dexar extras")
+                    help="--full at N=1: only the headline workload, without the lognormal / dexta / dexar extras")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, the on-device decode and round-trip checks, the text "
+                         "front end, the per-kernel roofline, the extra workloads (N=1) and the cross-rank checks (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64; "
+                         "arrays larger than a cap as a fixed, seeded sample)")
     return ap.parse_args()
 
 
@@ -142,17 +151,18 @@ def main():
         if world > 1:
             print("bench.py: the dexta/dexar lines are single-GPU (reads shard with no exchange at all)", file=sys.stderr)
             sys.exit(2)
-        print(json.dumps(pack2_bench(args, args.workload == "dexar")))
+        print(json.dumps(pack2_bench(args, args.workload == "dexar", dump_dir=args.dump_outputs)))
         return
     if os.environ.get("DEXGPU_BENCH_ONE_DEVICE"):        # testing the N>1 path on a 1-GPU box
         local = 0
     if args.entries is None:
         args.entries = ENTRIES_1GPU if world == 1 else ENTRIES_SHARD
 
-    line = dexqv_bench(args, rank, world, local, cpu=(world == 1 and not args.no_cpu_baseline))
+    line = dexqv_bench(args, rank, world, local, cpu=(args.full and world == 1 and not args.no_cpu_baseline),
+                       dump_dir=args.dump_outputs)
     if rank != 0:
         return
-    if world == 1 and not args.only_main:
+    if args.full and world == 1 and not args.only_main:
         extra = {}
         a2 = argparse.Namespace(**vars(args))
         a2.dist = "lognormal" if args.dist == "fixed" else "fixed"
@@ -277,7 +287,7 @@ def main():
 # ------------------------------------------------------------------------------------------------
 #  dexqv (BASELINE configs[3] at N=1, configs[4] at N>1)
 # ------------------------------------------------------------------------------------------------
-def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=True):
+def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=True, dump_dir=None):
     import torch
     import torch.distributed as dist
     if world > 1 and not dist.is_initialized():
@@ -426,9 +436,17 @@ def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=Tru
     ctx.profile(False)
     ctx.qv_subindex(False)
     p_out = state["p_out"]
+    if dump_dir and rank == 0:               # what the last timed step left (before any check below touches the device state)
+        total = int(state["total"])
+        dump_outputs(dump_dir, args.seed, {
+            "dexqv_stream": (p_out.t[:total], np.float32),              # the .dexqv record stream (bytes)
+            "dexqv_stream_bytes": (np.array([total]), np.float64),
+            "dexqv_record_offsets": (p_rec.t, np.float64),              # n + 1 record starts in the stream
+            "dexqv_segments": (p_seg.t, np.float64),                     # 5 segment sizes an entry
+            "dexqv_histograms": (np.asarray(state["hist_mine"]), np.float64)})
 
     roundtrip = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         # size-independent property at full size: decode(encode(x)) == x, entirely on the device (the decoder
         # is fed by the encoder's own index), in chunks of entries so that any corpus size fits.  The decoder
         # writes only the five data lines of an entry; the chunk buffer is zero elsewhere and header bytes are
@@ -595,7 +613,7 @@ def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=Tru
                 state["decode_walk_indexed"] = {"skipped": f"{type(e).__name__}: {e}"[:200]}
     # GPU text front end on the same resident image (untimed extra): newline scan -> entry index
     fr = None
-    if front and not args.no_verify:
+    if args.full and front and not args.no_verify:
         torch.cuda.synchronize()
         ctx.profile(True)
         trace("front end: index")
@@ -618,13 +636,14 @@ def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=Tru
         all_bases, all_out = int(bb[0]), int(bb[1])
         if roundtrip is not None:
             roundtrip = int(bb[2]) == world
-        # every rank must have built the same tables: compare the coding images
-        import hashlib
-        img = api.qv_write_coding(state["coding"], b"@" + movie.encode())
-        sig = torch.tensor([int.from_bytes(hashlib.sha256(img).digest()[:7], "little")], dtype=torch.int64)
-        every = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
-        dist.all_gather(every, sig)
-        tables_same = all(int(e[0]) == int(every[0][0]) for e in every)
+        if args.full:
+            # every rank must have built the same tables: compare the coding images
+            import hashlib
+            img = api.qv_write_coding(state["coding"], b"@" + movie.encode())
+            sig = torch.tensor([int.from_bytes(hashlib.sha256(img).digest()[:7], "little")], dtype=torch.int64)
+            every = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(every, sig)
+            tables_same = all(int(e[0]) == int(every[0][0]) for e in every)
     else:
         all_bases, all_out = bases, state["total"]
 
@@ -694,7 +713,7 @@ def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=Tru
                                     "frac": round(dk["algo_bytes_8d_per_step"] / (dk["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                     "traffic": (dk["traffic_bytes_per_step"] / dk["launches_per_step"]) if dk["traffic_bytes_per_step"] else None},
                 "per_kernel": per_kernel}
-    if by_hist and args.dist == "fixed" and not args.lossy:
+    if args.full and by_hist and args.dist == "fixed" and not args.lossy:
         roofline["valu_issue"] = read_valu_issue(bases, times, args.steps)
     pipe = {"algo_bytes": step_algo, "step_ms": round(step_s * 1e3, 3),
             "kernel_ms_sum": round(sum(kern[k]["ms_avg"] * kern[k]["launches"] / args.steps for k in kern if k != "k_synth"), 3),
@@ -739,7 +758,13 @@ def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=Tru
         "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
                     for k, v in kern.items()},
     }
-    if world > 1:
+    if not args.full:                        # a plain run's line: the headline, the workload, the step's roofline and kernel times
+        for k in ("tables_identical_across_ranks", "host_table_build_us", "decode", "decode_indexed", "decode_walk_indexed",
+                  "device_walk", "text_front_end", "pipeline"):
+            del line[k]
+        line["roofline"] = {k: roofline[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "algo_bytes_per_step")}
+        line["roofline"]["dominant_kernel"] = {k: roofline["dominant_kernel"][k] for k in ("kernel", "achieved", "frac")}
+    if world > 1 and args.full:
         # what ONE GPU does with the same slice (2.5 M entries) when it runs alone: the figure a scaling efficiency is to be read
         # against -- the N = 1 line of this bench is BASELINE configs[3], 1 M entries, a different per-GPU workload (measured by
         # tools/evidence.sh under WORLD_SIZE=1 --entries 2500000, kept in profiles/per_gpu_reference.json)
@@ -749,11 +774,37 @@ def dexqv_bench(args, rank, world, local, cpu=True, front=True, index_decode=Tru
                 line["per_gpu_reference"] = ref
         except Exception:
             line["per_gpu_reference"] = None
+    if world > 1:
         dist.destroy_process_group()
     del d_text, p_out, state["p_out"], p_text
     ctx.close()
     torch.cuda.empty_cache()
     return line
+
+
+DUMP_CAP_BYTES = 16 << 20        # --dump-outputs: at most this much a file (a run writes at most three files this large)
+
+
+def dump_outputs(d, seed, arrays):
+    """--dump-outputs: every (array, dtype) of `arrays` to d/<name>.npy as that dtype (float32 or float64).  An array of more
+    elements than fit under DUMP_CAP_BYTES is written as a sample of that many: one element from each equal stretch of it, at a
+    place drawn from a generator seeded by the bench seed and the name -- the same places in every run with the same arguments.
+    Device tensors are sampled on the device."""
+    import zlib
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for name, (a, dtype) in arrays.items():
+        cap = DUMP_CAP_BYTES // np.dtype(dtype).itemsize
+        size = a.numel() if isinstance(a, torch.Tensor) else a.size
+        if size > cap:
+            stride = size // cap
+            rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+            idx = np.arange(cap, dtype=np.int64) * stride + rng.integers(0, stride, cap)
+            a = a.reshape(-1)
+            a = a.index_select(0, torch.from_numpy(idx).to(a.device)) if isinstance(a, torch.Tensor) else a[idx]
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a).astype(dtype))
 
 
 def read_traffic(path, workload, kernel, want, launches_per_step=1, per_step=False):
@@ -941,7 +992,7 @@ def cpu_baseline(ctx, api, d_text, off, lens, hlen, args, state, big):
 # ------------------------------------------------------------------------------------------------
 #  dexta / dexar (BASELINE configs[1] / [2])
 # ------------------------------------------------------------------------------------------------
-def pack2_bench(args, arrow):
+def pack2_bench(args, arrow, dump_dir=None):
     """2-bit pack + unpack of `--reads` x `--mean` reads (80-column text).  A host-generated tile of
     20000 reads is replicated on the device to the full size.  Returns the JSON line as a dict."""
     import torch
@@ -1006,16 +1057,21 @@ def pack2_bench(args, arrow):
     dt = time.perf_counter() - t0
     times = ctx.kernel_times()
     ctx.profile(False)
+    if dump_dir:                                      # what the last timed step left: the packed records and the text unpacked from them
+        dump_outputs(dump_dir, args.seed, {f"{name}_packed": (p_out.t[:out_bytes], np.float32),
+                                           f"{name}_unpacked": (p_back.t, np.float32)})
     # round trip: the sequence text of every read of the first and the last tile must come back
     # byte-identical (header lines are not rewritten by the decoder)
-    seqmask = np.zeros(tb, dtype=bool)
-    for o_, t_ in zip(tile.off, tile.tlen):
-        seqmask[int(o_): int(o_) + int(t_)] = True
-    same = True
-    for t in sorted({0, reps - 1} if not args.p2_align else set()):
-        a = d_text[t * tb: (t + 1) * tb].cpu().numpy()
-        b = p_back.t[t * tb: (t + 1) * tb].cpu().numpy()
-        same = same and bool(np.array_equal(a[seqmask], b[seqmask]))
+    same = None
+    if args.full:
+        seqmask = np.zeros(tb, dtype=bool)
+        for o_, t_ in zip(tile.off, tile.tlen):
+            seqmask[int(o_): int(o_) + int(t_)] = True
+        same = True
+        for t in sorted({0, reps - 1} if not args.p2_align else set()):
+            a = d_text[t * tb: (t + 1) * tb].cpu().numpy()
+            b = p_back.t[t * tb: (t + 1) * tb].cpu().numpy()
+            same = same and bool(np.array_equal(a[seqmask], b[seqmask]))
     bases = int(nsym.astype(np.uint64).sum())
     text_in = int(tlen.astype(np.uint64).sum())
     enc_ms, dec_ms = times["k_pack2_encode"][0] / args.steps, times["k_pack2_decode"][0] / args.steps
@@ -1024,7 +1080,7 @@ def pack2_bench(args, arrow):
     # CPU baseline: the real reference tool on the host tile (one core), and the GPU file driver on the
     # same tile compared with its output byte for byte
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         ref_bin = os.path.join(ROOT, "oracle", "_ref", name)
         shm = "/dev/shm" if os.path.isdir("/dev/shm") else None
         ext = ".arrow" if arrow else ".fasta"

@@ -31,7 +31,7 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
 
 @pytest.mark.gpu
 def test_bench_line_single_gpu():
-    d = _run(["--entries", "30000", "--steps", "2", "--warmup", "1", "--only-main", "--no-cpu-baseline"])
+    d = _run(["--full", "--entries", "30000", "--steps", "2", "--warmup", "1", "--only-main", "--no-cpu-baseline"])
     assert all(k in d for k in FIELDS)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "GB/s" and d["dtype"] == "u8"
     assert d["roundtrip_bit_exact"] is True and d["decode_indexed"]["bit_exact"] is True
@@ -49,7 +49,7 @@ def test_bench_line_single_gpu():
 
 @pytest.mark.gpu
 def test_bench_line_two_ranks_on_one_device():
-    d = _run(["--gpus", "2", "--entries", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    d = _run(["--full", "--gpus", "2", "--entries", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
              env={"DEXGPU_BENCH_ONE_DEVICE": "1"})
     assert all(k in d for k in FIELDS)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
@@ -63,9 +63,48 @@ def test_bench_line_four_ranks_on_one_device():
     its card at once, so the N = 8 launch cannot be rehearsed there: its sharding logic runs under gloo in
     tests/test_shard_gloo.py::test_eight_rank_sharded_dexqv_equals_single): one JSON line, n_gpus 4, identical tables on
     every rank, value = the whole job's bytes over the slowest rank's time."""
-    d = _run(["--gpus", "4", "--entries", "8000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    d = _run(["--full", "--gpus", "4", "--entries", "8000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
              env={"DEXGPU_BENCH_ONE_DEVICE": "1"})
     assert all(k in d for k in FIELDS)
     assert d["n_gpus"] == 4 and d["scaling"] == "weak" and d["config"]["sharding"] != "single GPU"
     assert d["tables_identical_across_ranks"] is True and d["roundtrip_bit_exact"] is True
     assert abs(d["value"] - 4 * 5 * 8000 * 10000 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.02 * d["value"]     # whole job
+
+
+def _dumped(d):
+    import numpy as np
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    return out
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_its_outputs_repeat(tmp_path):
+    """A run without --full: the headline fields, --steps timed steps, a line short enough to read from the end of the output,
+    nothing of --full's checks; --dump-outputs writes the last step's stream, record offsets, segment sizes and histograms, the
+    same in a second run with the same arguments."""
+    import numpy as np
+    args = ["--entries", "8000", "--steps", "3", "--warmup", "1"]
+    d = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["unit"] == "GB/s" and d["dtype"] == "u8" and d["higher_is_better"] is True
+    assert d["cpu_baseline"] is None and d["roundtrip_bit_exact"] is None and "other_workloads" not in d
+    assert len(json.dumps(d)) < 1800
+    assert abs(d["value"] - 5 * 8000 * 10000 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.02 * d["value"]
+    a = _dumped(tmp_path / "a")
+    assert set(a) == {"dexqv_stream", "dexqv_stream_bytes", "dexqv_record_offsets", "dexqv_segments", "dexqv_histograms"}
+    assert int(a["dexqv_stream_bytes"][0]) == d["config"]["output_bytes"] == int(a["dexqv_record_offsets"][-1])
+    assert a["dexqv_record_offsets"].shape == (8001,) and a["dexqv_histograms"].shape == (6, 256)
+    assert a["dexqv_histograms"].sum() > 0 and a["dexqv_segments"].min() >= 0
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    b = _dumped(tmp_path / "b")
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
+@pytest.mark.gpu
+def test_plain_pack2_line_and_its_outputs(tmp_path):
+    d = _run(["--workload", "dexta", "--reads", "20000", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 2 and d["cpu_baseline"] is None and d["roundtrip_bit_exact"] is None
+    a = _dumped(tmp_path)
+    assert set(a) == {"dexta_packed", "dexta_unpacked"}
+    assert a["dexta_packed"].max() <= 255 and a["dexta_unpacked"].max() <= 255

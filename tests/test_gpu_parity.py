@@ -1577,16 +1577,16 @@ def test_file_pointer_shims_in_the_order_of_dexqv(tmp_path):
 
 
 def test_the_references_own_mains_over_the_shims(tmp_path):
-    """oracle/_ref_compat/{dexqv,undexqv}: the reference's OWN dexqv.c / undexqv.c (main() and all, with its DB.c), compiled
+    """oracle/_ref/compat/{dexqv,undexqv}: the reference's OWN dexqv.c / undexqv.c (main() and all, with its DB.c), compiled
     unchanged against include/dexcompat.h in place of QV.h and linked with libdexgpu.so in place of QV.c (oracle/Makefile:
     compat).  Its main() drives QVcoding_Scan / Create_QVcoding / Write_QVcoding / Compress_Next_QVentry (dexqv.c:81-141) and
     Read_QVcoding / Uncompress_Next_QVentry (undexqv.c:112-208) -- the shims, the GPU behind them -- and must leave the golden
     bytes: every .quiva golden -> its .dexqv, and back (-U) -> the reference's own round trip."""
     import os, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = {t: os.path.join(root, "oracle", "_ref_compat", t) for t in ("dexqv", "undexqv")}
+    exe = {t: os.path.join(root, "oracle", "_ref", "compat", t) for t in ("dexqv", "undexqv")}
     if not all(os.path.isfile(e) for e in exe.values()):
-        pytest.skip("oracle/_ref_compat not built (make -C oracle compat needs /root/reference)")
+        pytest.skip("oracle/_ref/compat not built (make -C oracle compat needs the reference's sources)")
     ran = 0
     for case in O.cases("quiva"):
         if case.get("expect_error"):

@@ -8,7 +8,7 @@ for rep in 1 2; do
   for v in "$@"; do
     lib=$PWD/dextractor_amd/libdexgpu.so
     [ "$v" != main ] && lib=$PWD/tools/variants/libdexgpu_$v.so
-    DEXGPU_LIB=$lib python bench.py --no-cpu-baseline --only-main "${args[@]}" 2>/dev/null | python -c "
+    DEXGPU_LIB=$lib python bench.py --full --no-cpu-baseline --only-main "${args[@]}" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 pk=d['roofline']['per_kernel']

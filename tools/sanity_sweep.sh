@@ -4,7 +4,7 @@
 #  the device walk of the stream: its index the encoder's, the decode from it bit-exact)
 fail=0
 while read -r a; do
-  python bench.py --no-cpu-baseline --only-main --steps 2 --warmup 1 $a 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --only-main --steps 2 --warmup 1 $a 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 g=lambda k,f: (d.get(k) or {}).get(f)
