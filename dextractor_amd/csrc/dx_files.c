@@ -70,6 +70,24 @@ static void dfree_all(dpool *pool)
   pool->n = 0;
 }
 
+/* DEXGPU_TEXT_BUDGET (bytes): how much of `whole` bytes the device is to take at once.  1: the variable is set and has decided -- *cap is
+   its figure (`floor` at least), or 0 for all at once (no figure, or one the whole stays under); 0: it is not set, what is free decides */
+static int budget_env(size_t whole, size_t floor, size_t *cap)
+{ const char *e = getenv("DEXGPU_TEXT_BUDGET");
+  unsigned long long v;
+  if (e == NULL || !*e) return 0;
+  v = strtoull(e, NULL, 10);
+  *cap = v && v < whole ? (size_t) (v < floor ? floor : v) : 0;
+  return 1;
+}
+
+/* a sink that sees its chunks `shift` bytes further on (the record stream follows the file's head; a piece follows the pieces before it) */
+typedef struct { dx_sink_fn sink; void *user; size_t shift; } shifted_sink;
+static int pass_shifted(void *arg, uint8_t *data, size_t len, size_t at)
+{ shifted_sink *h = arg;
+  return h->sink(h->user, data, len, at + h->shift);
+}
+
 /* ==========================================================================================
  *  dexta / dexar
  * ========================================================================================== */
@@ -86,14 +104,111 @@ static int ends_with_a_header(const uint8_t *text, size_t n)
 /* how much text the device packs at once: DEXGPU_TEXT_BUDGET (bytes) when set, else all of it (0) unless the text, its packed
    image and the index do not fit what is free */
 static size_t pack2_cap(dx_ctx *ctx, size_t n)
-{ const char *e = getenv("DEXGPU_TEXT_BUDGET");
-  uint64_t fr = 0, all = 0;
-  if (e != NULL && *e)
-    { const unsigned long long v = strtoull(e, NULL, 10);
-      return v && v < n ? (size_t) (v < 65536u ? 65536u : v) : 0;
-    }
+{ uint64_t fr = 0, all = 0;
+  size_t   cap;
+  if (budget_env(n, 65536u, &cap)) return cap;
   if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
   return 1.35 * (double) n > 0.9 * (double) fr ? (size_t) (0.6 * (double) fr) : 0;
+}
+
+/* The index of a .fasta / .arrow text and the layout of its image.  Per read: where its lines begin in the text and how long they are
+   (off, tlen: host index only), its symbols (nsym), the header's fields (hdr4, cnr4); then the framed header bytes (blob, hoff[cnt + 1])
+   and the record's place in the image (ooff[cnt + 1]; ooff[cnt] == total). */
+typedef struct
+  { uint64_t  cnt, *off, *hoff, *ooff;
+    uint32_t *tlen, *nsym;
+    int32_t  *hdr4;
+    uint16_t *cnr4;
+    uint8_t  *blob;
+    size_t    plen, total;
+  } seq_index;
+
+static void seq_index_free(seq_index *ix)
+{ free(ix->off); free(ix->hoff); free(ix->ooff); free(ix->tlen); free(ix->nsym); free(ix->hdr4); free(ix->cnr4); free(ix->blob); }
+
+static int seq_index_host(seq_index *ix, int arrow, const uint8_t *text, size_t n, uint64_t *errline, int *errcode)
+{ const int rc = dx_index_seq(arrow, text, n, 0, NULL, NULL, NULL, NULL, NULL, &ix->cnt, &ix->plen, errline, errcode);
+  if (rc != DX_OK) return rc;
+  ix->off  = malloc((ix->cnt + 1) * sizeof(*ix->off));
+  ix->tlen = malloc((ix->cnt + 1) * sizeof(*ix->tlen));
+  ix->nsym = malloc((ix->cnt + 1) * sizeof(*ix->nsym));
+  ix->hdr4 = malloc((ix->cnt + 1) * 4 * sizeof(*ix->hdr4));
+  ix->cnr4 = malloc((ix->cnt + 1) * 4 * sizeof(*ix->cnr4));
+  if (!ix->off || !ix->tlen || !ix->nsym || !ix->hdr4 || !ix->cnr4) return DX_E_NOMEM;
+  return dx_index_seq(arrow, text, n, ix->cnt, ix->off, ix->tlen, ix->nsym, ix->hdr4, ix->cnr4, &ix->cnt, &ix->plen, errline, errcode);
+}
+
+/* the framing bytes of every header, *well the last record's well before and after (the record framing codes differences,
+   dexta.c:187-193), and the records' places in an image whose first record stands at `at` */
+static int seq_index_frame(seq_index *ix, int arrow, int32_t *well, size_t at)
+{ uint64_t i;
+  int      rc;
+  ix->hoff = malloc((ix->cnt + 1) * sizeof(*ix->hoff));
+  ix->ooff = malloc((ix->cnt + 1) * sizeof(*ix->ooff));
+  ix->blob = malloc(dx_frame_bound(ix->hdr4, ix->cnt, 0, arrow) + 16);
+  if (!ix->hoff || !ix->ooff || !ix->blob) return DX_E_NOMEM;
+  rc = dx_frame_headers(ix->hdr4, ix->cnr4, ix->cnt, arrow, well, ix->blob, ix->hoff);
+  if (rc != DX_OK) return rc;
+  for (i = 0; i < ix->cnt; i++)
+    { ix->ooff[i] = at;
+      at += (size_t) (ix->hoff[i+1] - ix->hoff[i]) + (((size_t) ix->nsym[i] + 3) >> 2);
+    }
+  ix->ooff[ix->cnt] = ix->total = at;
+  return DX_OK;
+}
+
+/* key, prefix length, prefix (2 + 4 + plen bytes): dexta.c:124-129 */
+static void pack2_head(uint8_t *img, const uint8_t *text, size_t plen)
+{ const uint16_t key = 0x55aa;
+  const int32_t  pl  = (int32_t) plen;
+  memcpy(img, &key, 2);
+  memcpy(img + 2, &pl, 4);
+  memcpy(img + 6, text, plen);
+}
+
+/* Reads [i0, i1) of a host index: their text up, with offsets counted from the range's first byte; packed; the records down to their
+   places in img.  The device buffers live for the call. */
+static int pack2_range(dx_ctx *ctx, int arrow, const uint8_t *text, const seq_index *ix, uint64_t i0, uint64_t i1, uint8_t *img)
+{ dpool     pool = { {0}, 0, ctx };
+  const uint64_t m = i1 - i0;
+  uint64_t  i, *roff, *rhoff, *rooff;
+  void     *d_text, *d_off, *d_tlen, *d_nsym, *d_hdr, *d_hoff, *d_out, *d_ooff;
+  int       rc;
+  if (m == 0) return DX_OK;
+  roff = malloc((3 * m + 1) * sizeof(*roff));
+  if (roff == NULL) return DX_E_NOMEM;
+  rooff = roff + m; rhoff = rooff + m;
+  { const uint64_t t0 = ix->off[i0], t1 = ix->off[i1 - 1] + ix->tlen[i1 - 1];
+    const uint64_t h0 = ix->hoff[i0], o0 = ix->ooff[i0], obytes = ix->ooff[i1] - o0;
+    for (i = 0; i < m; i++)
+      { roff[i]  = ix->off[i0 + i] - t0;
+        rhoff[i] = ix->hoff[i0 + i] - h0;
+        rooff[i] = ix->ooff[i0 + i] - o0;
+      }
+    rhoff[m] = ix->hoff[i1] - h0;
+    TRY(dupload(&pool, text + t0, (size_t) (t1 - t0), &d_text));
+    TRY(dupload(&pool, roff, m * 8, &d_off));
+    TRY(dupload(&pool, ix->tlen + i0, m * 4, &d_tlen));
+    TRY(dupload(&pool, ix->nsym + i0, m * 4, &d_nsym));
+    TRY(dupload(&pool, ix->blob + h0, (size_t) rhoff[m], &d_hdr));
+    TRY(dupload(&pool, rhoff, (m + 1) * 8, &d_hoff));
+    TRY(dupload(&pool, rooff, m * 8, &d_ooff));
+    TRY(dalloc(&pool, (size_t) obytes, &d_out));
+    TRY(dx_pack2_encode(ctx, arrow ? DX_ALPHA_ARROW : DX_ALPHA_BASES, d_text, d_off, d_tlen, d_nsym, m,
+                        d_hdr, d_hoff, d_out, d_ooff));
+    TRY(dx_d2h(ctx, img + o0, d_out, (size_t) obytes));
+  }
+done:
+  dfree_all(&pool);
+  free(roff);
+  return rc;
+}
+
+/* a slice of whole reads from i0 on: as many as make at most `cap` bytes of text, and one at least */
+static uint64_t pack2_slice_end(const seq_index *ix, uint64_t i0, size_t cap)
+{ uint64_t i1 = i0 + 1;
+  while (i1 < ix->cnt && (size_t) ix->off[i1] + ix->tlen[i1] - (size_t) ix->off[i0] <= cap) i1++;
+  return i1;
 }
 
 /* One piece of a .fasta / .arrow text -- whole records, the first of them the file's first (`first`: the image then begins with the
@@ -102,18 +217,17 @@ static size_t pack2_cap(dx_ctx *ctx, size_t n)
 static int pack2_piece(dx_ctx *ctx, int arrow, const uint8_t *text, size_t n, int first, int32_t *well,
                        uint8_t **out, size_t *out_len, uint64_t *errline, int *errcode)
 { dpool     pool = { {0}, 0, ctx };
-  uint64_t  cnt = 0, i, *off = NULL, *hoff = NULL, *ooff = NULL;
-  uint32_t *tlen = NULL, *nsym = NULL;
-  int32_t  *hdr4 = NULL, lwell = *well;
-  uint16_t *cnr4 = NULL;
-  uint8_t  *blob = NULL, *img = NULL;
-  size_t    plen = 0, at, total;
-  void     *d_text = NULL, *d_off = NULL, *d_tlen = NULL, *d_nsym = NULL, *d_hdr, *d_hoff, *d_out, *d_ooff;
+  seq_index ix;
+  int32_t   lwell = *well;
+  uint8_t  *img = NULL;
+  void     *d_text, *d_off = NULL, *d_tlen = NULL, *d_nsym = NULL, *d_hdr, *d_hoff, *d_out, *d_ooff;
+  uint64_t  i0, i1;
   size_t    sliced;
   int       rc;
 
   if (ctx == NULL || out == NULL || out_len == NULL) return DX_E_ARG;
   *out = NULL; *out_len = 0;
+  memset(&ix, 0, sizeof(ix));
 
   /* A text that does not fit the device beside its packed image (or DEXGPU_TEXT_BUDGET): indexed on the host, then slices of
      whole reads -- upload, pack, the slice's records into the image (the reference reads record after record,
@@ -121,121 +235,49 @@ static int pack2_piece(dx_ctx *ctx, int arrow, const uint8_t *text, size_t n, in
   sliced = pack2_cap(ctx, n);
   /* index: on the GPU for large images (newline scan, record extents there; only header lines come
      back), on the host for small ones and for anything the GPU front end rejects (exact message) */
-  if (n > 0 && !sliced) TRY(dupload(&pool, text, n, &d_text));
   if (!sliced && n >= DX_GPU_INDEX_MIN && !dx_test_on("host_index") && !ends_with_a_header(text, n))
     { uint64_t *go = NULL; uint32_t *gt = NULL, *gs = NULL;
-      rc = dx_index_seq_device(ctx, arrow, d_text, n, &go, &gt, &gs, &cnt, &hdr4, &cnr4, &plen, errline, errcode);
+      TRY(dupload(&pool, text, n, &d_text));
+      rc = dx_index_seq_device(ctx, arrow, d_text, n, &go, &gt, &gs, &ix.cnt, &ix.hdr4, &ix.cnr4, &ix.plen, errline, errcode);
       if (rc == DX_OK)
         { d_off = go; d_tlen = gt; d_nsym = gs;
           pool.p[pool.n++] = go; pool.p[pool.n++] = gt; pool.p[pool.n++] = gs;
-          nsym = malloc((cnt + 1) * sizeof(*nsym));
-          if (!nsym) { rc = DX_E_NOMEM; goto done; }
-          TRY(dx_d2h(ctx, nsym, d_nsym, cnt * 4));
+          ix.nsym = malloc((ix.cnt + 1) * sizeof(*ix.nsym));
+          if (!ix.nsym) { rc = DX_E_NOMEM; goto done; }
+          TRY(dx_d2h(ctx, ix.nsym, d_nsym, ix.cnt * 4));
         }
       else if (rc != DX_E_FORMAT)
         goto done;
-      rc = DX_OK;
     }
-  if (d_off == NULL)
-    { TRY(dx_index_seq(arrow, text, n, 0, NULL, NULL, NULL, NULL, NULL, &cnt, &plen, errline, errcode));
-      off  = malloc((cnt + 1) * sizeof(*off));
-      tlen = malloc((cnt + 1) * sizeof(*tlen));
-      nsym = malloc((cnt + 1) * sizeof(*nsym));
-      hdr4 = malloc((cnt + 1) * 4 * sizeof(*hdr4));
-      cnr4 = malloc((cnt + 1) * 4 * sizeof(*cnr4));
-      if (!off || !tlen || !nsym || !hdr4 || !cnr4) { rc = DX_E_NOMEM; goto done; }
-      TRY(dx_index_seq(arrow, text, n, cnt, off, tlen, nsym, hdr4, cnr4, &cnt, &plen, errline, errcode));
-      if (!sliced)
-        { TRY(dupload(&pool, off,  cnt * 8, &d_off));
-          TRY(dupload(&pool, tlen, cnt * 4, &d_tlen));
-          TRY(dupload(&pool, nsym, cnt * 4, &d_nsym));
-        }
-    }
-  hoff = malloc((cnt + 1) * sizeof(*hoff));
-  ooff = malloc((cnt + 1) * sizeof(*ooff));
-  if (!hoff || !ooff) { rc = DX_E_NOMEM; goto done; }
+  if (d_off == NULL) TRY(seq_index_host(&ix, arrow, text, n, errline, errcode));
+  TRY(seq_index_frame(&ix, arrow, &lwell, first ? 2 + 4 + ix.plen : 0));
 
-  blob = malloc(dx_frame_bound(hdr4, cnt, 0, arrow) + 16);
-  if (!blob) { rc = DX_E_NOMEM; goto done; }
-  TRY(dx_frame_headers(hdr4, cnr4, cnt, arrow, &lwell, blob, hoff));
-
-  if (!first) plen = 0;
-  at = first ? 2 + 4 + plen : 0;                       /* key, prefix length, prefix: dexta.c:124-129 */
-  for (i = 0; i < cnt; i++)
-    { ooff[i] = at;
-      at += (size_t) (hoff[i+1] - hoff[i]) + (((size_t) nsym[i] + 3) >> 2);
-    }
-  total = at;
-
-  img = malloc(total + 16);
+  img = malloc(ix.total + 16);
   if (!img) { rc = DX_E_NOMEM; goto done; }
-  if (first)
-    { uint16_t key = 0x55aa;
-      int32_t  pl  = (int32_t) plen;
-      memcpy(img, &key, 2);
-      memcpy(img + 2, &pl, 4);
-      memcpy(img + 6, text, plen);
-    }
+  if (first) pack2_head(img, text, ix.plen);
 
-  if (cnt > 0 && sliced)
-    { uint64_t *rel = NULL, i0, i1, most = 0;
-      size_t    tmax = 0, omax = 0;
-#define READ_END(i) ((size_t) off[i] + tlen[i])
-      for (i0 = 0; i0 < cnt; i0 = i1)
-        { i1 = i0 + 1;
-          while (i1 < cnt && READ_END(i1) - (size_t) off[i0] <= sliced) i1++;
-          if (READ_END(i1 - 1) - (size_t) off[i0] > tmax) tmax = READ_END(i1 - 1) - (size_t) off[i0];
-          if ((i1 < cnt ? ooff[i1] : total) - ooff[i0] > omax) omax = (size_t) ((i1 < cnt ? ooff[i1] : total) - ooff[i0]);
-          if (i1 - i0 > most) most = i1 - i0;
-        }
-      rel = malloc(3 * (most + 1) * sizeof(*rel));
-      if (rel == NULL) { rc = DX_E_NOMEM; goto done; }
-      rc = dalloc(&pool, tmax, &d_text);
-      if (rc == DX_OK) rc = dalloc(&pool, (most + 1) * 8, &d_off);
-      if (rc == DX_OK) rc = dupload(&pool, tlen, cnt * 4, &d_tlen);
-      if (rc == DX_OK) rc = dupload(&pool, nsym, cnt * 4, &d_nsym);
-      if (rc == DX_OK) rc = dupload(&pool, blob, (size_t) hoff[cnt], &d_hdr);
-      if (rc == DX_OK) rc = dalloc(&pool, (most + 1) * 8, &d_hoff);
-      if (rc == DX_OK) rc = dalloc(&pool, (most + 1) * 8, &d_ooff);
-      if (rc == DX_OK) rc = dalloc(&pool, omax, &d_out);
-      for (i0 = 0; i0 < cnt && rc == DX_OK; i0 = i1)
-        { const size_t b0 = (size_t) off[i0];
-          const uint64_t o0 = ooff[i0];
-          i1 = i0 + 1;
-          while (i1 < cnt && READ_END(i1) - b0 <= sliced) i1++;
-          for (i = i0; i <= i1; i++)
-            { if (i < i1) { rel[i - i0] = off[i] - b0; rel[2 * (most + 1) + (i - i0)] = ooff[i] - o0; }
-              rel[(most + 1) + (i - i0)] = hoff[i] - hoff[i0];
-            }
-          rc = dx_h2d(ctx, d_text, text + b0, READ_END(i1 - 1) - b0);
-          if (rc == DX_OK) rc = dx_h2d(ctx, d_off, rel, (i1 - i0) * 8);
-          if (rc == DX_OK) rc = dx_h2d(ctx, d_hoff, rel + (most + 1), (i1 - i0 + 1) * 8);
-          if (rc == DX_OK) rc = dx_h2d(ctx, d_ooff, rel + 2 * (most + 1), (i1 - i0) * 8);
-          if (rc == DX_OK)
-            rc = dx_pack2_encode(ctx, arrow ? DX_ALPHA_ARROW : DX_ALPHA_BASES, d_text, d_off, (const uint32_t *) d_tlen + i0, (const uint32_t *) d_nsym + i0,
-                                 i1 - i0, (const uint8_t *) d_hdr + hoff[i0], d_hoff, d_out, d_ooff);
-          if (rc == DX_OK) rc = dx_d2h(ctx, img + o0, d_out, (size_t) ((i1 < cnt ? ooff[i1] : total) - o0));
-        }
-#undef READ_END
-      free(rel);
-      if (rc != DX_OK) goto done;
-    }
-  else if (cnt > 0)
-    { TRY(dupload(&pool, blob, (size_t) hoff[cnt], &d_hdr));
-      TRY(dupload(&pool, hoff, (cnt + 1) * 8, &d_hoff));
-      TRY(dupload(&pool, ooff, cnt * 8, &d_ooff));
-      TRY(dalloc(&pool, total, &d_out));
-      TRY(dx_pack2_encode(ctx, arrow ? DX_ALPHA_ARROW : DX_ALPHA_BASES, d_text, d_off, d_tlen, d_nsym, cnt,
+  if (d_off != NULL && ix.cnt > 0)                       /* indexed on the device: text and index are there, nothing to rebase */
+    { TRY(dupload(&pool, ix.blob, (size_t) ix.hoff[ix.cnt], &d_hdr));
+      TRY(dupload(&pool, ix.hoff, (ix.cnt + 1) * 8, &d_hoff));
+      TRY(dupload(&pool, ix.ooff, ix.cnt * 8, &d_ooff));
+      TRY(dalloc(&pool, ix.total, &d_out));
+      TRY(dx_pack2_encode(ctx, arrow ? DX_ALPHA_ARROW : DX_ALPHA_BASES, d_text, d_off, d_tlen, d_nsym, ix.cnt,
                           d_hdr, d_hoff, d_out, d_ooff));
-      TRY(dx_d2h(ctx, img + ooff[0], (uint8_t *) d_out + ooff[0], total - (size_t) ooff[0]));
+      TRY(dx_d2h(ctx, img + ix.ooff[0], (uint8_t *) d_out + ix.ooff[0], ix.total - (size_t) ix.ooff[0]));
     }
-  *out = img; *out_len = total; img = NULL;
+  else if (d_off == NULL)
+    for (i0 = 0; i0 < ix.cnt; i0 = i1)                   /* indexed here: all reads at once, or slice after slice */
+      { i1 = sliced ? pack2_slice_end(&ix, i0, sliced) : ix.cnt;
+        TRY(pack2_range(ctx, arrow, text, &ix, i0, i1, img));
+      }
+  *out = img; *out_len = ix.total; img = NULL;
   *well = lwell;
   rc = DX_OK;
 
 done:
   dfree_all(&pool);
-  free(off); free(hoff); free(ooff); free(tlen); free(nsym); free(hdr4); free(cnr4); free(blob); free(img);
+  seq_index_free(&ix);
+  free(img);
   return rc;
 }
 
@@ -287,18 +329,20 @@ static void *ra_main(void *arg)
   int slot = 0;
   for (;;)
     { size_t n = 0;
+      int    bad = 0;
       pthread_mutex_lock(&r->mx);
       while (r->full[slot] && !r->stop) pthread_cond_wait(&r->cv, &r->mx);
       if (r->stop) { pthread_mutex_unlock(&r->mx); break; }
       pthread_mutex_unlock(&r->mx);
       while (n < RA_BLOCK)
         { const long k = r->rd(r->user, r->blk[slot] + n, RA_BLOCK - n);
-          if (k < 0) { r->err = 1; break; }
+          if (k < 0) { bad = 1; break; }
           if (k == 0) break;
           n += (size_t) k;
         }
       pthread_mutex_lock(&r->mx);
       r->len[slot] = n; r->full[slot] = 1;
+      if (bad) r->err = 1;
       if (n < RA_BLOCK) r->eof = 1;
       pthread_cond_broadcast(&r->cv);
       pthread_mutex_unlock(&r->mx);
@@ -324,12 +368,12 @@ static long ra_read(void *arg, void *buf, size_t want)
   size_t got = 0;
   if (!r->threaded) return r->rd(r->user, buf, want);
   while (got < want)
-    { int have;
+    { int have, err;
       pthread_mutex_lock(&r->mx);
       while (!r->full[r->cur] && !r->eof && !r->err) pthread_cond_wait(&r->cv, &r->mx);
-      have = r->full[r->cur];
+      have = r->full[r->cur]; err = r->err;
       pthread_mutex_unlock(&r->mx);
-      if (r->err) return -1;
+      if (err) return -1;
       if (!have) break;                                /* the input's end, and nothing left in this block (blocks come in turn) */
       { const size_t k = r->len[r->cur] - r->pos < want - got ? r->len[r->cur] - r->pos : want - got;
         memcpy((uint8_t *) buf + got, r->blk[r->cur] + r->pos, k);
@@ -439,63 +483,25 @@ done:
  *  cross-record datum, the previous well of a range's first read, is known from the host index.
  * ========================================================================================== */
 typedef struct
-  { dx_ctx         *ctx;
-    int             arrow, rc;
-    const uint8_t  *text;
-    const uint64_t *off, *ooff, *hoff;       /* per read: text offset, output offset, header-blob offset */
-    const uint32_t *tlen, *nsym;
-    const uint8_t  *blob;
-    uint8_t        *img;
-    uint64_t        lo, hi;                   /* reads [lo, hi) */
+  { dx_ctx          *ctx;
+    int              arrow, rc;
+    const uint8_t   *text;
+    const seq_index *ix;
+    uint8_t         *img;
+    uint64_t         lo, hi;                  /* reads [lo, hi) */
   } p2_job;
 
 static void *p2_main(void *arg)
-{ p2_job   *j = (p2_job *) arg;
-  dpool     pool = { {0}, 0, j->ctx };
-  uint64_t  m = j->hi - j->lo, i, *roff = NULL, *rhoff = NULL, *rooff = NULL;
-  void     *d_text, *d_off, *d_tlen, *d_nsym, *d_hdr, *d_hoff, *d_out, *d_ooff;
-  int       rc = DX_OK;
-  if (m == 0) { j->rc = DX_OK; return NULL; }
-  { const uint64_t t0 = j->off[j->lo], t1 = j->off[j->hi - 1] + j->tlen[j->hi - 1];
-    const uint64_t h0 = j->hoff[j->lo], o0 = j->ooff[j->lo];
-    const uint64_t obytes = j->ooff[j->hi] - o0;
-    roff  = malloc(m * sizeof(*roff));
-    rhoff = malloc((m + 1) * sizeof(*rhoff));
-    rooff = malloc(m * sizeof(*rooff));
-    if (!roff || !rhoff || !rooff) { rc = DX_E_NOMEM; goto done; }
-    for (i = 0; i < m; i++)
-      { roff[i]  = j->off[j->lo + i] - t0;
-        rhoff[i] = j->hoff[j->lo + i] - h0;
-        rooff[i] = j->ooff[j->lo + i] - o0;
-      }
-    rhoff[m] = j->hoff[j->hi] - h0;
-    TRY(dupload(&pool, j->text + t0, (size_t) (t1 - t0), &d_text));
-    TRY(dupload(&pool, roff, m * 8, &d_off));
-    TRY(dupload(&pool, j->tlen + j->lo, m * 4, &d_tlen));
-    TRY(dupload(&pool, j->nsym + j->lo, m * 4, &d_nsym));
-    TRY(dupload(&pool, j->blob + h0, (size_t) rhoff[m], &d_hdr));
-    TRY(dupload(&pool, rhoff, (m + 1) * 8, &d_hoff));
-    TRY(dupload(&pool, rooff, m * 8, &d_ooff));
-    TRY(dalloc(&pool, (size_t) obytes, &d_out));
-    TRY(dx_pack2_encode(j->ctx, j->arrow ? DX_ALPHA_ARROW : DX_ALPHA_BASES, d_text, d_off, d_tlen, d_nsym, m,
-                        d_hdr, d_hoff, d_out, d_ooff));
-    TRY(dx_d2h(j->ctx, j->img + o0, d_out, (size_t) obytes));
-  }
-done:
-  dfree_all(&pool);
-  free(roff); free(rhoff); free(rooff);
-  j->rc = rc;
+{ p2_job *j = (p2_job *) arg;
+  j->rc = pack2_range(j->ctx, j->arrow, j->text, j->ix, j->lo, j->hi, j->img);
   return NULL;
 }
 
 int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *text, size_t n,
                           uint8_t **out, size_t *out_len, uint64_t *errline, int *errcode)
-{ uint64_t  cnt = 0, i, *off = NULL, *hoff = NULL, *ooff = NULL;
-  uint32_t *tlen = NULL, *nsym = NULL;
-  int32_t  *hdr4 = NULL, lwell = 0;
-  uint16_t *cnr4 = NULL;
-  uint8_t  *blob = NULL, *img = NULL;
-  size_t    plen = 0, at;
+{ seq_index ix;
+  int32_t   lwell = 0;
+  uint8_t  *img = NULL;
   p2_job   *jobs = NULL;
   pthread_t *th = NULL;
   int       rc, k, started = 0;
@@ -503,48 +509,25 @@ int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *tex
   if (ctxs == NULL || nctx < 1 || out == NULL || out_len == NULL) return DX_E_ARG;
   if (nctx == 1) return dx_file_pack2(ctxs[0], arrow, text, n, out, out_len, errline, errcode);
   *out = NULL; *out_len = 0;
+  memset(&ix, 0, sizeof(ix));
 
-  TRY(dx_index_seq(arrow, text, n, 0, NULL, NULL, NULL, NULL, NULL, &cnt, &plen, errline, errcode));
-  off  = malloc((cnt + 1) * sizeof(*off));
-  tlen = malloc((cnt + 1) * sizeof(*tlen));
-  nsym = malloc((cnt + 1) * sizeof(*nsym));
-  hdr4 = malloc((cnt + 1) * 4 * sizeof(*hdr4));
-  cnr4 = malloc((cnt + 1) * 4 * sizeof(*cnr4));
-  hoff = malloc((cnt + 1) * sizeof(*hoff));
-  ooff = malloc((cnt + 1) * sizeof(*ooff));
-  if (!off || !tlen || !nsym || !hdr4 || !cnr4 || !hoff || !ooff) { rc = DX_E_NOMEM; goto done; }
-  TRY(dx_index_seq(arrow, text, n, cnt, off, tlen, nsym, hdr4, cnr4, &cnt, &plen, errline, errcode));
-  blob = malloc(dx_frame_bound(hdr4, cnt, 0, arrow) + 16);
-  if (!blob) { rc = DX_E_NOMEM; goto done; }
-  TRY(dx_frame_headers(hdr4, cnr4, cnt, arrow, &lwell, blob, hoff));     /* one pass: well deltas chain over the whole file */
-
-  at = 2 + 4 + plen;
-  for (i = 0; i < cnt; i++)
-    { ooff[i] = at;
-      at += (size_t) (hoff[i+1] - hoff[i]) + (((size_t) nsym[i] + 3) >> 2);
-    }
-  ooff[cnt] = at;
-  img = malloc(at + 16);
+  TRY(seq_index_host(&ix, arrow, text, n, errline, errcode));
+  TRY(seq_index_frame(&ix, arrow, &lwell, 2 + 4 + ix.plen));             /* one pass: well deltas chain over the whole file */
+  img = malloc(ix.total + 16);
   if (!img) { rc = DX_E_NOMEM; goto done; }
-  { uint16_t key = 0x55aa;
-    int32_t  pl  = (int32_t) plen;
-    memcpy(img, &key, 2);
-    memcpy(img + 2, &pl, 4);
-    memcpy(img + 6, text, plen);
-  }
+  pack2_head(img, text, ix.plen);
 
   jobs = calloc((size_t) nctx, sizeof(*jobs));
   th   = calloc((size_t) nctx, sizeof(*th));
   if (!jobs || !th) { rc = DX_E_NOMEM; goto done; }
   { uint64_t lo = 0;
-    const uint64_t tbytes = cnt ? off[cnt - 1] + tlen[cnt - 1] - off[0] : 0;
+    const uint64_t tbytes = ix.cnt ? ix.off[ix.cnt - 1] + ix.tlen[ix.cnt - 1] - ix.off[0] : 0;
     for (k = 0; k < nctx; k++)
       { uint64_t hi = lo;
-        const uint64_t want = off[0] + tbytes / (uint64_t) nctx * (uint64_t) (k + 1);
-        if (k == nctx - 1) hi = cnt;
-        else while (hi < cnt && off[hi] < want) hi++;
-        jobs[k].ctx = ctxs[k]; jobs[k].arrow = arrow; jobs[k].text = text; jobs[k].off = off; jobs[k].ooff = ooff;
-        jobs[k].hoff = hoff; jobs[k].tlen = tlen; jobs[k].nsym = nsym; jobs[k].blob = blob; jobs[k].img = img;
+        const uint64_t want = ix.off[0] + tbytes / (uint64_t) nctx * (uint64_t) (k + 1);
+        if (k == nctx - 1) hi = ix.cnt;
+        else while (hi < ix.cnt && ix.off[hi] < want) hi++;
+        jobs[k].ctx = ctxs[k]; jobs[k].arrow = arrow; jobs[k].text = text; jobs[k].ix = &ix; jobs[k].img = img;
         jobs[k].lo = lo; jobs[k].hi = hi;
         lo = hi;
       }
@@ -560,11 +543,11 @@ int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *tex
   for (k = 0; k < nctx; k++)
     if (jobs[k].rc != DX_OK) { rc = jobs[k].rc; break; }
   if (rc == DX_OK)
-    { *out = img; *out_len = at; img = NULL; }
+    { *out = img; *out_len = ix.total; img = NULL; }
 
 done:
-  free(off); free(hoff); free(ooff); free(tlen); free(nsym); free(hdr4); free(cnr4); free(blob); free(img);
-  free(jobs); free(th);
+  seq_index_free(&ix);
+  free(img); free(jobs); free(th);
   return rc;
 }
 
@@ -601,6 +584,7 @@ typedef struct
   { uint64_t n; const uint64_t *ooff, *hat; const char *hd;
     dx_sink_fn sink; void *user;
     size_t base;                  /* where in the text the streamed buffer starts (a slice of the entries; else 0) */
+    size_t total;                 /* the whole text's bytes */
   } hdr_patch;
 
 static int patch_and_pass(void *arg, uint8_t *data, size_t len, size_t at0)
@@ -621,15 +605,23 @@ static int patch_and_pass(void *arg, uint8_t *data, size_t len, size_t at0)
   return h->sink(h->user, data, len, at);
 }
 
+/* where entry i's header line starts in the text (i == n: where the text ends) */
+static size_t text_at(const hdr_patch *h, uint64_t i)
+{ return i < h->n ? (size_t) h->ooff[i] - (size_t) (h->hat[i + 1] - h->hat[i]) : h->total; }
+
+/* a slice of whole entries from i0 on: as many as make at most `cap` bytes of text, and one at least */
+static uint64_t text_slice_end(const hdr_patch *h, uint64_t i0, size_t cap)
+{ uint64_t i1 = i0 + 1;
+  while (i1 < h->n && text_at(h, i1 + 1) - text_at(h, i0) <= cap) i1++;
+  return i1;
+}
+
 /* how much of an output of `total` bytes the device makes at once beside an input of n bytes (and 48 bytes of index a unit): 0 = all
    of it; DEXGPU_TEXT_BUDGET (bytes) when set, else what is free decides */
 static size_t out_cap(dx_ctx *ctx, size_t n, size_t total, uint64_t units)
-{ const char *e = getenv("DEXGPU_TEXT_BUDGET");
-  uint64_t fr = 0, all = 0;
-  if (e != NULL && *e)
-    { const unsigned long long v = strtoull(e, NULL, 10);
-      return v && v < total ? (size_t) (v < 65536u ? 65536u : v) : 0;
-    }
+{ uint64_t fr = 0, all = 0;
+  size_t   cap;
+  if (budget_env(total, 65536u, &cap)) return cap;
   if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
   if ((double) n + (double) total + 48.0 * (double) units <= 0.9 * (double) fr) return 0;
   { const double room = 0.9 * (double) fr - (double) n - 48.0 * (double) units;
@@ -778,12 +770,10 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
     if (cnt > 0 && cap)
       { uint64_t *rel = NULL, i0, i1, most = 0;
         size_t    tmax = 0;
-        hdr_patch h = { cnt, ooff, hat, hd.p, sink, user, 0 };
-#define TEXT_AT(i) ((i) < cnt ? (size_t) ooff[i] - (size_t) (hat[(i) + 1] - hat[i]) : total)
+        hdr_patch h = { cnt, ooff, hat, hd.p, sink, user, 0, total };
         for (i0 = 0; i0 < cnt; i0 = i1)
-          { i1 = i0 + 1;
-            while (i1 < cnt && TEXT_AT(i1 + 1) - TEXT_AT(i0) <= cap) i1++;
-            if (TEXT_AT(i1) - TEXT_AT(i0) > tmax) tmax = TEXT_AT(i1) - TEXT_AT(i0);
+          { i1 = text_slice_end(&h, i0, cap);
+            if (text_at(&h, i1) - text_at(&h, i0) > tmax) tmax = text_at(&h, i1) - text_at(&h, i0);
             if (i1 - i0 > most) most = i1 - i0;
           }
         rel = malloc((most + 1) * sizeof(*rel));
@@ -794,24 +784,22 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
         if (rc == DX_OK) rc = dalloc(&pool, (most + 1) * 8, &d_ooff);
         if (rc == DX_OK) rc = dalloc(&pool, tmax, &d_out);
         for (i0 = 0; i0 < cnt && rc == DX_OK; i0 = i1)
-          { const size_t t0 = TEXT_AT(i0);
-            i1 = i0 + 1;
-            while (i1 < cnt && TEXT_AT(i1 + 1) - t0 <= cap) i1++;
+          { const size_t t0 = text_at(&h, i0);
+            i1 = text_slice_end(&h, i0, cap);
             for (i = i0; i < i1; i++) rel[i - i0] = ooff[i] - t0;
             rc = dx_h2d(ctx, d_ooff, rel, (i1 - i0) * 8);
             if (rc == DX_OK)
               rc = dx_pack2_decode(ctx, mode, d_in, (const uint64_t *) d_ioff + i0, (const uint32_t *) d_nsym + i0, i1 - i0, width, d_out, d_ooff);
             if (rc == DX_OK && out)
-              { rc = dx_d2h(ctx, res + t0, d_out, TEXT_AT(i1) - t0);
+              { rc = dx_d2h(ctx, res + t0, d_out, text_at(&h, i1) - t0);
                 for (i = i0; i < i1 && rc == DX_OK; i++)
                   memcpy(res + ooff[i] - (hat[i+1] - hat[i]), hd.p + hat[i], (size_t) (hat[i+1] - hat[i]));
               }
             else if (rc == DX_OK)
               { h.base = t0;
-                rc = dx_d2h_stream(ctx, d_out, TEXT_AT(i1) - t0, patch_and_pass, &h);
+                rc = dx_d2h_stream(ctx, d_out, text_at(&h, i1) - t0, patch_and_pass, &h);
               }
           }
-#undef TEXT_AT
         free(rel);
         if (rc != DX_OK) goto done;
         cnt = 0;                                          /* (done: nothing left for the one-shot path below) */
@@ -830,7 +818,7 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
             memcpy(res + ooff[i] - (hat[i+1] - hat[i]), hd.p + hat[i], (size_t) (hat[i+1] - hat[i]));
         }
       else
-        { hdr_patch h = { cnt, ooff, hat, hd.p, sink, user, 0 };
+        { hdr_patch h = { cnt, ooff, hat, hd.p, sink, user, 0, total };
           TRY(dx_d2h_stream(ctx, d_out, total, patch_and_pass, &h));
         }
     }
@@ -859,11 +847,6 @@ int dx_file_unpack2_to(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint
 /* undexta / undexar of an image that arrives in pieces (a pipe: undexta -i, undexta.c:175-271 reads record after record): `chunk`
    bytes at a time from rd(), the whole records among them unpacked on the device, their text handed to the sink in file order, the
    rest (a record the chunk cuts) moved to the buffer's front.  The same bytes as dx_file_unpack2 of the whole image. */
-typedef struct { dx_sink_fn sink; void *user; size_t shift; } u2_shift;
-static int u2_pass(void *arg, uint8_t *data, size_t len, size_t at)
-{ u2_shift *h = arg;
-  return h->sink(h->user, data, len, at + h->shift);
-}
 
 int dx_file_unpack2_stream(dx_ctx *ctx, int mode, dx_read_fn rd_, void *ruser, size_t chunk, uint32_t width,
                            dx_sink_fn sink, void *suser, size_t *out_len)
@@ -881,7 +864,7 @@ int dx_file_unpack2_stream(dx_ctx *ctx, int mode, dx_read_fn rd_, void *ruser, s
   if (out_len) *out_len = 0;
   for (;;)
     { size_t piece = 0;
-      u2_shift h = { sink, suser, total };
+      shifted_sink h = { sink, suser, total };
       while (!eof && have < chunk)
         { const long got = rd_(ruser, buf + have, chunk - have);
           if (got < 0) { rc = DX_E_IO; goto done; }
@@ -889,7 +872,7 @@ int dx_file_unpack2_stream(dx_ctx *ctx, int mode, dx_read_fn rd_, void *ruser, s
           have += (size_t) got;
         }
       st.more = !eof;
-      rc = unpack2_core(ctx, mode, buf, have, width, NULL, u2_pass, &h, &piece, &st);
+      rc = unpack2_core(ctx, mode, buf, have, width, NULL, pass_shifted, &h, &piece, &st);
       if (rc != DX_OK) goto done;
       total += piece;
       if (eof) break;                                    /* (the last piece: whole, or the core has said DX_E_FORMAT) */
@@ -914,13 +897,110 @@ done:
 /* ==========================================================================================
  *  dexqv
  * ========================================================================================== */
-/* a sink that sees its chunks `shift` bytes further on (the record stream follows the file's head) */
-typedef struct { dx_sink_fn sink; void *user; size_t shift; } shifted_sink;
-static int pass_shifted(void *arg, uint8_t *data, size_t len, size_t at)
-{ shifted_sink *h = arg;
-  return h->sink(h->user, data, len, at + h->shift);
+/* The host's index of a .quiva text (dx_index_quiva): per entry where its five lines begin, how long they are, the header's four fields */
+typedef struct { uint64_t cnt, *off; uint32_t *len; int32_t *hdr4; size_t plen; } quiva_index;
+
+static int quiva_index_host(quiva_index *qx, const uint8_t *text, size_t n, uint64_t *errline, int *errcode)
+{ const int rc = dx_index_quiva(text, n, 0, NULL, NULL, NULL, &qx->cnt, &qx->plen, errline, errcode);
+  if (rc != DX_OK) return rc;
+  if (qx->cnt == 0) return DX_E_DEGENERATE;              /* empty file: the reference dereferences a NULL header (dexqv.c:94) */
+  qx->off  = malloc((qx->cnt + 1) * sizeof(*qx->off));
+  qx->len  = malloc((qx->cnt + 1) * sizeof(*qx->len));
+  qx->hdr4 = malloc((qx->cnt + 1) * 4 * sizeof(*qx->hdr4));
+  if (!qx->off || !qx->len || !qx->hdr4) return DX_E_NOMEM;
+  return dx_index_quiva(text, n, qx->cnt, qx->off, qx->len, qx->hdr4, &qx->cnt, &qx->plen, errline, errcode);
 }
 
+static void quiva_index_free(quiva_index *qx)
+{ free(qx->off); free(qx->len); free(qx->hdr4); }
+
+/* where entry e's five lines end in the text */
+static uint64_t quiva_end(const quiva_index *qx, uint64_t e)
+{ return qx->off[e] + 5 * ((uint64_t) qx->len[e] + 1); }
+
+/* a slice of whole entries from e0 on: as many as make at most `cap` bytes of text (an entry larger than the cap is a slice of its own) */
+static uint64_t quiva_slice_end(const quiva_index *qx, uint64_t e0, size_t cap)
+{ const uint64_t s0 = e0 ? quiva_end(qx, e0 - 1) : 0;
+  uint64_t e1 = e0 + 1;
+  while (e1 < qx->cnt && quiva_end(qx, e1) - s0 <= cap) e1++;
+  return e1;
+}
+
+static dx_qv_batch qv_batch(const void *d_text, const void *d_off, const void *d_len, uint64_t m, uint64_t span, int line_pad)
+{ dx_qv_batch b;
+  memset(&b, 0, sizeof(b));
+  b.d_text = d_text; b.d_off = d_off; b.d_len = d_len; b.n = m; b.line_pad = (uint32_t) line_pad; b.text_bytes = span;
+  return b;
+}
+
+/* A batch of entries as the encoder wants it: the text (b), the framing bytes of the headers and their offsets (none of either for the bare
+   record stream of the entry API), and the per-entry record offsets and segment sizes the encoder fills */
+typedef struct { dx_qv_batch b; void *d_hdr, *d_hoff, *d_rec, *d_seg; uint64_t hbytes; } qv_staged;
+
+/* m entries whose text is on the device (span bytes at d_text) staged in `pool`: their header fields hdr4 framed from *lwell on (the well
+   chain runs through a file's batches) and uploaded; hdr4 == NULL: no framing bytes */
+static int qv_stage(dpool *pool, const int32_t *hdr4, uint64_t m, int32_t *lwell, const void *d_text, const void *d_off, const void *d_len,
+                    uint64_t span, int line_pad, qv_staged *s)
+{ uint64_t *hoff = NULL;
+  uint8_t  *blob = NULL;
+  int       rc;
+  memset(s, 0, sizeof(*s));
+  s->b = qv_batch(d_text, d_off, d_len, m, span, line_pad);
+  if (hdr4 != NULL)
+    { hoff = malloc((m + 1) * sizeof(*hoff));
+      blob = malloc(dx_frame_bound(hdr4, m, *lwell, 0) + 16);
+      if (!hoff || !blob) { rc = DX_E_NOMEM; goto done; }
+      TRY(dx_frame_headers(hdr4, NULL, m, 0, lwell, blob, hoff));
+      TRY(dupload(pool, blob, (size_t) hoff[m], &s->d_hdr));
+      TRY(dupload(pool, hoff, (m + 1) * 8, &s->d_hoff));
+      s->hbytes = hoff[m];
+    }
+  TRY(dalloc(pool, (m + 1) * 8, &s->d_rec));
+  TRY(dalloc(pool, m * 5 * 4, &s->d_seg));
+done:
+  free(hoff); free(blob);
+  return rc;
+}
+
+/* Compress_Next_QVentry for a staged batch (dexqv.c:112-143) under the coding in force (cd): the records into *d_out, *total bytes of them.
+   `hist` is what dx_qv_hist counted for THIS batch: it bounds the output.  *d_out holds *out_cap bytes (none yet: NULL, 0) and is made
+   anew only when that is too few, so a caller with batch after batch keeps one buffer; it is the caller's to dx_free. */
+static int qv_encode_batch(dx_ctx *ctx, const qv_staged *s, const uint64_t (*hist)[256], const dx_qv_coding *cd, int lossy,
+                           void **d_out, size_t *out_cap, uint64_t *total)
+{ const int twice = two_pass();
+  uint64_t  need;
+  int       rc;
+  if (twice) TRY(dx_qv_sizes(ctx, &s->b, s->d_hoff, s->d_seg, s->d_rec, &need));
+  else       need = s->hbytes + dx_qv_out_bound(hist, s->b.n, cd, lossy);
+  if (need > *out_cap || *d_out == NULL)
+    { if (*d_out != NULL) { (void) dx_free(ctx, *d_out); *d_out = NULL; }
+      *out_cap = 0;
+      TRY(dx_malloc(ctx, (size_t) need + 64, d_out));
+      *out_cap = (size_t) need;
+    }
+  if (twice)
+    { TRY(dx_qv_encode(ctx, &s->b, s->d_hdr, s->d_hoff, s->d_rec, s->d_seg, *d_out));
+      *total = need;
+    }
+  else
+    TRY(dx_qv_encode_onepass(ctx, &s->b, s->d_hdr, s->d_hoff, s->d_seg, s->d_rec, *d_out, *out_cap, total));
+done:
+  return rc;
+}
+
+/* the head of a .dexqv image, dexqv.c:105-108: the key and the coding (Write_QVcoding; the prefix is the text's first plen bytes).
+   *img: malloc'd, `head` bytes written, room for `more` behind them */
+static int qv_head(const dx_qv_coding *cd, const uint8_t *text, size_t plen, size_t more, uint8_t **img, size_t *head)
+{ const uint16_t key = 0x55aa;
+  size_t clen = 0;
+  int    rc = dx_qv_write_coding(cd, (const char *) text, plen, NULL, 0, &clen);            /* size of Write_QVcoding */
+  if (rc != DX_OK && rc != DX_E_SPACE) return rc;
+  *head = 2 + clen;
+  *img  = malloc(*head + more + 16);
+  if (*img == NULL) return DX_E_NOMEM;
+  memcpy(*img, &key, 2);
+  return dx_qv_write_coding(cd, (const char *) text, plen, *img + 2, clen, &clen);
+}
 
 /* ---- a .quiva image larger than the device (or than DEXGPU_TEXT_BUDGET): slices of whole entries -------------------
  * The reference streams a file of any size through two passes (dexqv.c:81-82, 112-143).  Here: the host index of the
@@ -929,7 +1009,7 @@ static int pass_shifted(void *arg, uint8_t *data, size_t len, size_t at)
  *           dx_qv_hist (adds into the file's histograms);
  *   tables, the file's head (key + coding) out;
  *   pass 2: upload again, dx_qv_hist once more (for the tokens of THIS slice under the final scan state; its counts go
- *           nowhere), dx_qv_encode_onepass, the slice's records out behind the last slice's.
+ *           nowhere), the encoder (qv_encode_batch), the slice's records out behind the last slice's.
  * A slice is bound by the host link (two uploads of the text at ~50 GB/s against kernels at ~1.7 TB/s), so the second
  * histogram pass costs nothing that shows.  The well chain of the framing bytes runs through the slices.          */
 typedef struct { uint8_t *p; size_t n, cap; } grow_sink;
@@ -948,105 +1028,69 @@ static int grow_take(void *arg, uint8_t *data, size_t len, size_t at)
 
 static int dexqv_sliced(dx_ctx *ctx, const uint8_t *text, size_t n, int lossy, size_t cap, uint8_t **out, dx_sink_fn sink, void *user,
                         size_t *out_len, uint64_t *errline, int *errcode)
-{ dpool        pool = { {0}, 0, ctx };
-  uint64_t     cnt = 0, *off = NULL, *hoff = NULL, *rel = NULL, tot = 0, e0, at;
-  uint32_t    *len = NULL;
-  int32_t     *hdr4 = NULL, lwell = 0;
-  uint8_t     *blob = NULL, *head_img = NULL;
-  size_t       plen = 0, clen = 0, head = 0, maxent = 0, slice_bytes = 0;
+{ dpool        pool = { {0}, 0, ctx }, spool = { {0}, 0, ctx };       /* spool: what lives for one slice */
+  quiva_index  qx = { 0, NULL, NULL, NULL, 0 };
+  uint64_t    *rel = NULL, tot = 0, e0, e1, at = 0;
+  int32_t      lwell = 0;
+  uint8_t     *head_img = NULL;
+  size_t       head = 0, maxent = 0, slice_bytes = 0, out_cap = 0;
   dx_qv_params p = { -1, -1, -1, -1 };
   dx_qv_coding *cd = NULL;
   uint64_t   (*hist)[256] = NULL, (*junk)[256] = NULL;
-  void        *d_text = NULL, *d_off = NULL, *d_len = NULL, *d_hdr = NULL, *d_hoff = NULL, *d_rec = NULL, *d_seg = NULL, *d_out = NULL;
-  size_t       out_cap = 0;
+  void        *d_text = NULL, *d_off = NULL, *d_len = NULL, *d_out = NULL;
   grow_sink    grow = { NULL, 0, 0 };
   int          rc, pass, was_threads = 0;
 
   if (out) { sink = grow_take; user = &grow; was_threads = dx_set_sink_threads(ctx, 1); }     /* (grow_take wants its chunks in order) */
   cd = malloc(sizeof(*cd)); hist = calloc(6, sizeof(*hist)); junk = calloc(6, sizeof(*junk));
   if (!cd || !hist || !junk) { rc = DX_E_NOMEM; goto done; }
-  TRY(dx_index_quiva(text, n, 0, NULL, NULL, NULL, &cnt, &plen, errline, errcode));
-  if (cnt == 0) { rc = DX_E_DEGENERATE; goto done; }
-  off = malloc((cnt + 1) * sizeof(*off)); len = malloc((cnt + 1) * sizeof(*len)); hdr4 = malloc((cnt + 1) * 4 * sizeof(*hdr4));
-  if (!off || !len || !hdr4) { rc = DX_E_NOMEM; goto done; }
-  TRY(dx_index_quiva(text, n, cnt, off, len, hdr4, &cnt, &plen, errline, errcode));
-  /* the widest slice in entries and bytes under the cap (an entry larger than the cap is a slice of its own) */
-  for (e0 = 0; e0 < cnt; )
-    { const uint64_t s0 = e0 ? off[e0 - 1] + 5 * ((uint64_t) len[e0 - 1] + 1) : 0;
-      uint64_t e1 = e0 + 1;
-      while (e1 < cnt && off[e1] + 5 * ((uint64_t) len[e1] + 1) - s0 <= cap) e1++;
+  TRY(quiva_index_host(&qx, text, n, errline, errcode));
+  for (e0 = 0; e0 < qx.cnt; e0 = e1)                      /* the widest slice in entries and bytes: one allocation serves them all */
+    { const uint64_t s0 = e0 ? quiva_end(&qx, e0 - 1) : 0;
+      e1 = quiva_slice_end(&qx, e0, cap);
       if (e1 - e0 > maxent) maxent = (size_t) (e1 - e0);
-      if (off[e1 - 1] + 5 * ((uint64_t) len[e1 - 1] + 1) - s0 > slice_bytes) slice_bytes = (size_t) (off[e1 - 1] + 5 * ((uint64_t) len[e1 - 1] + 1) - s0);
-      e0 = e1;
+      if (quiva_end(&qx, e1 - 1) - s0 > slice_bytes) slice_bytes = (size_t) (quiva_end(&qx, e1 - 1) - s0);
     }
-  hoff = malloc((maxent + 1) * sizeof(*hoff)); rel = malloc((maxent + 1) * sizeof(*rel));
-  if (!hoff || !rel) { rc = DX_E_NOMEM; goto done; }
+  rel = malloc((maxent + 1) * sizeof(*rel));
+  if (!rel) { rc = DX_E_NOMEM; goto done; }
   TRY(dalloc(&pool, slice_bytes, &d_text));
   TRY(dalloc(&pool, (maxent + 1) * 8, &d_off));
   TRY(dalloc(&pool, (maxent + 1) * 4, &d_len));
-  TRY(dalloc(&pool, (maxent + 1) * 8, &d_hoff));
-  TRY(dalloc(&pool, (maxent + 1) * 8, &d_rec));
-  TRY(dalloc(&pool, maxent * 5 * 4 + 64, &d_seg));
 
-  at = 0;
   for (pass = 1; pass <= 2; pass++)
     { if (pass == 2)
         { TRY(dx_qv_build((const uint64_t (*)[256]) hist, tot, &p, lossy, cd));          /* Create_QVcoding, dexqv.c:86 */
           TRY(dx_qv_set_coding(ctx, cd, lossy));
-          rc = dx_qv_write_coding(cd, (const char *) text, plen, NULL, 0, &clen);
-          if (rc != DX_OK && rc != DX_E_SPACE) goto done;
-          head = 2 + clen;
-          head_img = malloc(head + 16);
-          if (!head_img) { rc = DX_E_NOMEM; goto done; }
-          { uint16_t key = 0x55aa;                                                       /* dexqv.c:105-108 */
-            memcpy(head_img, &key, 2);
-            TRY(dx_qv_write_coding(cd, (const char *) text, plen, head_img + 2, clen, &clen));
-          }
+          TRY(qv_head(cd, text, qx.plen, 0, &head_img, &head));
           if (sink(user, head_img, head, 0)) { rc = DX_E_IO; goto done; }
           at = head;
         }
-      for (e0 = 0; e0 < cnt; )
-        { const uint64_t s0 = e0 ? off[e0 - 1] + 5 * ((uint64_t) len[e0 - 1] + 1) : 0;
-          uint64_t e1 = e0 + 1, s1, k, m, total = 0;
+      for (e0 = 0; e0 < qx.cnt; e0 = e1)
+        { const uint64_t s0 = e0 ? quiva_end(&qx, e0 - 1) : 0;
+          uint64_t s1, k, m, total = 0;
           dx_qv_batch b;
-          while (e1 < cnt && off[e1] + 5 * ((uint64_t) len[e1] + 1) - s0 <= cap) e1++;
-          s1 = off[e1 - 1] + 5 * ((uint64_t) len[e1 - 1] + 1);
+          e1 = quiva_slice_end(&qx, e0, cap);
+          s1 = quiva_end(&qx, e1 - 1);
           m  = e1 - e0;
-          for (k = 0; k < m; k++) rel[k] = off[e0 + k] - s0;
+          for (k = 0; k < m; k++) rel[k] = qx.off[e0 + k] - s0;
           TRY(dx_h2d(ctx, d_text, text + s0, (size_t) (s1 - s0)));
           TRY(dx_h2d(ctx, d_off, rel, (size_t) m * 8));
-          TRY(dx_h2d(ctx, d_len, len + e0, (size_t) m * 4));
-          b.d_text = d_text; b.d_off = d_off; b.d_len = d_len; b.n = m; b.line_pad = 1; b.text_bytes = s1 - s0;
+          TRY(dx_h2d(ctx, d_len, qx.len + e0, (size_t) m * 4));
+          b = qv_batch(d_text, d_off, d_len, m, s1 - s0, 1);
           if (pass == 1)
             TRY(dx_qv_scan(ctx, &b, e0, &p, hist, &tot));                               /* QV.c:993-1017, state carried along */
           else
-            { uint64_t t2 = 0, bound;
-              size_t   bb;
+            { uint64_t  t2 = 0;
+              qv_staged st;
+              shifted_sink h = { sink, user, (size_t) at };
               memset(junk, 0, 6 * sizeof(*junk));
               TRY(dx_qv_hist(ctx, &b, e0, &p, junk, &t2));                               /* this slice's tokens (and its own counts, for the bound) */
-              bb = dx_frame_bound(hdr4 + 4 * e0, m, lwell, 0) + 16;
-              { uint8_t *nb = realloc(blob, bb);
-                if (nb == NULL) { rc = DX_E_NOMEM; goto done; }
-                blob = nb;
-              }
-              TRY(dx_frame_headers(hdr4 + 4 * e0, NULL, m, 0, &lwell, blob, hoff));
-              if (d_hdr) { dx_free(ctx, d_hdr); d_hdr = NULL; }
-              TRY(dx_malloc(ctx, (size_t) hoff[m] + 64, &d_hdr));
-              TRY(dx_h2d(ctx, d_hdr, blob, (size_t) hoff[m]));
-              TRY(dx_h2d(ctx, d_hoff, hoff, (size_t) (m + 1) * 8));
-              bound = hoff[m] + dx_qv_out_bound((const uint64_t (*)[256]) junk, m, cd, lossy);
-              if (bound > out_cap)
-                { if (d_out) { dx_free(ctx, d_out); d_out = NULL; }
-                  TRY(dx_malloc(ctx, (size_t) bound + 64, &d_out));
-                  out_cap = (size_t) bound;
-                }
-              TRY(dx_qv_encode_onepass(ctx, &b, d_hdr, d_hoff, d_seg, d_rec, d_out, out_cap, &total));
-              { shifted_sink h = { sink, user, (size_t) at };
-                TRY(dx_d2h_stream(ctx, d_out, total, pass_shifted, &h));
-              }
+              TRY(qv_stage(&spool, qx.hdr4 + 4 * e0, m, &lwell, d_text, d_off, d_len, s1 - s0, 1, &st));
+              TRY(qv_encode_batch(ctx, &st, (const uint64_t (*)[256]) junk, cd, lossy, &d_out, &out_cap, &total));
+              TRY(dx_d2h_stream(ctx, d_out, total, pass_shifted, &h));
               at += total;
+              dfree_all(&spool);
             }
-          e0 = e1;
         }
     }
   *out_len = (size_t) at;
@@ -1055,23 +1099,21 @@ static int dexqv_sliced(dx_ctx *ctx, const uint8_t *text, size_t n, int lossy, s
 
 done:
   if (was_threads) (void) dx_set_sink_threads(ctx, was_threads);
-  if (d_hdr) dx_free(ctx, d_hdr);
   if (d_out) dx_free(ctx, d_out);
+  dfree_all(&spool);
   dfree_all(&pool);
   (void) dx_trim(ctx, DX_TRIM_TOKENS);                     /* (a slice's tokens must not meet another batch that looks like it) */
-  free(off); free(hoff); free(rel); free(len); free(hdr4); free(blob); free(cd); free(hist); free(junk); free(head_img); free(grow.p);
+  quiva_index_free(&qx);
+  free(rel); free(cd); free(hist); free(junk); free(head_img); free(grow.p);
   return rc;
 }
 
 /* how much text the device takes at once: DEXGPU_TEXT_BUDGET (bytes) when set, else what fits beside the tokens, the scratch
    regions and the output (about 2.5 bytes of device memory per byte of text), 0 = all of it */
 static size_t text_cap(dx_ctx *ctx, size_t n)
-{ const char *e = getenv("DEXGPU_TEXT_BUDGET");
-  uint64_t fr = 0, all = 0;
-  if (e != NULL && *e)
-    { const unsigned long long v = strtoull(e, NULL, 10);
-      return v && v < n ? (size_t) (v < (4u << 20) ? (4u << 20) : v) : 0;
-    }
+{ uint64_t fr = 0, all = 0;
+  size_t   cap;
+  if (budget_env(n, (size_t) 4 << 20, &cap)) return cap;
   if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
   return (double) n * 2.5 > (double) fr ? (size_t) (fr / 3) : 0;
 }
@@ -1083,16 +1125,16 @@ static int dexqv_core(dx_ctx *ctx, const uint8_t *text, int fd, size_t n, int lo
                       size_t *out_len, uint64_t *errline, int *errcode)
 { dpool        pool = { {0}, 0, ctx };
   uint8_t      headbuf[4096];
-  uint64_t     cnt = 0, *off = NULL, *hoff = NULL, total = 0, tot = 0;
-  uint32_t    *len = NULL;
-  int32_t     *hdr4 = NULL, lwell = 0;
-  uint8_t     *blob = NULL, *img = NULL;
-  size_t       plen = 0, clen = 0, head;
-  dx_qv_batch  b;
+  quiva_index  qx = { 0, NULL, NULL, NULL, 0 };
+  uint64_t     total = 0, tot = 0;
+  int32_t      lwell = 0;
+  uint8_t     *img = NULL;
+  size_t       head = 0, out_cap = 0;
+  qv_staged    st;
   dx_qv_params p = { -1, -1, -1, -1 };
   dx_qv_coding *cd = NULL;
   uint64_t   (*hist)[256] = NULL;
-  void        *d_text, *d_off = NULL, *d_len = NULL, *d_hdr, *d_hoff, *d_rec, *d_seg, *d_out;
+  void        *d_text, *d_off = NULL, *d_len = NULL, *d_out = NULL;
   int          rc;
 
   if (ctx == NULL || (out == NULL && sink == NULL) || out_len == NULL) return DX_E_ARG;
@@ -1126,8 +1168,8 @@ static int dexqv_core(dx_ctx *ctx, const uint8_t *text, int fd, size_t n, int lo
   fmark("dexqv: text on the device");
   if (n >= DX_GPU_INDEX_MIN && !dx_test_on("host_index"))
     { uint64_t *go = NULL; uint32_t *gl = NULL;
-      rc = dx_index_quiva_device(ctx, d_text, n, &go, &gl, &cnt, &hdr4, &plen, errline, errcode);
-      if (rc == DX_OK && cnt > 0)
+      rc = dx_index_quiva_device(ctx, d_text, n, &go, &gl, &qx.cnt, &qx.hdr4, &qx.plen, errline, errcode);
+      if (rc == DX_OK && qx.cnt > 0)
         { d_off = go; d_len = gl;
           pool.p[pool.n++] = go; pool.p[pool.n++] = gl;
         }
@@ -1138,69 +1180,28 @@ static int dexqv_core(dx_ctx *ctx, const uint8_t *text, int fd, size_t n, int lo
       rc = DX_OK;
     }
   if (text == NULL)
-    { if (plen >= sizeof(headbuf)) { rc = DX_E_AGAIN; goto done; }
+    { if (qx.plen >= sizeof(headbuf)) { rc = DX_E_AGAIN; goto done; }
       text = headbuf;                                     /* (from here on only the prefix is looked at) */
     }
   if (d_off == NULL)
-    { TRY(dx_index_quiva(text, n, 0, NULL, NULL, NULL, &cnt, &plen, errline, errcode));
-      off  = malloc((cnt + 1) * sizeof(*off));
-      len  = malloc((cnt + 1) * sizeof(*len));
-      free(hdr4);
-      hdr4 = malloc((cnt + 1) * 4 * sizeof(*hdr4));
-      if (!off || !len || !hdr4) { rc = DX_E_NOMEM; goto done; }
-      TRY(dx_index_quiva(text, n, cnt, off, len, hdr4, &cnt, &plen, errline, errcode));
-      if (cnt > 0)
-        { TRY(dupload(&pool, off, cnt * 8, &d_off));
-          TRY(dupload(&pool, len, cnt * 4, &d_len));
-        }
-    }
-  if (cnt == 0)
-    { rc = DX_E_DEGENERATE;     /* empty file: the reference dereferences a NULL header (dexqv.c:94) */
-      goto done;
+    { free(qx.hdr4); qx.hdr4 = NULL;
+      TRY(quiva_index_host(&qx, text, n, errline, errcode));
+      TRY(dupload(&pool, qx.off, qx.cnt * 8, &d_off));
+      TRY(dupload(&pool, qx.len, qx.cnt * 4, &d_len));
     }
   fmark("dexqv: indexed");
-  hoff = malloc((cnt + 1) * sizeof(*hoff));
-  if (!hoff) { rc = DX_E_NOMEM; goto done; }
-
-  blob = malloc(dx_frame_bound(hdr4, cnt, 0, 0) + 16);
-  if (!blob) { rc = DX_E_NOMEM; goto done; }
-  TRY(dx_frame_headers(hdr4, NULL, cnt, 0, &lwell, blob, hoff));
-
-  TRY(dupload(&pool, blob, (size_t) hoff[cnt], &d_hdr));
-  TRY(dupload(&pool, hoff, (cnt + 1) * 8, &d_hoff));
-  TRY(dalloc(&pool, (cnt + 1) * 8, &d_rec));
-  TRY(dalloc(&pool, cnt * 5 * 4, &d_seg));
-  b.d_text = d_text; b.d_off = d_off; b.d_len = d_len; b.n = cnt; b.line_pad = 1;
-  b.text_bytes = n;
+  TRY(qv_stage(&pool, qx.hdr4, qx.cnt, &lwell, d_text, d_off, d_len, n, 1, &st));
 
   /* ... and histogram on the device (QV.c:988-1017) */
-  TRY(dx_qv_scan(ctx, &b, 0, &p, hist, &tot));
+  TRY(dx_qv_scan(ctx, &st.b, 0, &p, hist, &tot));
   TRY(dx_qv_build((const uint64_t (*)[256]) hist, tot, &p, lossy, cd));   /* Create_QVcoding, dexqv.c:86 */
   TRY(dx_qv_set_coding(ctx, cd, lossy));
   fmark("dexqv: scanned, tables built");
 
-  rc = dx_qv_write_coding(cd, (const char *) text, plen, NULL, 0, &clen);  /* size of Write_QVcoding */
-  if (rc != DX_OK && rc != DX_E_SPACE) goto done;
-  head = 2 + clen;
-
   /* pass 2, dexqv.c:112-143: Compress_Next_QVentry for every entry */
-  if (!two_pass())
-    { const uint64_t cap = hoff[cnt] + dx_qv_out_bound((const uint64_t (*)[256]) hist, cnt, cd, lossy);
-      TRY(dalloc(&pool, cap, &d_out));
-      TRY(dx_qv_encode_onepass(ctx, &b, d_hdr, d_hoff, d_seg, d_rec, d_out, cap, &total));
-    }
-  else
-    { TRY(dx_qv_sizes(ctx, &b, d_hoff, d_seg, d_rec, &total));
-      TRY(dalloc(&pool, total, &d_out));
-      TRY(dx_qv_encode(ctx, &b, d_hdr, d_hoff, d_rec, d_seg, d_out));
-    }
+  TRY(qv_encode_batch(ctx, &st, (const uint64_t (*)[256]) hist, cd, lossy, &d_out, &out_cap, &total));
   fmark("dexqv: encoded");
-  img = malloc(head + (out ? total : 0) + 16);
-  if (!img) { rc = DX_E_NOMEM; goto done; }
-  { uint16_t key = 0x55aa;                                                 /* dexqv.c:105-108 */
-    memcpy(img, &key, 2);
-    TRY(dx_qv_write_coding(cd, (const char *) text, plen, img + 2, clen, &clen));
-  }
+  TRY(qv_head(cd, text, qx.plen, out ? total : 0, &img, &head));
   if (out)
     { TRY(dx_d2h(ctx, img + head, d_out, total));
       *out = img; img = NULL;
@@ -1215,8 +1216,10 @@ static int dexqv_core(dx_ctx *ctx, const uint8_t *text, int fd, size_t n, int lo
   fmark("dexqv: output passed on");
 
 done:
+  if (d_out) (void) dx_free(ctx, d_out);
   dfree_all(&pool);
-  free(off); free(hoff); free(len); free(hdr4); free(blob); free(cd); free(hist); free(img);
+  quiva_index_free(&qx);
+  free(cd); free(hist); free(img);
   fmark("dexqv: device memory released");
   return rc;
 }
@@ -1297,7 +1300,7 @@ static int plan_layout(dx_undexqv_plan *p)
    threads take 7.5 s), and only the entries' lengths and header fields come back for the header lines.  Whatever the device
    walk does not take -- small images (the host walk is over before the device's tables are up), 16-bit framing fields,
    walks that do not chain up, a damaged stream -- is planned on the host as before (dx_file_undexqv_plan), which also
-   has the words for what is wrong with a file.  DEXGPU_HOST_WALK=1: always on the host.                             */
+   has the words for what is wrong with a file.  DEXGPU_TEST=host_walk: always on the host.                          */
 #define DX_DEVICE_WALK_MIN ((size_t) 256 << 20)
 int dx_file_undexqv_plan_on(dx_ctx *ctx, const uint8_t *img, size_t n, dx_undexqv_plan **plan, size_t *out_len)
 { dx_undexqv_plan *p;
@@ -1373,7 +1376,7 @@ int dx_file_undexqv_plan(const uint8_t *img, size_t n, dx_undexqv_plan **plan, s
   *plan = NULL; *out_len = 0;
   p = calloc(1, sizeof(*p));
   if (p == NULL) return DX_E_NOMEM;
-  /* boundary walk (host).  With DEXGPU_WALK_INDEX set it also leaves the group index the wave-per-line decoders take
+  /* boundary walk (host).  With DEXGPU_TEST=walk_index it also leaves the group index the wave-per-line decoders take
      (dx_qv_use_index below): 31 instead of 50 ms of kernels per 14 GB of records -- but the walk is 45 % longer with it
      and the index is another 30 % to upload, and from file to file that costs more than it saves (undexqv of a 1 GB
      .quiva: 0.54-0.59 s with, 0.44-0.48 s without; profiles/r03c_cli_timing.txt), so it is off unless asked for */
@@ -1421,6 +1424,39 @@ int dx_file_undexqv_plan_index(const dx_undexqv_plan *p, dx_qv_index *x)
   return rc;
 }
 
+/* What a decode of a plan's records reads, on the device: the image and per record its offset, framing offset, segment sizes and length.
+   What the plan has there already (dx_file_undexqv_plan_on) is taken as it is, the rest goes up into `pool`.  in_bytes > 0: the image stays
+   down; d_in and d_rec are buffers for a slice's records, in_bytes of them at most in `most` records.  The coding is set, and the device
+   walk's group index installed when there is one (*indexed: dx_qv_use_index takes it out again, before the plan's arrays go). */
+typedef struct { void *d_in, *d_rec, *d_hoff, *d_seg, *d_len; } undexqv_staged;
+
+static int undexqv_stage(dx_ctx *ctx, const dx_undexqv_plan *p, dpool *pool, size_t in_bytes, uint64_t most, undexqv_staged *s, int *indexed)
+{ const uint64_t n = p->x.n;
+  int rc;
+  TRY(dx_qv_set_coding(ctx, &p->x.coding, 0));
+  if (PLAN_HAS_IMAGE(p)) s->d_in = p->d_in;
+  else if (!in_bytes)    TRY(dupload(pool, p->img, p->n, &s->d_in));
+  else                   TRY(dalloc(pool, in_bytes, &s->d_in));
+  if (PLAN_HAS_INDEX(p))
+    { s->d_rec = p->dix.d_rec_off; s->d_hoff = p->dix.d_hdr_off; s->d_seg = p->dix.d_seg; s->d_len = p->dix.d_len; }
+  else
+    { if (!in_bytes) TRY(dupload(pool, p->x.rec_off, (n + 1) * 8, &s->d_rec));
+      else           TRY(dalloc(pool, (most + 1) * 8, &s->d_rec));
+      TRY(dupload(pool, p->x.hdr_off, (n + 1) * 8, &s->d_hoff));
+      TRY(dupload(pool, p->x.seg, n * 5 * 4, &s->d_seg));
+      TRY(dupload(pool, p->x.len, n * 4, &s->d_len));
+    }
+  if (PLAN_HAS_INDEX(p) && p->dix.d_gidx != NULL && !p->x.flip)     /* the run-coded lines' groups (a slice is a contiguous part of the index) */
+    { TRY(dx_qv_use_dindex(ctx, s->d_in, &p->dix));
+      *indexed = 1;
+    }
+done:
+  return rc;
+}
+
+static int decode_flags(const dx_undexqv_plan *p, int upper)
+{ return (upper ? DX_DECODE_UPPER : 0) | (p->x.flip ? DX_DECODE_FLIP : 0); }
+
 /* ---- a text larger than the device (or than DEXGPU_TEXT_BUDGET): slices of whole entries ------------------------------
  * The reference writes entry after entry (undexqv.c:182-207).  Here: per slice of at most `cap` bytes of text, the slice's
  * records -- the whole image stays on the device when it is there already (a plan made there) or fits beside a slice's text,
@@ -1430,62 +1466,42 @@ static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_s
 { const int whole_in = whole_in_ || PLAN_HAS_IMAGE(p);    /* (an image that is there is there whole) */
   dpool     pool = { {0}, 0, ctx };
   const uint64_t n = p->x.n;
-  void     *d_in = NULL, *d_rec = NULL, *d_hoff = NULL, *d_seg = NULL, *d_len = NULL, *d_out = NULL, *d_ooff = NULL;
+  undexqv_staged s;
+  void     *d_out = NULL, *d_ooff = NULL;
   uint64_t *rel = NULL, i0, i1, i, most = 0;
   size_t    tmax = 0, imax = 0;
-  hdr_patch h;
+  hdr_patch h = { n, p->ooff, p->hat, p->hd.p, sink, user, 0, p->total };
   int       rc = DX_OK, indexed = 0;
-#define TEXT_AT(i) ((i) < n ? (size_t) p->ooff[i] - (size_t) (p->hat[(i) + 1] - p->hat[i]) : p->total)      /* where entry i's header line starts */
-  h.n = n; h.ooff = p->ooff; h.hat = p->hat; h.hd = p->hd.p; h.sink = sink; h.user = user; h.base = 0;
   for (i0 = 0; i0 < n; i0 = i1)                           /* the largest slice: one allocation serves them all */
-    { i1 = i0 + 1;
-      while (i1 < n && TEXT_AT(i1 + 1) - TEXT_AT(i0) <= cap) i1++;
-      if (TEXT_AT(i1) - TEXT_AT(i0) > tmax) tmax = TEXT_AT(i1) - TEXT_AT(i0);
+    { i1 = text_slice_end(&h, i0, cap);
+      if (text_at(&h, i1) - text_at(&h, i0) > tmax) tmax = text_at(&h, i1) - text_at(&h, i0);
       if (i1 - i0 > most) most = i1 - i0;
       if (!whole_in && p->x.rec_off[i1] - p->x.rec_off[i0] > imax) imax = (size_t) (p->x.rec_off[i1] - p->x.rec_off[i0]);
     }
   rel = malloc((most + 1) * 2 * sizeof(*rel));
   if (rel == NULL) return DX_E_NOMEM;
-  TRY(dx_qv_set_coding(ctx, &p->x.coding, 0));
-  if (PLAN_HAS_IMAGE(p))  d_in = p->d_in;
-  else if (whole_in)      TRY(dupload(&pool, p->img, p->n, &d_in));
-  else                    TRY(dalloc(&pool, imax, &d_in));
-  if (PLAN_HAS_INDEX(p))
-    { d_rec = p->dix.d_rec_off; d_hoff = p->dix.d_hdr_off; d_seg = p->dix.d_seg; d_len = p->dix.d_len; }
-  else
-    { if (whole_in) TRY(dupload(&pool, p->x.rec_off, (n + 1) * 8, &d_rec));
-      else          TRY(dalloc(&pool, (most + 1) * 8, &d_rec));
-      TRY(dupload(&pool, p->x.hdr_off, (n + 1) * 8, &d_hoff));
-      TRY(dupload(&pool, p->x.seg, n * 5 * 4, &d_seg));
-      TRY(dupload(&pool, p->x.len, n * 4, &d_len));
-    }
+  TRY(undexqv_stage(ctx, p, &pool, imax, most, &s, &indexed));
   TRY(dalloc(&pool, (most + 1) * 8, &d_ooff));
   TRY(dalloc(&pool, tmax, &d_out));
-  if (PLAN_HAS_IMAGE(p) && PLAN_HAS_INDEX(p) && p->dix.d_gidx != NULL && !p->x.flip)     /* (a slice is a contiguous part of the walk's index) */
-    { TRY(dx_qv_use_dindex(ctx, d_in, &p->dix));
-      indexed = 1;
-    }
   for (i0 = 0; i0 < n; i0 = i1)
-    { const size_t t0 = TEXT_AT(i0);
-      const uint64_t *rec = d_rec;
-      i1 = i0 + 1;
-      while (i1 < n && TEXT_AT(i1 + 1) - t0 <= cap) i1++;
+    { const size_t t0 = text_at(&h, i0);
+      const uint64_t *rec = s.d_rec;
+      i1 = text_slice_end(&h, i0, cap);
       for (i = i0; i < i1; i++) rel[i - i0] = p->ooff[i] - t0;
       TRY(dx_h2d(ctx, d_ooff, rel, (i1 - i0) * 8));
       if (whole_in)
-        rec = (const uint64_t *) d_rec + i0;
+        rec = (const uint64_t *) s.d_rec + i0;
       else                                                /* this slice's records, their offsets from the slice's first byte */
         { const uint64_t b0 = p->x.rec_off[i0];
           for (i = i0; i <= i1; i++) rel[most + 1 + (i - i0)] = p->x.rec_off[i] - b0;
-          TRY(dx_h2d(ctx, d_in, p->img + b0, (size_t) (p->x.rec_off[i1] - b0)));
-          TRY(dx_h2d(ctx, d_rec, rel + most + 1, (i1 - i0 + 1) * 8));
+          TRY(dx_h2d(ctx, s.d_in, p->img + b0, (size_t) (p->x.rec_off[i1] - b0)));
+          TRY(dx_h2d(ctx, s.d_rec, rel + most + 1, (i1 - i0 + 1) * 8));
         }
-      TRY(dx_qv_decode(ctx, d_in, rec, (const uint64_t *) d_hoff + i0, (const uint32_t *) d_seg + 5 * i0, (const uint32_t *) d_len + i0, i1 - i0,
-                       (upper ? DX_DECODE_UPPER : 0) | (p->x.flip ? DX_DECODE_FLIP : 0), d_out, d_ooff));
+      TRY(dx_qv_decode(ctx, s.d_in, rec, (const uint64_t *) s.d_hoff + i0, (const uint32_t *) s.d_seg + 5 * i0, (const uint32_t *) s.d_len + i0, i1 - i0,
+                       decode_flags(p, upper), d_out, d_ooff));
       h.base = t0;
-      TRY(dx_d2h_stream(ctx, d_out, TEXT_AT(i1) - t0, patch_and_pass, &h));
+      TRY(dx_d2h_stream(ctx, d_out, text_at(&h, i1) - t0, patch_and_pass, &h));
     }
-#undef TEXT_AT
 done:
   if (indexed) (void) dx_qv_use_index(ctx, NULL, NULL, 0, NULL, NULL, 0);
   dfree_all(&pool);
@@ -1493,69 +1509,55 @@ done:
   return rc;
 }
 
+/* does the text fit beside the image?  DEXGPU_TEXT_BUDGET (bytes) says how much text the device takes at once; else what is free
+   decides: the image (unless it is there already), the index and the text, and a tenth to spare.  0: all of it at once; else the
+   bytes of text a slice may have, and *whole_in: the image goes up whole beside them */
+static size_t undexqv_cap(dx_ctx *ctx, const dx_undexqv_plan *p, int *whole_in)
+{ uint64_t fr = 0, all = 0;
+  size_t   cap = 0;
+  *whole_in = 1;
+  if (budget_env(p->total, 65536u, &cap)) return cap;
+  if (dx_mem_info(ctx, &fr, &all) == DX_OK && fr > 0)
+    { const double in = PLAN_HAS_IMAGE(p) ? 0.0 : (double) p->n;
+      if (in + (double) p->total + 48.0 * (double) p->x.n > 0.9 * (double) fr)
+        { *whole_in = in <= 0.4 * (double) fr;
+          cap = (size_t) ((0.9 * (double) fr - (*whole_in ? in : 0.0) - 48.0 * (double) p->x.n) / (*whole_in ? 1.0 : 1.4));
+          if (cap < ((size_t) 4 << 20)) cap = (size_t) 4 << 20;
+        }
+    }
+  return cap;
+}
+
 int dx_file_undexqv_run(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_sink_fn sink, void *user)
 { dpool     pool = { {0}, 0, ctx };
-  void     *d_in, *d_rec, *d_hoff, *d_seg, *d_len, *d_out, *d_ooff;
+  undexqv_staged s;
+  void     *d_out, *d_ooff;
   hdr_patch h;
-  int       rc = DX_OK, indexed = 0;
+  size_t    cap;
+  int       rc = DX_OK, indexed = 0, whole_in;
 
   if (ctx == NULL || p == NULL || sink == NULL) return DX_E_ARG;
-  h.n = p->x.n; h.ooff = p->ooff; h.hat = p->hat; h.hd = p->hd.p; h.sink = sink; h.user = user; h.base = 0;
+  h.n = p->x.n; h.ooff = p->ooff; h.hat = p->hat; h.hd = p->hd.p; h.sink = sink; h.user = user; h.base = 0; h.total = p->total;
   if (p->ctx != NULL && p->ctx != ctx) return DX_E_ARG;   /* (a plan made on a device runs there) */
-  if (p->x.n > 0)
-    { /* does the text fit beside the image?  DEXGPU_TEXT_BUDGET (bytes) says how much text the device takes at once; else what
-         is free decides: the image (unless it is there already), the index and the text, and a tenth to spare */
-      const char *e = getenv("DEXGPU_TEXT_BUDGET");
-      uint64_t fr = 0, all = 0;
-      size_t   cap = 0;
-      int      whole_in = 1;
-      if (e != NULL && *e)
-        { const unsigned long long v = strtoull(e, NULL, 10);
-          if (v && v < p->total) cap = (size_t) (v < 65536u ? 65536u : v);
-        }
-      else if (dx_mem_info(ctx, &fr, &all) == DX_OK && fr > 0)
-        { const double in = PLAN_HAS_IMAGE(p) ? 0.0 : (double) p->n;
-          if (in + (double) p->total + 48.0 * (double) p->x.n > 0.9 * (double) fr)
-            { whole_in = in <= 0.4 * (double) fr;
-              cap = (size_t) ((0.9 * (double) fr - (whole_in ? in : 0.0) - 48.0 * (double) p->x.n) / (whole_in ? 1.0 : 1.4));
-              if (cap < ((size_t) 4 << 20)) cap = (size_t) 4 << 20;
-            }
-        }
-      if (cap)
-        return undexqv_sliced(ctx, p, upper, sink, user, cap, dx_test_on("slice_input") && !PLAN_HAS_IMAGE(p) ? 0 : whole_in);   /* (DEXGPU_TEST=slice_input) */
+  if (p->x.n == 0) return DX_OK;
+  cap = undexqv_cap(ctx, p, &whole_in);
+  if (cap)
+    return undexqv_sliced(ctx, p, upper, sink, user, cap, dx_test_on("slice_input") && !PLAN_HAS_IMAGE(p) ? 0 : whole_in);   /* (DEXGPU_TEST=slice_input) */
+  TRY(undexqv_stage(ctx, p, &pool, 0, 0, &s, &indexed));  /* (image and index: up, or on the device already) */
+  TRY(dupload(&pool, p->ooff, p->x.n * 8, &d_ooff));
+  TRY(dalloc(&pool, p->total, &d_out));
+  if (p->x.gidx != NULL && !p->x.flip)                   /* the host walk's group index: a wavefront per line (dx_qv_use_index) */
+    { void *d_gidx, *d_goff;
+      TRY(dupload(&pool, p->x.gidx, (size_t) p->x.gidx_words * 4, &d_gidx));
+      TRY(dupload(&pool, p->x.gidx_off, (p->x.n + 1) * 8, &d_goff));
+      TRY(dx_qv_use_index(ctx, s.d_in, s.d_seg, p->x.n, d_gidx, d_goff, p->x.gidx_none));
+      indexed = 1;
     }
-  if (p->x.n > 0)
-    { TRY(dx_qv_set_coding(ctx, &p->x.coding, 0));
-      if (PLAN_HAS_IMAGE(p)) d_in = p->d_in;              /* (the image is on the device already) */
-      else                   TRY(dupload(&pool, p->img, p->n, &d_in));
-      if (PLAN_HAS_INDEX(p))                              /* (and so is the index) */
-        { d_rec = p->dix.d_rec_off; d_hoff = p->dix.d_hdr_off; d_seg = p->dix.d_seg; d_len = p->dix.d_len; }
-      else
-        { TRY(dupload(&pool, p->x.rec_off, (p->x.n + 1) * 8, &d_rec));
-          TRY(dupload(&pool, p->x.hdr_off, (p->x.n + 1) * 8, &d_hoff));
-          TRY(dupload(&pool, p->x.seg, p->x.n * 5 * 4, &d_seg));
-          TRY(dupload(&pool, p->x.len, p->x.n * 4, &d_len));
-        }
-      TRY(dupload(&pool, p->ooff, p->x.n * 8, &d_ooff));
-      TRY(dalloc(&pool, p->total, &d_out));
-      if (p->x.gidx != NULL && !p->x.flip)               /* the walk's group index: a wavefront per line (dx_qv_use_index) */
-        { void *d_gidx, *d_goff;
-          TRY(dupload(&pool, p->x.gidx, (size_t) p->x.gidx_words * 4, &d_gidx));
-          TRY(dupload(&pool, p->x.gidx_off, (p->x.n + 1) * 8, &d_goff));
-          TRY(dx_qv_use_index(ctx, d_in, d_seg, p->x.n, d_gidx, d_goff, p->x.gidx_none));
-          indexed = 1;
-        }
-      else if (PLAN_HAS_INDEX(p) && p->dix.d_gidx != NULL && !p->x.flip)      /* the device walk's: the run-coded lines' groups */
-        { TRY(dx_qv_use_dindex(ctx, d_in, &p->dix));
-          indexed = 1;
-        }
-      fmark("undexqv: buffers ready");
-      TRY(dx_qv_decode(ctx, d_in, d_rec, d_hoff, d_seg, d_len, p->x.n,
-                       (upper ? DX_DECODE_UPPER : 0) | (p->x.flip ? DX_DECODE_FLIP : 0), d_out, d_ooff));
-      fmark("undexqv: decoded");
-      TRY(dx_d2h_stream(ctx, d_out, p->total, patch_and_pass, &h));
-      fmark("undexqv: text passed on");
-    }
+  fmark("undexqv: buffers ready");
+  TRY(dx_qv_decode(ctx, s.d_in, s.d_rec, s.d_hoff, s.d_seg, s.d_len, p->x.n, decode_flags(p, upper), d_out, d_ooff));
+  fmark("undexqv: decoded");
+  TRY(dx_d2h_stream(ctx, d_out, p->total, patch_and_pass, &h));
+  fmark("undexqv: text passed on");
 done:
   if (indexed) (void) dx_qv_use_index(ctx, NULL, NULL, 0, NULL, NULL, 0);     /* (the index lives in the pool freed below) */
   dfree_all(&pool);
@@ -1646,14 +1648,69 @@ static int all_ok(shard_all *a)
 
 static int shard_slice(shard_job *j, dpool *pool, void **d_text, void **d_off, void **d_len, uint64_t *span);
 
+/* The shard's entries staged on its device and prescanned (QV.c:993-1015, per shard).  By bytes, shard_slice has put text and index
+   there (d_text, d_off, d_len, span); else they are cut from the file's host index here. */
+static int shard_stage(shard_job *j, dpool *pool, void *d_text, void *d_off, void *d_len, uint64_t span, qv_staged *st)
+{ shard_all     *a = j->all;
+  const uint64_t m = j->hi - j->lo;
+  const int32_t *hdr4 = j->hdr4;
+  uint64_t      *roff = NULL, i;
+  int32_t        lwell;
+  int            rc;
+  if (a->by_bytes)
+    { const shard_job *prev = &a->jobs[j->id ? j->id - 1 : 0];
+      lwell = j->id ? prev->hdr4[4 * (prev->hi - prev->lo - 1)] : 0;
+    }
+  else                                                   /* this shard's slice of the text image */
+    { const uint64_t base = a->off[j->lo];
+      hdr4  = a->hdr4 + 4 * j->lo;
+      lwell = j->lo ? a->hdr4[4 * (j->lo - 1)] : 0;
+      span  = a->off[j->hi - 1] + 5 * ((uint64_t) a->len[j->hi - 1] + 1) - base;
+      roff  = malloc(m * sizeof(*roff));
+      if (!roff) return DX_E_NOMEM;
+      for (i = 0; i < m; i++) roff[i] = a->off[j->lo + i] - base;
+      TRY(dupload(pool, a->text + base, span, &d_text));
+      TRY(dupload(pool, roff, m * 8, &d_off));
+      TRY(dupload(pool, a->len + j->lo, m * 4, &d_len));
+    }
+  TRY(qv_stage(pool, hdr4, m, &lwell, d_text, d_off, d_len, span, 1, st));
+  TRY(dx_qv_prescan(j->ctx, &st->b, j->lo, &j->p));
+done:
+  free(roff);
+  return rc;
+}
+
+/* the file's first 100000 symbols (QV.c:1006-1015) reach beyond shard 0: the provisional subChar from a prefix batch of
+   entries [0, cut] instead */
+static int shard_prefix_sub(shard_job *j, dpool *pool)
+{ shard_all   *a = j->all;
+  const uint64_t mp = a->cut + 1, sp = a->off[a->cut] + 5 * ((uint64_t) a->len[a->cut] + 1) - a->off[0];
+  uint64_t    *po = malloc(mp * sizeof(*po)), i;
+  void        *pt = NULL, *pd_off = NULL, *pd_len = NULL;
+  dx_qv_batch  pb;
+  dx_qv_params pp = { 0, -1, 0, -1 };                     /* delChar "set": only the sub search runs */
+  int          rc;
+  if (po == NULL) return DX_E_NOMEM;
+  for (i = 0; i < mp; i++) po[i] = a->off[i] - a->off[0];
+  TRY(dupload(pool, a->text + a->off[0], sp, &pt));
+  TRY(dupload(pool, po, mp * 8, &pd_off));
+  TRY(dupload(pool, a->len, mp * 4, &pd_len));
+  pb = qv_batch(pt, pd_off, pd_len, mp, sp, 1);
+  TRY(dx_qv_prescan(j->ctx, &pb, 0, &pp));
+done:
+  j->p.subChar = pp.subChar; j->p.sub_first = pp.sub_first;
+  free(po);
+  return rc;
+}
+
 static void *shard_main(void *arg)
 { shard_job  *j = arg;
   shard_all  *a = j->all;
   dpool       pool = { {0}, 0, j->ctx };
-  uint64_t    m = j->hi - j->lo, i, *roff = NULL, *hoff = NULL, base = 0, span = 0, total = 0;
-  uint8_t    *blob = NULL;
-  void       *d_text = NULL, *d_off = NULL, *d_len = NULL, *d_hdr = NULL, *d_hoff = NULL, *d_rec = NULL, *d_seg = NULL, *d_out = NULL;
-  dx_qv_batch b;
+  uint64_t    m = j->hi - j->lo, span = 0, total = 0;
+  void       *d_text = NULL, *d_off = NULL, *d_len = NULL, *d_out = NULL;
+  size_t      out_cap = 0;
+  qv_staged   st;
   int         rc = DX_OK, k;
 
   pthread_mutex_lock(&a->gate_mx);                        /* all threads exist, or none runs */
@@ -1662,65 +1719,18 @@ static void *shard_main(void *arg)
   pthread_mutex_unlock(&a->gate_mx);
   if (k < 0) return NULL;
 
-  memset(&b, 0, sizeof(b));
+  memset(&st, 0, sizeof(st));
   j->p.delChar = j->p.subChar = -1; j->p.del_first = j->p.sub_first = -1;
   memset(j->hist, 0, sizeof(j->hist)); j->tot = 0; j->bytes = 0;
 
   if (a->by_bytes)
     { rc = shard_slice(j, &pool, &d_text, &d_off, &d_len, &span);        /* (five barriers inside, whatever becomes of it) */
       m = j->hi - j->lo;
-      if (rc == DX_OK && m > 0)
-        { int32_t lwell = j->id ? a->jobs[j->id - 1].hdr4[4 * (a->jobs[j->id - 1].hi - a->jobs[j->id - 1].lo - 1)] : 0;
-          hoff = malloc((m + 1) * sizeof(*hoff));
-          blob = malloc(dx_frame_bound(j->hdr4, m, lwell, 0) + 16);
-          if (!hoff || !blob) rc = DX_E_NOMEM;
-          if (rc == DX_OK) rc = dx_frame_headers(j->hdr4, NULL, m, 0, &lwell, blob, hoff);
-          if (rc == DX_OK) rc = dupload(&pool, blob, (size_t) hoff[m], &d_hdr);
-          if (rc == DX_OK) rc = dupload(&pool, hoff, (m + 1) * 8, &d_hoff);
-          if (rc == DX_OK) rc = dalloc(&pool, (m + 1) * 8, &d_rec);
-          if (rc == DX_OK) rc = dalloc(&pool, m * 20, &d_seg);
-          b.d_text = d_text; b.d_off = d_off; b.d_len = d_len; b.n = m; b.line_pad = 1; b.text_bytes = span;
-          if (rc == DX_OK) rc = dx_qv_prescan(j->ctx, &b, j->lo, &j->p);
-        }
     }
-  else if (m > 0)                                        /* this shard's slice of the text image */
-    { int32_t lwell = j->lo ? a->hdr4[4*(j->lo-1)] : 0;
-      base = a->off[j->lo];
-      span = a->off[j->hi-1] + 5 * ((uint64_t) a->len[j->hi-1] + 1) - base;
-      roff = malloc(m * sizeof(*roff));
-      hoff = malloc((m + 1) * sizeof(*hoff));
-      blob = malloc(dx_frame_bound(a->hdr4 + 4*j->lo, m, lwell, 0) + 16);
-      if (!roff || !hoff || !blob) rc = DX_E_NOMEM;
-      for (i = 0; rc == DX_OK && i < m; i++) roff[i] = a->off[j->lo + i] - base;
-      if (rc == DX_OK) rc = dx_frame_headers(a->hdr4 + 4*j->lo, NULL, m, 0, &lwell, blob, hoff);
-      if (rc == DX_OK) rc = dupload(&pool, a->text + base, span, &d_text);
-      if (rc == DX_OK) rc = dupload(&pool, roff, m * 8, &d_off);
-      if (rc == DX_OK) rc = dupload(&pool, a->len + j->lo, m * 4, &d_len);
-      if (rc == DX_OK) rc = dupload(&pool, blob, (size_t) hoff[m], &d_hdr);
-      if (rc == DX_OK) rc = dupload(&pool, hoff, (m + 1) * 8, &d_hoff);
-      if (rc == DX_OK) rc = dalloc(&pool, (m + 1) * 8, &d_rec);
-      if (rc == DX_OK) rc = dalloc(&pool, m * 20, &d_seg);
-      b.d_text = d_text; b.d_off = d_off; b.d_len = d_len; b.n = m; b.line_pad = 1; b.text_bytes = span;
-      if (rc == DX_OK) rc = dx_qv_prescan(j->ctx, &b, j->lo, &j->p);       /* QV.c:993-1015, per shard */
-    }
+  if (rc == DX_OK && m > 0)
+    rc = shard_stage(j, &pool, d_text, d_off, d_len, span, &st);
   if (rc == DX_OK && j->id == 0 && a->cut >= j->hi && !a->by_bytes)      /* (by bytes: shard_slice has seen to it that this is not so) */
-    { /* the file's first 100000 symbols (QV.c:1006-1015) reach beyond shard 0: find the provisional
-         subChar on a prefix batch of entries [0, cut] instead */
-      uint64_t     mp = a->cut + 1, sp = a->off[a->cut] + 5 * ((uint64_t) a->len[a->cut] + 1) - a->off[0];
-      uint64_t    *po = malloc(mp * sizeof(*po));
-      void        *pt = NULL, *pd_off = NULL, *pd_len = NULL;
-      dx_qv_batch  pb;
-      dx_qv_params pp = { 0, -1, 0, -1 };                 /* delChar "set": only the sub search runs */
-      if (po == NULL) rc = DX_E_NOMEM;
-      for (i = 0; rc == DX_OK && i < mp; i++) po[i] = a->off[i] - a->off[0];
-      if (rc == DX_OK) rc = dupload(&pool, a->text + a->off[0], sp, &pt);
-      if (rc == DX_OK) rc = dupload(&pool, po, mp * 8, &pd_off);
-      if (rc == DX_OK) rc = dupload(&pool, a->len, mp * 4, &pd_len);
-      pb.d_text = pt; pb.d_off = pd_off; pb.d_len = pd_len; pb.n = mp; pb.line_pad = 1; pb.text_bytes = sp;
-      if (rc == DX_OK) rc = dx_qv_prescan(j->ctx, &pb, 0, &pp);
-      j->p.subChar = pp.subChar; j->p.sub_first = pp.sub_first;
-      free(po);
-    }
+    rc = shard_prefix_sub(j, &pool);
   j->rc = rc;
   pthread_barrier_wait(&a->bar);
 
@@ -1736,7 +1746,7 @@ static void *shard_main(void *arg)
   pthread_barrier_wait(&a->bar);
 
   if (a->ok && m > 0)
-    j->rc = dx_qv_hist(j->ctx, &b, j->lo, &a->p, j->hist, &j->tot);        /* QV.c:988-1017, per shard */
+    j->rc = dx_qv_hist(j->ctx, &st.b, j->lo, &a->p, j->hist, &j->tot);     /* QV.c:988-1017, per shard */
   pthread_barrier_wait(&a->bar);
 
   if (j->id == 0 && (a->ok = all_ok(a)))                 /* host-side sum + Create_QVcoding */
@@ -1755,50 +1765,33 @@ static void *shard_main(void *arg)
 
   if (a->ok && m > 0)                                    /* Compress_Next_QVentry for the shard's entries */
     { rc = dx_qv_set_coding(j->ctx, &a->cd, a->lossy);
-      if (rc == DX_OK && !two_pass())
-        { const uint64_t cap = hoff[m] + dx_qv_out_bound((const uint64_t (*)[256]) j->hist, m, &a->cd, a->lossy);
-          rc = dalloc(&pool, cap, &d_out);
-          if (rc == DX_OK) rc = dx_qv_encode_onepass(j->ctx, &b, d_hdr, d_hoff, d_seg, d_rec, d_out, cap, &total);
-        }
-      else if (rc == DX_OK)
-        { rc = dx_qv_sizes(j->ctx, &b, d_hoff, d_seg, d_rec, &total);
-          if (rc == DX_OK) rc = dalloc(&pool, total, &d_out);
-          if (rc == DX_OK) rc = dx_qv_encode(j->ctx, &b, d_hdr, d_hoff, d_rec, d_seg, d_out);
-        }
+      if (rc == DX_OK) rc = qv_encode_batch(j->ctx, &st, (const uint64_t (*)[256]) j->hist, &a->cd, a->lossy, &d_out, &out_cap, &total);
       j->bytes = total;
       j->rc = rc;
     }
   pthread_barrier_wait(&a->bar);
 
   if (j->id == 0 && (a->ok = all_ok(a)))                 /* layout of the final image */
-    { size_t clen = 0, plen = 0;
-      if (a->by_bytes) plen = a->plen;
-      else
+    { size_t plen = a->plen, records = 0;
+      if (!a->by_bytes)
         { const uint8_t *h = a->text, *slash = memchr(h + 1, '/', (size_t) (a->off[0] - 1));
           plen = slash ? (size_t) (slash - h) : 0;
         }
-      dx_qv_write_coding(&a->cd, (const char *) a->text, plen, NULL, 0, &clen);
-      a->head = 2 + clen;
-      a->total = a->head;
       for (k = 0; k < a->nsh; k++)
-        { a->jobs[k].at = a->total;
-          a->total += a->jobs[k].bytes;
+        { a->jobs[k].at = records;                        /* (behind the head, once that is known) */
+          records += a->jobs[k].bytes;
         }
-      a->img = malloc(a->total + 16);
-      if (a->img == NULL) a->rc = DX_E_NOMEM;
-      else
-        { uint16_t key = 0x55aa;
-          memcpy(a->img, &key, 2);
-          a->rc = dx_qv_write_coding(&a->cd, (const char *) a->text, plen, a->img + 2, clen, &clen);
-        }
+      a->rc = qv_head(&a->cd, a->text, plen, records, &a->img, &a->head);
+      for (k = 0; k < a->nsh; k++) a->jobs[k].at += a->head;
+      a->total = a->head + records;
       a->ok = a->rc == DX_OK;
     }
   pthread_barrier_wait(&a->bar);
 
   if (a->ok && m > 0)
     j->rc = dx_d2h(j->ctx, a->img + j->at, d_out, total);
+  if (d_out) (void) dx_free(j->ctx, d_out);
   dfree_all(&pool);
-  free(roff); free(hoff); free(blob);
   return NULL;
 }
 
@@ -1876,10 +1869,7 @@ int dx_file_dexqv_sharded(dx_ctx **ctxs, int nctx, const uint8_t *text, size_t n
                           uint8_t **out, size_t *out_len, uint64_t *errline, int *errcode)
 { shard_all  a;
   pthread_t *th = NULL;
-  uint64_t   cnt = 0, *off = NULL;
-  uint32_t  *len = NULL;
-  int32_t   *hdr4 = NULL;
-  size_t     plen = 0;
+  quiva_index qx = { 0, NULL, NULL, NULL, 0 };
   int        rc, k, started = 0, by_bytes;
 
   if (ctxs == NULL || nctx < 1 || out == NULL || out_len == NULL) return DX_E_ARG;
@@ -1897,29 +1887,22 @@ again:
   a.nsh = nctx; a.lossy = lossy; a.text = text; a.n = n; a.rc = DX_OK; a.by_bytes = by_bytes;
 
   if (!by_bytes)                                          /* the whole file indexed here first (small files; what the shards turn down) */
-    { rc = dx_index_quiva(text, n, 0, NULL, NULL, NULL, &cnt, &plen, errline, errcode);
-      if (rc != DX_OK) goto done;
-      if (cnt == 0) { rc = DX_E_DEGENERATE; goto done; }
-      off  = malloc((cnt + 1) * sizeof(*off));
-      len  = malloc((cnt + 1) * sizeof(*len));
-      hdr4 = malloc((cnt + 1) * 4 * sizeof(*hdr4));
-      if (!off || !len || !hdr4) { rc = DX_E_NOMEM; goto done; }
-      TRY(dx_index_quiva(text, n, cnt, off, len, hdr4, &cnt, &plen, errline, errcode));
-      a.off = off; a.len = len; a.hdr4 = hdr4; a.cnt = cnt;
+    { TRY(quiva_index_host(&qx, text, n, errline, errcode));
+      a.off = qx.off; a.len = qx.len; a.hdr4 = qx.hdr4; a.cnt = qx.cnt;
       { uint64_t run = 0, e;
         a.cut = 0;
-        for (e = 0; e < cnt; e++)
-          { run += len[e];
+        for (e = 0; e < qx.cnt; e++)
+          { run += qx.len[e];
             if (run >= 100000) break;
           }
-        a.cut = e < cnt ? e : 0;             /* never reached: no subChar at all, shard 0 finds that too */
+        a.cut = e < qx.cnt ? e : 0;             /* never reached: no subChar at all, shard 0 finds that too */
       }
     }
   pthread_barrier_init(&a.bar, NULL, (unsigned) nctx);
   pthread_mutex_init(&a.gate_mx, NULL);
   pthread_cond_init(&a.gate_cv, NULL);
   a.go = 0; a.ok = 1;
-  { uint64_t per = cnt / (uint64_t) nctx, extra = cnt % (uint64_t) nctx, lo = 0;
+  { uint64_t per = qx.cnt / (uint64_t) nctx, extra = qx.cnt % (uint64_t) nctx, lo = 0;
     for (k = 0; k < nctx; k++)
       { uint64_t m = per + ((uint64_t) k < extra ? 1 : 0);
         a.jobs[k].all = &a; a.jobs[k].ctx = ctxs[k]; a.jobs[k].id = k;
@@ -1954,8 +1937,10 @@ again:
   pthread_cond_destroy(&a.gate_cv);
 done:
   for (k = 0; a.jobs != NULL && k < nctx; k++) { free(a.jobs[k].hdr4); free(a.jobs[k].len); }
-  free(off); free(len); free(hdr4); free(a.jobs); free(th); free(a.img);
-  off = NULL; len = NULL; hdr4 = NULL; th = NULL;
+  quiva_index_free(&qx);
+  memset(&qx, 0, sizeof(qx));
+  free(a.jobs); free(th); free(a.img);
+  th = NULL;
   if (by_bytes && a.again && started == nctx)            /* the shards turned the file down: the serial way (and its words for what is wrong) */
     { by_bytes = 0;
       goto again;
@@ -2018,10 +2003,11 @@ int dx_entries_add(dx_entries *e, int rlen, const char *del, const char *tag, co
 int dx_entries_compress(dx_ctx *ctx, const dx_entries *e, int lossy, dx_qv_coding *coding,
                         uint8_t **records, size_t *nbytes, uint64_t **coff)
 { dpool        pool = { {0}, 0, ctx };
-  dx_qv_batch  b;
+  qv_staged    st;
   dx_qv_params p = { -1, -1, -1, -1 };
   uint64_t   (*hist)[256] = NULL, tot = 0, total = 0;
-  void        *d_text, *d_off, *d_len, *d_rec, *d_seg, *d_out;
+  void        *d_text, *d_off, *d_len, *d_out = NULL;
+  size_t       out_cap = 0;
   uint8_t     *res = NULL;
   uint64_t    *ro = NULL;
   int          rc;
@@ -2035,32 +2021,22 @@ int dx_entries_compress(dx_ctx *ctx, const dx_entries *e, int lossy, dx_qv_codin
   TRY(dupload(&pool, e->text, e->tlen, &d_text));
   TRY(dupload(&pool, e->off, e->n * 8, &d_off));
   TRY(dupload(&pool, e->len, e->n * 4, &d_len));
-  TRY(dalloc(&pool, (e->n + 1) * 8, &d_rec));
-  TRY(dalloc(&pool, e->n * 20, &d_seg));
-  b.d_text = d_text; b.d_off = d_off; b.d_len = d_len; b.n = e->n; b.line_pad = 0; b.text_bytes = e->tlen;
-  TRY(dx_qv_scan(ctx, &b, 0, &p, hist, &tot));             /* QVcoding_Scan1 over all entries */
+  TRY(qv_stage(&pool, NULL, e->n, NULL, d_text, d_off, d_len, e->tlen, 0, &st));      /* (line_pad 0, no framing bytes) */
+  TRY(dx_qv_scan(ctx, &st.b, 0, &p, hist, &tot));          /* QVcoding_Scan1 over all entries */
   TRY(dx_qv_build((const uint64_t (*)[256]) hist, tot, &p, lossy, coding));   /* Create_QVcoding */
   TRY(dx_qv_set_coding(ctx, coding, lossy));
-  if (!two_pass())                                              /* Compress_Next_QVentry1 x n */
-    { const uint64_t cap = dx_qv_out_bound((const uint64_t (*)[256]) hist, e->n, coding, lossy);
-      TRY(dalloc(&pool, cap, &d_out));
-      TRY(dx_qv_encode_onepass(ctx, &b, NULL, NULL, d_seg, d_rec, d_out, cap, &total));
-    }
-  else
-    { TRY(dx_qv_sizes(ctx, &b, NULL, d_seg, d_rec, &total));
-      TRY(dalloc(&pool, total, &d_out));
-      TRY(dx_qv_encode(ctx, &b, NULL, NULL, d_rec, d_seg, d_out));
-    }
+  TRY(qv_encode_batch(ctx, &st, (const uint64_t (*)[256]) hist, coding, lossy, &d_out, &out_cap, &total));     /* Compress_Next_QVentry1 x n */
   res = malloc(total + 16);
   ro  = malloc((e->n + 1) * sizeof(*ro));
   if (!res || !ro) { rc = DX_E_NOMEM; goto done; }
   TRY(dx_d2h(ctx, res, d_out, total));
-  TRY(dx_d2h(ctx, ro, d_rec, (e->n + 1) * 8));
+  TRY(dx_d2h(ctx, ro, st.d_rec, (e->n + 1) * 8));
   *records = res; *nbytes = total; res = NULL;
   if (coff) { *coff = ro; ro = NULL; }
   rc = DX_OK;
 
 done:
+  if (d_out) (void) dx_free(ctx, d_out);
   dfree_all(&pool);
   free(hist); free(res); free(ro);
   return rc;

@@ -158,6 +158,9 @@ def test_file_larger_than_the_text_budget_goes_in_slices(monkeypatch, tmp_path):
             assert ctx.dexqv(c.text) == whole
             assert ctx.dexqv(c.text, True) == O.dexqv(c.text, True)
             ctx.set_scratch_budget(0)
+        set_flag(monkeypatch, "twopass", "1")                                     # the 7 slices under the two-pass encoder: same file
+        assert ctx.dexqv(c.text) == whole
+        set_flag(monkeypatch, "twopass", None)
         late = synth.make_quiva(300, seed=78, mean=9000)                          # the first 'N' tag far into the file: delChar found
         t = bytearray(late.text)                                                 # in a later slice than the first
         for i in range(200):
