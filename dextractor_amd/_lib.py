@@ -65,6 +65,14 @@ class QVDIndex(C.Structure):                     # dx_qv_dindex
                 ("d_gidx", C.c_void_p), ("d_gidx_off", C.c_void_p), ("gidx_words", C.c_uint64), ("gidx_none", C.c_uint64),
                 ("gidx_nosync", C.c_uint64), ("sync_kinds", C.c_uint32)]
 
+class VerifyReport(C.Structure):                 # dx_verify_report
+    _fields_ = [("ok", C.c_int32), ("upper", C.c_int32), ("width", C.c_uint32), ("where", C.c_int32),
+                ("records_src", C.c_uint64), ("records_img", C.c_uint64), ("record", C.c_uint64), ("line", C.c_uint64),
+                ("column", C.c_uint64), ("src_byte", C.c_uint64), ("img_byte", C.c_uint64)]
+
+DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
+VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
+
 # name -> (restype, argtypes); every symbol include/dexgpu.h declares
 _P = C.c_void_p
 SINK_FN = C.CFUNCTYPE(C.c_int, _P, C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t)     # dx_sink_fn
@@ -159,6 +167,9 @@ SIGNATURES = {
     "dx_file_undexqv_plan_free": (None, [_P]),
     "dx_d2h_stream": (C.c_int, [_P, _P, C.c_size_t, SINK_FN, _P]),
     "dx_file_free": (None, [_P]),
+    "dx_verify_ranges": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint64)]),
+    "dx_file_verify": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_int, C.POINTER(VerifyReport)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),
     "dx_entries_add": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),

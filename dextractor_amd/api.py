@@ -328,6 +328,28 @@ class Context:
     def undexqv(self, img: bytes, upper=False) -> bytes:
         return self._file_call(self.lib.dx_file_undexqv, img, len(img), int(upper))
 
+    # ---- round-trip check --------------------------------------------------------------------------
+    def verify_ranges(self, d_a, d_a_off, d_a_len, d_b, d_b_off, d_b_len, n, count=True):
+        """dx_verify_ranges: (first differing unit or None, first differing byte in it, differing units -- None when count=False,
+        which also lets the kernel skip what lies behind a difference already found)"""
+        unit, pos, differ = C.c_uint64(), C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.dx_verify_ranges(self.h, d_a.ptr, d_a_off.ptr, d_a_len.ptr, d_b.ptr, d_b_off.ptr, d_b_len.ptr, n,
+                                            C.byref(unit), C.byref(pos), C.byref(differ) if count else None))
+        none = unit.value == 2**64 - 1
+        return (None if none else unit.value), pos.value, (differ.value if count else None)
+
+    def verify(self, kind, text: bytes, img: bytes, lossy=False) -> dict:
+        """dx_file_verify: does img (a .dexta / .dexar / .dexqv image) give text back?  kind: "fasta", "arrow" or "quiva".  The
+        report as a dict; `where` is one of _lib.VERIFY_WHERE, `error` the library's words when it is "IMAGE"."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        rep = L.VerifyReport()
+        self._chk(self.lib.dx_file_verify(self.h, k, text, len(text), img, len(img), int(lossy), C.byref(rep)))
+        out = {f: getattr(rep, f) for f, _ in L.VerifyReport._fields_}
+        out["ok"], out["upper"], out["where"] = bool(rep.ok), bool(rep.upper), L.VERIFY_WHERE[rep.where]
+        if out["where"] == "IMAGE":
+            out["error"] = (self.lib.dx_last_error(self.h) or b"").decode()
+        return out
+
     def qv_subindex(self, on=True):
         self._chk(self.lib.dx_qv_subindex(self.h, int(bool(on))))
 

@@ -448,6 +448,39 @@ static void tmark(const char *what)
   fprintf(stderr, "[%s %8.1f ms] %s\n", Prog, (now - t0) * 1e3, what);
 }
 
+/* DEXGPU_VERIFY=1 (dexta, dexar, dexqv of a file): before the source goes, is it what the file just written gives back?  Both as
+   they are on disk now, decoded and compared on the GPU (dx_file_verify).  1: yes -- with -v, the invocation that restores it. */
+static int verified_on_disk(dx_ctx *ctx, int tool, const char *src, const char *dst, int lossy, int verbose)
+{ static const char *where[] = { "nothing", "header line", "body", "body length", "record count", "image" };
+  const int kind = tool == TOOL_DEXTA ? DX_KIND_FASTA : (tool == TOOL_DEXAR ? DX_KIND_ARROW : DX_KIND_QUIVA);
+  FILE    *fs = fopen(src, "r"), *fd = fopen(dst, "r");
+  uint8_t *text = NULL, *img = NULL;
+  size_t   n = 0, m = 0;
+  int      tmapped = 0, imapped = 0, rc = DX_E_IO, ok = 0;
+  dx_verify_report rep;
+  memset(&rep, 0, sizeof(rep));
+  if (fs != NULL && fd != NULL && (text = slurp(fs, &n, &tmapped)) != NULL && (img = slurp(fd, &m, &imapped)) != NULL)
+    rc = dx_file_verify(ctx, kind, text, n, img, m, lossy, &rep);
+  if (rc != DX_OK)
+    fprintf(stderr, "%s: %s could not be verified against %s (%s); both are kept\n", Prog, dst, src,
+            rc == DX_E_IO ? "cannot be read" : dx_last_error(ctx));
+  else if (!rep.ok)
+    fprintf(stderr, "%s: %s does not give %s back: record %llu, line %llu, column %llu (%s); both are kept\n", Prog, dst, src,
+            (unsigned long long) rep.record, (unsigned long long) rep.line, (unsigned long long) rep.column, where[rep.where]);
+  else
+    { ok = 1;
+      if (verbose)
+        { if (kind == DX_KIND_QUIVA) fprintf(stderr, "Verified (undexqv%s)\n", rep.upper ? " -U" : "");
+          else fprintf(stderr, "Verified (%s%s -w%u)\n", kind == DX_KIND_ARROW ? "undexar" : "undexta", rep.upper ? " -U" : "", rep.width);
+        }
+    }
+  if (text != NULL) unslurp(text, n, tmapped);
+  if (img != NULL) unslurp(img, m, imapped);
+  if (fs != NULL) fclose(fs);
+  if (fd != NULL) fclose(fd);
+  return ok;
+}
+
 int dex_tool_main(int tool, int argc, char *argv[])
 { const tool_t *t = &TOOLS[tool];
   int     flags[128], i, j, k, width = 80;
@@ -743,6 +776,15 @@ written:
           if (fclose(output) != 0)                         /* a deferred write error (ENOSPC, quota, NFS) surfaces here: */
             { fprintf(stderr, "%s: System error, write failed!\n", Prog);   /* the source must survive it */
               leave(2);
+            }
+          if ((tool == TOOL_DEXTA || tool == TOOL_DEXAR || tool == TOOL_DEXQV) && getenv("DEXGPU_VERIFY") != NULL && atoi(getenv("DEXGPU_VERIFY")) != 0)
+            { if (Opening)
+                { pthread_join(Opener, NULL);
+                  Opening = 0;
+                }
+              if (!verified_on_disk(Ctx0, tool, src, dst, LOSSY, VERBOSE))
+                leave(3);                                  /* (the reference's tools leave with 1 and 2; the files that follow are not touched) */
+              tmark("verified");
             }
           if (!KEEP)
             unlink(src);

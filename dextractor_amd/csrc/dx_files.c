@@ -629,32 +629,52 @@ static size_t out_cap(dx_ctx *ctx, size_t n, size_t total, uint64_t units)
   }
 }
 
+/* What becomes of a slice of decoded text -- entries [i0, i1), `bytes` of them at d_out, the first at t0 in the whole text: DX_OK
+   (the next slice), SLICE_STOP (no more slices are wanted: not an error), or an error */
+typedef int (*slice_fn)(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes);
+#define SLICE_STOP 1
+
+/* ... out to the caller: into the text in memory (res), or through the sink of h; header lines in place either way */
+typedef struct { dx_ctx *ctx; hdr_patch *h; uint8_t *res; } slice_out;
+static int slice_deliver(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes)
+{ slice_out *s = arg;
+  hdr_patch *h = s->h;
+  uint64_t   i;
+  int        rc;
+  if (s->res == NULL)
+    { h->base = t0;
+      return dx_d2h_stream(s->ctx, d_out, bytes, patch_and_pass, h);
+    }
+  rc = dx_d2h(s->ctx, s->res + t0, d_out, bytes);
+  for (i = i0; i < i1 && rc == DX_OK; i++)
+    memcpy(s->res + h->ooff[i] - (h->hat[i+1] - h->hat[i]), h->hd + h->hat[i], (size_t) (h->hat[i+1] - h->hat[i]));
+  return rc;
+}
+
 /* an image that arrives in pieces (dx_file_unpack2_stream): what the file's head said, the well the last record stood at, and
    how far into this piece the whole records reached (a piece may end inside a record: `more` says that more is coming) */
 typedef struct { int started, flip, newv, well, more; int32_t plen; char *name; size_t consumed; } u2_state;
 
-/* mode: DX_LETTERS_LOWER / _UPPER (dexta images) or _ARROW (dexar images); out != NULL: the text in memory,
-   else through the sink */
-static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width,
-                        uint8_t **out, dx_sink_fn sink, void *user, size_t *out_len, u2_state *st)
-{ dpool     pool = { {0}, 0, ctx };
-  rsrc      r = { img, n, 0, 0 };
-  tbuf      hd = { NULL, 0, 0 };               /* all header lines, concatenated */
-  uint64_t  cnt = 0, cap = 0, i, *ioff = NULL, *ooff = NULL, *hat = NULL;
-  uint32_t *nsym = NULL;
+/* The records of a .dexta / .dexar image, walked (undexta.c:138-271, undexar.c:136-229): per read where its packed bases stand in the
+   image (ioff) and how many there are (nsym), and its header line as the tool prints it (hd, from hat[i] on; hat[cnt]: their end);
+   `at`: how far the whole records reached, `well`: the last one's well. */
+typedef struct { uint64_t cnt, *ioff, *hat; uint32_t *nsym; tbuf hd; size_t at; int well; } u2_index;
+
+static void u2_index_free(u2_index *x)
+{ free(x->ioff); free(x->hat); free(x->nsym); free(x->hd.p); }
+
+#define U2_NOT_YET 1                /* (a piece of an image that arrives in pieces: its head is not all here yet; nothing consumed) */
+
+/* mode: DX_LETTERS_LOWER / _UPPER (dexta images) or _ARROW (dexar images); st: the image arrives in pieces (else NULL) */
+static int u2_walk(int mode, const uint8_t *img, size_t n, u2_state *st, u2_index *x)
+{ rsrc      r = { img, n, 0, 0 };
+  uint64_t  cnt = 0, cap = 0;
   uint16_t  key;
-  int       flip, newv, well = 0, rc, arrow = (mode == DX_LETTERS_ARROW);
+  int       flip, newv, well = 0, rc = DX_OK, arrow = (mode == DX_LETTERS_ARROW);
   int32_t   plen;
   char     *name = NULL;
-  uint8_t  *res = NULL;
-  size_t    total = 0;
-  void     *d_in, *d_ioff, *d_nsym, *d_out, *d_ooff;
 
-  if (ctx == NULL || (out == NULL && sink == NULL) || out_len == NULL || img == NULL) return DX_E_ARG;
-  if (width == 0) return DX_E_ARG;
-  if (out) *out = NULL;
-  *out_len = 0;
-
+  memset(x, 0, sizeof(*x));
   if (st != NULL) st->consumed = 0;
   if (st != NULL && st->started)                          /* a later piece: records from its first byte on */
     { flip = st->flip; newv = st->newv; plen = st->plen; well = st->well;
@@ -664,7 +684,7 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
     }
   else
     { rd(&r, &key, 2);                                    /* undexta.c:138-159, undexar.c:136-145 */
-      if (r.bad) return st != NULL && st->more ? DX_OK : DX_E_FORMAT;
+      if (r.bad) return st != NULL && st->more ? U2_NOT_YET : DX_E_FORMAT;
       if (key == 0x55aa)               { flip = 0; newv = 1; }
       else if (key == 0xaa55)          { flip = 1; newv = 1; }
       else if (!arrow && key == 0x33cc) { flip = 0; newv = 0; }
@@ -672,9 +692,9 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
       else return DX_E_FORMAT;
 
       plen = rd_i32(&r, flip);                            /* undexta.c:161-169 */
-      if (r.bad) return st != NULL && st->more ? DX_OK : DX_E_FORMAT;            /* (DX_OK, nothing consumed: the head is not all here yet) */
+      if (r.bad) return st != NULL && st->more ? U2_NOT_YET : DX_E_FORMAT;
       if (plen < 0) return DX_E_FORMAT;
-      if ((size_t) plen > n - r.at) return st != NULL && st->more && plen < (1 << 24) ? DX_OK : DX_E_FORMAT;
+      if ((size_t) plen > n - r.at) return st != NULL && st->more && plen < (1 << 24) ? U2_NOT_YET : DX_E_FORMAT;
       name = malloc((size_t) plen + 1);
       if (!name) return DX_E_NOMEM;
       rd(&r, name, (size_t) plen);
@@ -723,113 +743,152 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
         }
 
       if (cnt == cap)
-        { void *t;                                        /* a failed realloc leaves the old block to `done` */
+        { void *t;                                        /* a failed realloc leaves the old block to the caller's u2_index_free */
           cap  = cap ? 2 * cap : 1024;
-          if ((t = realloc(ioff, cap * sizeof(*ioff))) == NULL) { rc = DX_E_NOMEM; goto done; }
-          ioff = t;
-          if ((t = realloc(ooff, cap * sizeof(*ooff))) == NULL) { rc = DX_E_NOMEM; goto done; }
-          ooff = t;
-          if ((t = realloc(hat, (cap + 1) * sizeof(*hat))) == NULL) { rc = DX_E_NOMEM; goto done; }
-          hat = t;
-          if ((t = realloc(nsym, cap * sizeof(*nsym))) == NULL) { rc = DX_E_NOMEM; goto done; }
-          nsym = t;
+          if ((t = realloc(x->ioff, cap * sizeof(*x->ioff))) == NULL) { rc = DX_E_NOMEM; goto done; }
+          x->ioff = t;
+          if ((t = realloc(x->hat, (cap + 1) * sizeof(*x->hat))) == NULL) { rc = DX_E_NOMEM; goto done; }
+          x->hat = t;
+          if ((t = realloc(x->nsym, cap * sizeof(*x->nsym))) == NULL) { rc = DX_E_NOMEM; goto done; }
+          x->nsym = t;
         }
-      if ((rc = tb_room(&hd, (size_t) plen + 160)) != DX_OK) goto done;
-      hat[cnt] = hd.len;
+      if ((rc = tb_room(&x->hd, (size_t) plen + 160)) != DX_OK) goto done;
+      x->hat[cnt] = x->hd.len;
       if (arrow)                                          /* undexar.c:199-203 */
         { float snr[4];
           for (k = 0; k < 4; k++) snr[k] = (float) (cnr[k] / 100.);
-          hd.len += (size_t) sprintf(hd.p + hd.len, "%s/%d/%d_%d SN=%.2f,%.2f,%.2f,%.2f\n", name, well, beg, end,
-                                     snr[0], snr[1], snr[2], snr[3]);
+          x->hd.len += (size_t) sprintf(x->hd.p + x->hd.len, "%s/%d/%d_%d SN=%.2f,%.2f,%.2f,%.2f\n", name, well, beg, end,
+                                        snr[0], snr[1], snr[2], snr[3]);
         }
       else                                                /* undexta.c:242 */
-        hd.len += (size_t) sprintf(hd.p + hd.len, "%s/%d/%d_%d RQ=0.%d\n", name, well, beg, end, qv);
+        x->hd.len += (size_t) sprintf(x->hd.p + x->hd.len, "%s/%d/%d_%d RQ=0.%d\n", name, well, beg, end, qv);
 
-      ioff[cnt] = r.at;
-      nsym[cnt] = rlen;
+      x->ioff[cnt] = r.at;
+      x->nsym[cnt] = rlen;
       r.at += clen;
       cnt  += 1;
     }
-  if (cnt) hat[cnt] = hd.len;
+  if (cnt) x->hat[cnt] = x->hd.len;
+  x->cnt = cnt; x->at = r.at; x->well = well;
+done:
+  free(name);
+  return rc;
+}
 
-  for (i = 0; i < cnt; i++)                               /* output layout: header line, wrapped text */
-    { size_t L = nsym[i];
-      total  += (size_t) (hat[i+1] - hat[i]);
+/* the text's layout for a line width: header line, wrapped letters, read after read; ooff[i]: where read i's letters begin */
+static size_t u2_layout(const u2_index *x, uint32_t width, uint64_t *ooff)
+{ size_t   total = 0;
+  uint64_t i;
+  for (i = 0; i < x->cnt; i++)
+    { const size_t L = x->nsym[i];
+      total  += (size_t) (x->hat[i+1] - x->hat[i]);
       ooff[i] = total;
       total  += L + (L + width - 1) / width;
     }
+  return total;
+}
+
+/* A walked image's text made in slices of whole reads, at most `cap` bytes of text each, the image resident (a quarter of the text);
+   every slice goes to `deliver` before the next one is made (the reference writes read after read, undexta.c:175-271). */
+static int unpack2_slices(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width, const u2_index *x, const hdr_patch *h,
+                          size_t cap, slice_fn deliver, void *arg)
+{ dpool     pool = { {0}, 0, ctx };
+  const uint64_t cnt = x->cnt;
+  uint64_t *rel = NULL, i, i0, i1, most = 0;
+  size_t    tmax = 0;
+  void     *d_in, *d_ioff, *d_nsym, *d_out, *d_ooff;
+  int       rc;
+  for (i0 = 0; i0 < cnt; i0 = i1)
+    { i1 = text_slice_end(h, i0, cap);
+      if (text_at(h, i1) - text_at(h, i0) > tmax) tmax = text_at(h, i1) - text_at(h, i0);
+      if (i1 - i0 > most) most = i1 - i0;
+    }
+  rel = malloc((most + 1) * sizeof(*rel));
+  if (rel == NULL) return DX_E_NOMEM;
+  rc = dupload(&pool, img, n, &d_in);
+  if (rc == DX_OK) rc = dupload(&pool, x->ioff, cnt * 8, &d_ioff);
+  if (rc == DX_OK) rc = dupload(&pool, x->nsym, cnt * 4, &d_nsym);
+  if (rc == DX_OK) rc = dalloc(&pool, (most + 1) * 8, &d_ooff);
+  if (rc == DX_OK) rc = dalloc(&pool, tmax, &d_out);
+  for (i0 = 0; i0 < cnt && rc == DX_OK; i0 = i1)
+    { const size_t t0 = text_at(h, i0);
+      i1 = text_slice_end(h, i0, cap);
+      for (i = i0; i < i1; i++) rel[i - i0] = h->ooff[i] - t0;
+      rc = dx_h2d(ctx, d_ooff, rel, (i1 - i0) * 8);
+      if (rc == DX_OK)
+        rc = dx_pack2_decode(ctx, mode, d_in, (const uint64_t *) d_ioff + i0, (const uint32_t *) d_nsym + i0, i1 - i0, width, d_out, d_ooff);
+      if (rc == DX_OK)
+        rc = deliver(arg, d_out, i0, i1, t0, text_at(h, i1) - t0);
+    }
+  dfree_all(&pool);
+  free(rel);
+  return rc == SLICE_STOP ? DX_OK : rc;
+}
+
+/* out != NULL: the text in memory, else through the sink */
+static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width,
+                        uint8_t **out, dx_sink_fn sink, void *user, size_t *out_len, u2_state *st)
+{ dpool     pool = { {0}, 0, ctx };
+  u2_index  x;
+  uint64_t  cnt, i, *ooff = NULL;
+  int       rc;
+  uint8_t  *res = NULL;
+  size_t    total = 0;
+  void     *d_in, *d_ioff, *d_nsym, *d_out, *d_ooff;
+
+  if (ctx == NULL || (out == NULL && sink == NULL) || out_len == NULL || img == NULL) return DX_E_ARG;
+  if (width == 0) return DX_E_ARG;
+  if (out) *out = NULL;
+  *out_len = 0;
+
+  rc = u2_walk(mode, img, n, st, &x);
+  if (rc == U2_NOT_YET) { u2_index_free(&x); return DX_OK; }
+  if (rc != DX_OK) goto done;
+  cnt = x.cnt;
+  ooff = malloc((cnt + 1) * sizeof(*ooff));
+  if (ooff == NULL) { rc = DX_E_NOMEM; goto done; }
+  total = u2_layout(&x, width, ooff);                     /* output layout: header line, wrapped text */
   if (out)
     { res = malloc(total + 16);
       if (!res) { rc = DX_E_NOMEM; goto done; }
     }
 
-  { /* A text that does not fit the device beside the image (or DEXGPU_TEXT_BUDGET): slices of whole reads, the image resident
-       (a quarter of the text), every slice's text out before the next one's is made (the reference writes read after read,
-       undexta.c:175-271). */
+  { /* A text that does not fit the device beside the image (or DEXGPU_TEXT_BUDGET): slices of whole reads, every slice's text
+       out before the next one's is made. */
     const size_t cap = out_cap(ctx, n, total, cnt);
     if (cnt > 0 && cap)
-      { uint64_t *rel = NULL, i0, i1, most = 0;
-        size_t    tmax = 0;
-        hdr_patch h = { cnt, ooff, hat, hd.p, sink, user, 0, total };
-        for (i0 = 0; i0 < cnt; i0 = i1)
-          { i1 = text_slice_end(&h, i0, cap);
-            if (text_at(&h, i1) - text_at(&h, i0) > tmax) tmax = text_at(&h, i1) - text_at(&h, i0);
-            if (i1 - i0 > most) most = i1 - i0;
-          }
-        rel = malloc((most + 1) * sizeof(*rel));
-        if (rel == NULL) { rc = DX_E_NOMEM; goto done; }
-        rc = dupload(&pool, img, n, &d_in);
-        if (rc == DX_OK) rc = dupload(&pool, ioff, cnt * 8, &d_ioff);
-        if (rc == DX_OK) rc = dupload(&pool, nsym, cnt * 4, &d_nsym);
-        if (rc == DX_OK) rc = dalloc(&pool, (most + 1) * 8, &d_ooff);
-        if (rc == DX_OK) rc = dalloc(&pool, tmax, &d_out);
-        for (i0 = 0; i0 < cnt && rc == DX_OK; i0 = i1)
-          { const size_t t0 = text_at(&h, i0);
-            i1 = text_slice_end(&h, i0, cap);
-            for (i = i0; i < i1; i++) rel[i - i0] = ooff[i] - t0;
-            rc = dx_h2d(ctx, d_ooff, rel, (i1 - i0) * 8);
-            if (rc == DX_OK)
-              rc = dx_pack2_decode(ctx, mode, d_in, (const uint64_t *) d_ioff + i0, (const uint32_t *) d_nsym + i0, i1 - i0, width, d_out, d_ooff);
-            if (rc == DX_OK && out)
-              { rc = dx_d2h(ctx, res + t0, d_out, text_at(&h, i1) - t0);
-                for (i = i0; i < i1 && rc == DX_OK; i++)
-                  memcpy(res + ooff[i] - (hat[i+1] - hat[i]), hd.p + hat[i], (size_t) (hat[i+1] - hat[i]));
-              }
-            else if (rc == DX_OK)
-              { h.base = t0;
-                rc = dx_d2h_stream(ctx, d_out, text_at(&h, i1) - t0, patch_and_pass, &h);
-              }
-          }
-        free(rel);
-        if (rc != DX_OK) goto done;
+      { hdr_patch h = { cnt, ooff, x.hat, x.hd.p, sink, user, 0, total };
+        slice_out so = { ctx, &h, res };
+        TRY(unpack2_slices(ctx, mode, img, n, width, &x, &h, cap, slice_deliver, &so));
         cnt = 0;                                          /* (done: nothing left for the one-shot path below) */
       }
   }
   if (cnt > 0)
     { TRY(dupload(&pool, img, n, &d_in));
-      TRY(dupload(&pool, ioff, cnt * 8, &d_ioff));
-      TRY(dupload(&pool, nsym, cnt * 4, &d_nsym));
+      TRY(dupload(&pool, x.ioff, cnt * 8, &d_ioff));
+      TRY(dupload(&pool, x.nsym, cnt * 4, &d_nsym));
       TRY(dupload(&pool, ooff, cnt * 8, &d_ooff));
       TRY(dalloc(&pool, total, &d_out));
       TRY(dx_pack2_decode(ctx, mode, d_in, d_ioff, d_nsym, cnt, width, d_out, d_ooff));
       if (out)
         { TRY(dx_d2h(ctx, res, d_out, total));
           for (i = 0; i < cnt; i++)
-            memcpy(res + ooff[i] - (hat[i+1] - hat[i]), hd.p + hat[i], (size_t) (hat[i+1] - hat[i]));
+            memcpy(res + ooff[i] - (x.hat[i+1] - x.hat[i]), x.hd.p + x.hat[i], (size_t) (x.hat[i+1] - x.hat[i]));
         }
       else
-        { hdr_patch h = { cnt, ooff, hat, hd.p, sink, user, 0, total };
+        { hdr_patch h = { cnt, ooff, x.hat, x.hd.p, sink, user, 0, total };
           TRY(dx_d2h_stream(ctx, d_out, total, patch_and_pass, &h));
         }
     }
   if (out) { *out = res; res = NULL; }
   *out_len = total;
-  if (st != NULL) { st->well = well; st->consumed = r.at; }
+  if (st != NULL) { st->well = x.well; st->consumed = x.at; }
   rc = DX_OK;
 
 done:
   dfree_all(&pool);
-  free(name); free(hd.p); free(ioff); free(ooff); free(hat); free(nsym); free(res);
+  u2_index_free(&x);
+  free(ooff); free(res);
   return rc;
 }
 
@@ -1460,9 +1519,9 @@ static int decode_flags(const dx_undexqv_plan *p, int upper)
 /* ---- a text larger than the device (or than DEXGPU_TEXT_BUDGET): slices of whole entries ------------------------------
  * The reference writes entry after entry (undexqv.c:182-207).  Here: per slice of at most `cap` bytes of text, the slice's
  * records -- the whole image stays on the device when it is there already (a plan made there) or fits beside a slice's text,
- * else the slice's bytes are uploaded -- are decoded into one buffer that goes out before the next slice comes in.
+ * else the slice's bytes are uploaded -- are decoded into one buffer that goes to `deliver` before the next slice comes in.
  * Same text; such a file is bound by the host link.                                                               */
-static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_sink_fn sink, void *user, size_t cap, int whole_in_)
+static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_fn deliver, void *arg, size_t cap, int whole_in_)
 { const int whole_in = whole_in_ || PLAN_HAS_IMAGE(p);    /* (an image that is there is there whole) */
   dpool     pool = { {0}, 0, ctx };
   const uint64_t n = p->x.n;
@@ -1470,7 +1529,7 @@ static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_s
   void     *d_out = NULL, *d_ooff = NULL;
   uint64_t *rel = NULL, i0, i1, i, most = 0;
   size_t    tmax = 0, imax = 0;
-  hdr_patch h = { n, p->ooff, p->hat, p->hd.p, sink, user, 0, p->total };
+  const hdr_patch h = { n, p->ooff, p->hat, p->hd.p, NULL, NULL, 0, p->total };      /* (the layout, for the slices' bounds) */
   int       rc = DX_OK, indexed = 0;
   for (i0 = 0; i0 < n; i0 = i1)                           /* the largest slice: one allocation serves them all */
     { i1 = text_slice_end(&h, i0, cap);
@@ -1499,14 +1558,13 @@ static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_s
         }
       TRY(dx_qv_decode(ctx, s.d_in, rec, (const uint64_t *) s.d_hoff + i0, (const uint32_t *) s.d_seg + 5 * i0, (const uint32_t *) s.d_len + i0, i1 - i0,
                        decode_flags(p, upper), d_out, d_ooff));
-      h.base = t0;
-      TRY(dx_d2h_stream(ctx, d_out, text_at(&h, i1) - t0, patch_and_pass, &h));
+      TRY(deliver(arg, d_out, i0, i1, t0, text_at(&h, i1) - t0));
     }
 done:
   if (indexed) (void) dx_qv_use_index(ctx, NULL, NULL, 0, NULL, NULL, 0);
   dfree_all(&pool);
   free(rel);
-  return rc;
+  return rc == SLICE_STOP ? DX_OK : rc;
 }
 
 /* does the text fit beside the image?  DEXGPU_TEXT_BUDGET (bytes) says how much text the device takes at once; else what is free
@@ -1542,7 +1600,9 @@ int dx_file_undexqv_run(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_sin
   if (p->x.n == 0) return DX_OK;
   cap = undexqv_cap(ctx, p, &whole_in);
   if (cap)
-    return undexqv_sliced(ctx, p, upper, sink, user, cap, dx_test_on("slice_input") && !PLAN_HAS_IMAGE(p) ? 0 : whole_in);   /* (DEXGPU_TEST=slice_input) */
+    { slice_out so = { ctx, &h, NULL };
+      return undexqv_sliced(ctx, p, upper, slice_deliver, &so, cap, dx_test_on("slice_input") && !PLAN_HAS_IMAGE(p) ? 0 : whole_in);   /* (DEXGPU_TEST=slice_input) */
+    }
   TRY(undexqv_stage(ctx, p, &pool, 0, 0, &s, &indexed));  /* (image and index: up, or on the device already) */
   TRY(dupload(&pool, p->ooff, p->x.n * 8, &d_ooff));
   TRY(dalloc(&pool, p->total, &d_out));
@@ -1586,6 +1646,257 @@ int dx_file_undexqv(dx_ctx *ctx, const uint8_t *img, size_t n, int upper, uint8_
   if (rc == DX_OK) { *out = m.res; *out_len = total; }
   else             free(m.res);
   dx_file_undexqv_plan_free(p);
+  return rc;
+}
+
+/* ==========================================================================================
+ *  round-trip check (dx_file_verify): the tools remove their source (dexta.c:205), and nothing ever asked whether the image
+ *  gives it back -- SURVEY.md 8(c) lists when it does not.  The text is indexed and the image walked as the drivers above do
+ *  it, the image decoded by their kernels slice by slice, and every slice compared with its part of the text where it lies:
+ *  on the device (dx_verify_ranges).  Only the verdict comes back.
+ * ========================================================================================== */
+/* one side of the comparison, record by record: where the record's header line and body begin in the host text and how long the
+   body is.  The text side reads them off its index, the image side off the decoder's layout. */
+typedef struct
+  { dx_ctx           *ctx;
+    dx_verify_report *rep;
+    int               kind, lossy, failed;         /* failed: the device said no to a slice (an error, not a verdict) */
+    const uint8_t    *text;
+    size_t            n;
+    uint64_t          cnt;                         /* the text's records */
+    const uint64_t   *off;                         /* ... where each one's body begins */
+    const uint32_t   *blen;                        /* fasta / arrow: its bytes (tlen); quiva: symbols a line (len) */
+    const uint64_t   *ooff, *hat;                  /* the decoded text's layout (hdr_patch) */
+    uint64_t          upto;                        /* records [0, upto) have bodies to compare: both sides have them, and no header before differs */
+    uint64_t          hit, hit_pos;                /* the first record whose bodies differ (UINT64_MAX: none), and where */
+    void             *d_src, *d_arr;               /* device: a slice of the text; its unit arrays */
+    size_t            src_cap, arr_cap;
+  } verify_job;
+
+static uint64_t vj_body_bytes(const verify_job *v, uint64_t i)
+{ uint64_t b = v->kind == DX_KIND_QUIVA ? 5 * ((uint64_t) v->blen[i] + 1) : v->blen[i];
+  return v->off[i] + b > v->n ? v->n - v->off[i] : b;    /* (a .quiva whose last line has no newline) */
+}
+static uint64_t vj_head_at(const verify_job *v, uint64_t i)
+{ return i ? v->off[i - 1] + vj_body_bytes(v, i - 1) : 0; }
+/* the decoded body of record i: from ooff[i] to the next record's header line (ooff[records_img]: the decoded text's end) */
+static uint64_t vj_dec_bytes(const verify_job *v, uint64_t i)
+{ return (i + 1 < v->rep->records_img ? v->ooff[i + 1] - (v->hat[i + 2] - v->hat[i + 1]) : v->ooff[i + 1]) - v->ooff[i]; }
+
+/* a slice of decoded text, records [i0, i1), against the same records of the text */
+static int verify_slice(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes)
+{ verify_job *v = arg;
+  const uint64_t e1 = i1 < v->upto ? i1 : v->upto, m = e1 > i0 ? e1 - i0 : 0;
+  uint64_t  s0, s1, k, unit = UINT64_MAX, *a_off, *b_off;
+  uint32_t *a_len, *b_len, *q_len, pos = 0;
+  uint8_t  *h = NULL;
+  int       rc = DX_OK;
+  (void) bytes;
+  if (m == 0) return SLICE_STOP;
+  s0 = v->off[i0]; s1 = v->off[e1 - 1] + vj_body_bytes(v, e1 - 1);
+  if (s1 - s0 + 64 > v->src_cap)
+    { if (v->d_src) (void) dx_free(v->ctx, v->d_src);
+      v->d_src = NULL; v->src_cap = 0;
+      if ((rc = dx_malloc(v->ctx, (size_t) (s1 - s0) + 64, &v->d_src)) != DX_OK) goto bad;
+      v->src_cap = (size_t) (s1 - s0) + 64;
+    }
+  if (m * 28 + 64 > v->arr_cap)
+    { if (v->d_arr) (void) dx_free(v->ctx, v->d_arr);
+      v->d_arr = NULL; v->arr_cap = 0;
+      if ((rc = dx_malloc(v->ctx, (size_t) m * 28 + 64, &v->d_arr)) != DX_OK) goto bad;
+      v->arr_cap = (size_t) m * 28 + 64;
+    }
+  h = malloc((size_t) m * 28 + 64);                        /* a_off, b_off (8 each), a_len, b_len, the lines' symbols (4 each) */
+  if (h == NULL) { rc = DX_E_NOMEM; goto bad; }
+  a_off = (uint64_t *) h; b_off = a_off + m; a_len = (uint32_t *) (b_off + m); b_len = a_len + m; q_len = b_len + m;
+  for (k = 0; k < m; k++)
+    { const uint64_t i = i0 + k;
+      a_off[k] = v->off[i] - s0;
+      a_len[k] = (uint32_t) vj_body_bytes(v, i);
+      b_off[k] = v->ooff[i] - t0;
+      b_len[k] = (uint32_t) vj_dec_bytes(v, i);
+      q_len[k] = v->blen[i];
+    }
+  if ((rc = dx_h2d(v->ctx, v->d_src, v->text + s0, (size_t) (s1 - s0))) != DX_OK) goto bad;
+  if ((rc = dx_h2d(v->ctx, v->d_arr, h, (size_t) m * 28)) != DX_OK) goto bad;
+  { const uint64_t *da_off = v->d_arr, *db_off = da_off + m;
+    const uint32_t *da_len = (const uint32_t *) (db_off + m), *db_len = da_len + m, *dq_len = db_len + m;
+    if (v->lossy && v->kind == DX_KIND_QUIVA)              /* what dexqv -l keeps of the text (QV.c:1355-1372) */
+      { const dx_qv_batch b = qv_batch(v->d_src, da_off, dq_len, m, s1 - s0, 1);
+        if ((rc = dx_qv_lossy_text(v->ctx, &b)) != DX_OK) goto bad;
+      }
+    rc = dx_verify_ranges(v->ctx, v->d_src, da_off, da_len, d_out, db_off, db_len, m, &unit, &pos, NULL);
+    if (rc != DX_OK) goto bad;
+  }
+  free(h);
+  if (unit != UINT64_MAX)
+    { v->hit = i0 + unit; v->hit_pos = pos;
+      return SLICE_STOP;
+    }
+  return e1 == v->upto ? SLICE_STOP : DX_OK;
+bad:
+  free(h);
+  v->failed = 1;
+  return rc;
+}
+
+/* how much decoded text a slice may have: the slice, its part of the text and the image are on the device together.  0: all at once */
+static size_t verify_cap(dx_ctx *ctx, size_t resident, size_t total, uint64_t units)
+{ uint64_t fr = 0, all = 0;
+  size_t   cap;
+  if (budget_env(2 * total, 131072u, &cap)) return cap / 2;
+  if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
+  if ((double) resident + 2.0 * (double) total + 80.0 * (double) units <= 0.9 * (double) fr) return 0;
+  { const double room = (0.9 * (double) fr - (double) resident - 80.0 * (double) units) / 2.0;
+    return room > (double) ((size_t) 4 << 20) ? (size_t) room : (size_t) 4 << 20;
+  }
+}
+
+/* record r's place in the report: byte `pos` of its body in the text (line, column), or of its header line (body == 0) */
+static void verify_place(const verify_job *v, uint64_t r, int body, uint64_t pos)
+{ dx_verify_report *rep = v->rep;
+  const uint64_t at = body ? v->off[r] : vj_head_at(v, r), lim = body ? vj_body_bytes(v, r) : v->off[r] - at;
+  uint64_t k, line = body ? 1 : 0, col = 0;
+  if (pos > lim) pos = lim;
+  for (k = 0; k < pos; k++)
+    if (v->text[at + k] == '\n') { line += 1; col = 0; } else col += 1;
+  rep->record = r; rep->line = line; rep->column = col; rep->src_byte = at + pos;
+}
+
+int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const uint8_t *img, size_t m, int lossy, dx_verify_report *rep)
+{ seq_index        sx;
+  quiva_index      qx = { 0, NULL, NULL, NULL, 0 };
+  u2_index         ux;
+  dx_undexqv_plan *plan = NULL;
+  verify_job       v;
+  uint64_t        *ooff = NULL, el = 0, both, i, hfirst;
+  const uint64_t  *hat = NULL;
+  const char      *hd = NULL;
+  size_t           total = 0, cap;
+  int              rc, ec = 0, mode = DX_LETTERS_LOWER;
+
+  if (ctx == NULL || rep == NULL || (text == NULL && n) || (img == NULL && m)) return DX_E_ARG;
+  if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW && kind != DX_KIND_QUIVA) return DX_E_ARG;
+  memset(rep, 0, sizeof(*rep));
+  memset(&sx, 0, sizeof(sx)); memset(&ux, 0, sizeof(ux)); memset(&v, 0, sizeof(v));
+  v.ctx = ctx; v.rep = rep; v.kind = kind; v.lossy = lossy; v.text = text; v.n = n; v.hit = UINT64_MAX;
+
+  /* the text: its records, and the options that would give it back */
+  if (kind == DX_KIND_QUIVA)
+    { TRY(quiva_index_host(&qx, text, n, &el, &ec));
+      v.cnt = qx.cnt; v.off = qx.off; v.blen = qx.len;
+      for (i = 0; i < qx.cnt; i++)                        /* undexqv -U: the deletion tags' case (undexqv.c:198-204) */
+        if (qx.len[i] > 0)
+          { const uint8_t c = text[qx.off[i] + qx.len[i] + 1];
+            rep->upper = c >= 'A' && c <= 'Z';
+            break;
+          }
+    }
+  else
+    { uint32_t longest = 0;
+      TRY(seq_index_host(&sx, kind == DX_KIND_ARROW, text, n, &el, &ec));
+      v.cnt = sx.cnt; v.off = sx.off; v.blen = sx.tlen;
+      for (i = 0; i < sx.cnt && kind == DX_KIND_FASTA; i++)
+        if (sx.nsym[i] > 0)
+          { const uint8_t *q = text + sx.off[i];
+            while (*q == '\n') q++;
+            rep->upper = *q >= 'A' && *q <= 'Z';
+            break;
+          }
+      for (i = 0; i < sx.cnt && rep->width == 0; i++)      /* -w: the first line that another line of its record follows */
+        { const uint8_t *q = text + sx.off[i], *e = sx.tlen[i] ? memchr(q, '\n', sx.tlen[i]) : NULL;
+          if (e != NULL && (size_t) (e - q) + 1 < sx.tlen[i] && e > q) rep->width = (uint32_t) (e - q);
+          if (sx.nsym[i] > longest) longest = sx.nsym[i];
+        }
+      if (rep->width == 0) rep->width = longest ? longest : 1;
+    }
+  rep->records_src = v.cnt;
+
+  /* the image: its records, the header lines the decoder prints, the text's layout */
+  if (kind == DX_KIND_QUIVA)
+    { rc = m ? dx_file_undexqv_plan_on(ctx, img, m, &plan, &total) : DX_E_FORMAT;
+      if (rc == DX_OK) { rep->records_img = plan->x.n; ooff = NULL; v.ooff = plan->ooff; hat = plan->hat; hd = plan->hd.p; }
+    }
+  else
+    { mode = kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : (rep->upper ? DX_LETTERS_UPPER : DX_LETTERS_LOWER);
+      rc = m ? u2_walk(mode, img, m, NULL, &ux) : DX_E_FORMAT;
+      if (rc == DX_OK && (ooff = malloc((ux.cnt + 1) * sizeof(*ooff))) == NULL) rc = DX_E_NOMEM;
+      if (rc == DX_OK)
+        { total = u2_layout(&ux, rep->width, ooff);
+          ooff[ux.cnt] = total;
+          rep->records_img = ux.cnt; v.ooff = ooff; hat = ux.hat; hd = ux.hd.p;
+        }
+    }
+  if (rc == DX_E_FORMAT || rc == DX_E_UNSUPPORTED || rc == DX_E_DEGENERATE)
+    { rep->where = DX_VERIFY_IMAGE;                        /* (no image of anything) */
+      rc = DX_OK; goto done;
+    }
+  if (rc != DX_OK) goto done;
+  v.hat = hat;
+
+  /* header lines, here: the first record whose line is not the decoder's (O(records)) */
+  both = v.cnt < rep->records_img ? v.cnt : rep->records_img;
+  for (hfirst = 0; hfirst < both; hfirst++)
+    { const uint64_t at = vj_head_at(&v, hfirst), hl = v.off[hfirst] - at;
+      if (hl != hat[hfirst + 1] - hat[hfirst] || memcmp(text + at, hd + hat[hfirst], (size_t) hl) != 0) break;
+    }
+
+  /* bodies, there: of the records in front of that one */
+  v.upto = hfirst;
+  cap = verify_cap(ctx, kind == DX_KIND_QUIVA && PLAN_HAS_IMAGE(plan) ? 0 : m, total, both);
+  if (v.upto > 0)
+    { if (kind == DX_KIND_QUIVA)
+        rc = undexqv_sliced(ctx, plan, rep->upper, verify_slice, &v, cap ? cap : total + 1, 1);
+      else
+        { const hdr_patch h = { ux.cnt, ooff, ux.hat, ux.hd.p, NULL, NULL, 0, total };
+          rc = unpack2_slices(ctx, mode, img, m, rep->width, &ux, &h, cap ? cap : total + 1, verify_slice, &v);
+        }
+      if (rc != DX_OK && !v.failed && (rc == DX_E_FORMAT || rc == DX_E_MISMATCH || rc == DX_E_UNSUPPORTED))
+        { rep->where = DX_VERIFY_IMAGE;                    /* the decoder turned the records down */
+          rc = DX_OK; goto done;
+        }
+      if (rc != DX_OK) goto done;
+    }
+
+  if (v.hit != UINT64_MAX)                                /* a body: a byte, or one side's end */
+    { const uint64_t al = vj_body_bytes(&v, v.hit);
+      const uint64_t bl = vj_dec_bytes(&v, v.hit);
+      rep->where = v.hit_pos < al && v.hit_pos < bl ? DX_VERIFY_BODY : DX_VERIFY_LENGTH;
+      verify_place(&v, v.hit, 1, v.hit_pos);
+    }
+  else if (hfirst < both)
+    { uint64_t at = vj_head_at(&v, hfirst), hl = v.off[hfirst] - at, dl = hat[hfirst + 1] - hat[hfirst], k = 0;
+      while (k < hl && k < dl && text[at + k] == (uint8_t) hd[hat[hfirst] + k]) k++;
+      rep->where = DX_VERIFY_HEADER;
+      verify_place(&v, hfirst, 0, k);
+    }
+  else if (v.cnt != rep->records_img)
+    { rep->where = DX_VERIFY_COUNT;
+      rep->record = both;
+      rep->src_byte = both < v.cnt ? vj_head_at(&v, both) : n;
+    }
+  else
+    rep->ok = 1;
+
+  if (!rep->ok && rep->record < rep->records_img)          /* where that record stands in the image */
+    { if (kind != DX_KIND_QUIVA)
+        { uint64_t sym = 0, k;
+          for (k = v.off[rep->record]; rep->where == DX_VERIFY_BODY && k < rep->src_byte; k++) sym += text[k] != '\n';
+          rep->img_byte = ux.ioff[rep->record] + sym / 4;
+        }
+      else if (PLAN_HAS_INDEX(plan))
+        TRY(dx_d2h(ctx, &rep->img_byte, plan->dix.d_rec_off + rep->record, 8));
+      else
+        rep->img_byte = plan->x.rec_off[rep->record];
+    }
+  rc = DX_OK;
+
+done:
+  if (v.d_src) (void) dx_free(ctx, v.d_src);
+  if (v.d_arr) (void) dx_free(ctx, v.d_arr);
+  dx_file_undexqv_plan_free(plan);
+  seq_index_free(&sx); quiva_index_free(&qx); u2_index_free(&ux);
+  free(ooff);
   return rc;
 }
 

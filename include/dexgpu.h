@@ -511,6 +511,50 @@ void dx_file_undexqv_plan_free(dx_undexqv_plan *plan);
 void dx_file_free(void *p);
 
 /* ------------------------------------------------------------------------------------------
+ *  round-trip check: does the image give the text back?  (neither the reference nor its tools ever ask)
+ * ------------------------------------------------------------------------------------------ */
+/* Compares n units of two device buffers: unit i is d_a[d_a_off[i] .. + d_a_len[i]) against d_b[d_b_off[i] .. + d_b_len[i]),
+ * offsets of any alignment, lengths from 0 up.  *first_unit = the smallest index whose two ranges differ (UINT64_MAX: none
+ * does), *first_pos = the first differing byte in it -- min(a_len, b_len) when one range is the other's beginning --,
+ * *n_differ = how many units differ.  n_differ == NULL: not counted, and units behind a difference already found are not
+ * read.  One read of the answer per call (it waits for the context's stream).  Reads 2 bytes per byte compared, writes nothing
+ * else (csrc/verify/dx_verify.hip).                                                                                  */
+int dx_verify_ranges(dx_ctx *ctx, const uint8_t *d_a, const uint64_t *d_a_off, const uint32_t *d_a_len,
+                     const uint8_t *d_b, const uint64_t *d_b_off, const uint32_t *d_b_len, uint64_t n,
+                     uint64_t *first_unit, uint32_t *first_pos, uint64_t *n_differ);
+
+enum { DX_KIND_FASTA = 0, DX_KIND_ARROW = 1, DX_KIND_QUIVA = 2 };
+enum { DX_VERIFY_NONE = 0,      /* nothing differs */
+       DX_VERIFY_HEADER = 1,    /* a header line is not the one the decoder prints */
+       DX_VERIFY_BODY = 2,      /* a byte of a record's sequence / QV lines differs */
+       DX_VERIFY_LENGTH = 3,    /* the lines of one side end where the other's go on */
+       DX_VERIFY_COUNT = 4,     /* one side has more records */
+       DX_VERIFY_IMAGE = 5 };   /* the image does not parse or decode (dx_last_error has the library's words) */
+typedef struct
+  { int32_t  ok;                /* 1: decoding the image with the options below gives the text back, byte for byte */
+    int32_t  upper;             /* the case the text wants: undexta / undexqv -U (arrow: 0) */
+    uint32_t width;             /* the line width the text wants: undexta / undexar -w (quiva: 0) */
+    int32_t  where;             /* DX_VERIFY_*; what follows describes the FIRST record, in file order, that differs in any way */
+    uint64_t records_src, records_img;
+    uint64_t record;            /* 0-based (COUNT: the first record only one side has; IMAGE: 0) */
+    uint64_t line;              /* 0-based line of the record in the text, 0 = its header line */
+    uint64_t column;            /* 0-based byte in that line */
+    uint64_t src_byte;          /* where that is in the text */
+    uint64_t img_byte;          /* where the record begins in the image (fasta / arrow BODY: the byte that holds the symbol) */
+  } dx_verify_report;
+
+/* Is `img` (a .dexta / .dexar / .dexqv image, kind DX_KIND_*) the text it was made from?  The decode options are read off the
+ * text: upper = its first sequence (quiva: deletion tag) letter is upper case; width = the length of the first sequence line
+ * that another line of the same record follows, else the longest sequence, 1 at least.  The text is indexed and the image
+ * walked by the drivers' own code, the image decoded on the device by the decoders' own kernels, the bodies compared THERE
+ * (dx_verify_ranges: the decoded text is never downloaded), the header lines here against what the decoders print.  lossy
+ * (quiva): the text is compared after dx_qv_lossy_text -- what dexqv -l promises to keep.  A text that does not fit the device
+ * beside image and decoded text (or DEXGPU_TEXT_BUDGET) goes in slices of whole records.  DX_OK whenever there is an answer:
+ * it stands in *rep.  A text that does not index is the error it is for dx_file_pack2 / dx_file_dexqv.                 */
+int  dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const uint8_t *img, size_t m, int lossy,
+                    dx_verify_report *rep);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
