@@ -4,9 +4,16 @@
  *
  * Same flags, usage text, file naming (<dir>/<root><.ext>), -i pipe mode, -v messages, source
  * removal unless -k, error messages and exit codes as dexta.c / undexta.c / dexar.c / undexar.c /
- * dexqv.c / undexqv.c (argument macros DB.h:79-123, path helpers DB.c:112-181).  The file is
- * read whole, handed to the GPU through the whole-file drivers of libdexgpu, and the result is
- * written whole.  There is no CPU codec here: without a HIP device the tools fail loudly.
+ * dexqv.c / undexqv.c (argument macros DB.h:79-123, path helpers DB.c:112-181).  A file goes to the
+ * GPU through one of libdexgpu's file drivers, by the first of these routes whose precondition holds:
+ *   1. dexqv of a large file on one context: read from the descriptor, written at the output's offsets
+ *   2. dexta / dexar with -i, or of a very large file on one context: streamed, a chunk of records at a time
+ *   3. undexta / undexar with -i: streamed likewise
+ *      (from here on the input is read whole)
+ *   4. undexqv on one context: by a plan of its records, into the output file or, for a pipe, through memory
+ *   5. dexqv on one context, undexta, undexar into a file of ours: chunk by chunk at the output's offsets
+ *   6. everything else, a file sharded over several contexts included: converted and written whole
+ * There is no CPU codec here: without a HIP device the tools fail loudly.
  */
 #include <pthread.h>
 #include <sys/stat.h>
@@ -16,6 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
+#include <time.h>
 #include <unistd.h>
 
 #include "cli_common.h"
@@ -73,8 +81,8 @@ static uint8_t *slurp(FILE *f, size_t *n, int *mapped)
 #ifdef MADV_POPULATE_READ
           size_t at;
           for (at = 0; at < (size_t) st.st_size; at += (size_t) 16 << 20)
-            { size_t len = (size_t) st.st_size - at < ((size_t) 16 << 20) ? (size_t) st.st_size - at : (size_t) 16 << 20;
-              if (madvise((uint8_t *) m + at, len, MADV_POPULATE_READ) != 0)
+            { size_t piece = (size_t) st.st_size - at < ((size_t) 16 << 20) ? (size_t) st.st_size - at : (size_t) 16 << 20;
+              if (madvise((uint8_t *) m + at, piece, MADV_POPULATE_READ) != 0)
                 break;                                   /* (older kernel: the pages fault in when they are read) */
             }
 #endif
@@ -215,179 +223,40 @@ static void report_text_error(int tool, uint64_t line, int code)
 
 /* ---- one file --------------------------------------------------------------------------------- */
 
+typedef struct { int tool, verbose, keep, pipe, upper, lossy, width; } options;
+
+/* one file's way through a tool */
+typedef struct
+  { char    *pwd, *root, *src, *dst;         /* names (with -i: root alone) */
+    FILE    *input, *output;
+    int      out_fd, seek;                   /* seek: the output was written at its offsets, the stream's position is still to follow */
+    uint8_t *in;  size_t n;  int mapped;     /* the whole input, once read_input has run, and how unslurp releases it */
+    uint8_t  key[2];  size_t nkey;           /* the input's first bytes (an image's endian key, for the reference's words about a wrong one) */
+    dx_ctx  *ctx;                            /* the context the route took */
+    size_t   out_len;
+    uint64_t line;  int code;                /* where and why a text is malformed (DX_E_FORMAT) */
+  } job;
+
+/* DEXGPU_TIMING=1: wall-clock marks on stderr (where an end-to-end run spends its time) */
+static void tmark(const char *what)
+{ static double t0 = -1.0;
+  struct timespec ts;
+  double now;
+  if (getenv("DEXGPU_TIMING") == NULL) return;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  now = ts.tv_sec + 1e-9 * ts.tv_nsec;
+  if (t0 < 0) t0 = now;
+  fprintf(stderr, "[%s %8.1f ms] %s\n", Prog, (now - t0) * 1e3, what);
+}
+
+/* ---- the GPU contexts --------------------------------------------------------------------------- */
+
+/* They are opened on a second thread while the first input file is being read
+   (HIP initialisation and a large read each take a few hundred milliseconds). */
 static dx_ctx *Ctxs[64];     /* DEXGPU_DEVICES: one context per listed GPU; a file's entries are sharded over them */
 static int     Nctx = 0;
-
-static int report_failure(dx_ctx *ctx, int tool, const uint8_t *in, size_t n, int rc, uint64_t line, int code);
-
-static int convert(dx_ctx *ctx, int tool, const uint8_t *in, size_t n, int opt_U, int opt_l, int width,
-                   uint8_t **out, size_t *out_len)
-{ uint64_t line = 0;
-  int      code = 0, rc;
-  if (tool == TOOL_DEXQV && Nctx > 1)
-    rc = dx_file_dexqv_sharded(Ctxs, Nctx, in, n, opt_l, out, out_len, &line, &code);
-  else if ((tool == TOOL_DEXTA || tool == TOOL_DEXAR) && Nctx > 1)
-    rc = dx_file_pack2_sharded(Ctxs, Nctx, tool == TOOL_DEXAR, in, n, out, out_len, &line, &code);
-  else
-  switch (tool)
-    { case TOOL_DEXTA:   rc = dx_file_pack2(ctx, 0, in, n, out, out_len, &line, &code); break;
-      case TOOL_DEXAR:   rc = dx_file_pack2(ctx, 1, in, n, out, out_len, &line, &code); break;
-      case TOOL_UNDEXTA: rc = dx_file_unpack2(ctx, opt_U ? DX_LETTERS_UPPER : DX_LETTERS_LOWER, in, n, (uint32_t) width, out, out_len); break;
-      case TOOL_UNDEXAR: rc = dx_file_unpack2(ctx, DX_LETTERS_ARROW, in, n, (uint32_t) width, out, out_len); break;
-      case TOOL_DEXQV:   rc = dx_file_dexqv(ctx, in, n, opt_l, out, out_len, &line, &code); break;
-      default:           rc = dx_file_undexqv(ctx, in, n, opt_U, out, out_len); break;
-    }
-  return rc == DX_OK ? 0 : report_failure(ctx, tool, in, n, rc, line, code);
-}
-
-/* sinks of dx_file_undexqv_run: the output file at its offset / a buffer */
-static int sink_pwrite(void *user, uint8_t *data, size_t len, size_t at)
-{ const int fd = *(int *) user;
-  size_t done = 0;
-  while (done < len)
-    { ssize_t k = pwrite(fd, data + done, len - done, (off_t) (at + done));
-      if (k <= 0) return 1;
-      done += (size_t) k;
-    }
-  return 0;
-}
-
-/* a pipe: the chunks come in file order (dx_file_pack2_stream) */
-static int sink_stream(void *user, uint8_t *data, size_t len, size_t at)
-{ (void) at;
-  return fwrite(data, 1, len, (FILE *) user) != len;
-}
-
-/* dx_read_fn over a descriptor: a pipe gives what it has, so ask until the want is met or the input ends */
-static long read_fd(void *user, void *buf, size_t want)
-{ const int fd = *(int *) user;
-  size_t got = 0;
-  while (got < want)
-    { const ssize_t k = read(fd, (uint8_t *) buf + got, want - got);
-      if (k < 0) return -1;
-      if (k == 0) break;
-      got += (size_t) k;
-    }
-  return (long) got;
-}
-
-/* ... with the input's first bytes looked at beforehand (an image's endian key, for the reference's words about a wrong one) */
-typedef struct { int fd; uint8_t pre[2]; size_t npre, given; } peek_fd;
-static long read_peeked(void *user, void *buf, size_t want)
-{ peek_fd *p = user;
-  size_t got = 0;
-  while (p->given < p->npre && got < want) ((uint8_t *) buf)[got++] = p->pre[p->given++];
-  if (got < want)
-    { const long k = read_fd(&p->fd, (uint8_t *) buf + got, want - got);
-      if (k < 0) return -1;
-      got += (size_t) k;
-    }
-  return (long) got;
-}
-
-static int sink_memory(void *user, uint8_t *data, size_t len, size_t at)
-{ memcpy((uint8_t *) user + at, data, len);
-  return 0;
-}
-
-/* ... and a large output file whose size is known (undexqv: the plan's) or can be guessed (dexqv: three tenths of the text):
-   a helper thread allocates its pages a stretch at a time while the text is still on its way -- one posix_fallocate call for
-   20 GB takes a second during which nothing else goes on --, and the sink writes a chunk (pwrite, in order, one thread) as soon
-   as the pages under it are there; what the guess leaves out the write allocates itself, what it has too much ftruncate takes
-   back.  For dexqv, whose output is ready while its pages can still be laid out beside the upload (5.7 GB: 0.93 -> 0.49 s).
-   (Measured and not kept for undexqv's 20 GB of text: the chunks copied into a shared mapping of the file by six threads -- every
-   page of the mapping faults once: 3.1 s where one thread's pwrite takes 2.0, and several threads' pwrite queue up behind the
-   inode's lock; the allocator beside the writer -- the two take turns at that lock: 2.1 - 4.5 s; the file allocated whole, then
-   written, is what undexqv does: 0.9 + 2.0 s.)  A full file system is an error return of posix_fallocate or pwrite.       */
-#define OUT_STRETCH ((size_t) 256 << 20)
-typedef struct
-  { size_t n; int fd, failed; size_t upto;
-    pthread_mutex_t mx; pthread_cond_t cv; pthread_t th; int threaded;
-  } outfile;
-
-static void *outfile_alloc(void *arg)
-{ outfile *o = arg;
-  size_t off;
-  for (off = 0; off < o->n; off += OUT_STRETCH)
-    { const size_t len = o->n - off < OUT_STRETCH ? o->n - off : OUT_STRETCH;
-      /* The size is a guess and laying pages out ahead is a convenience: when the file system will not (ENOSPC on an
-         over-estimate, EOPNOTSUPP / EINVAL where there is no fallocate) the writer simply goes on without -- pwrite
-         reports what is really wrong with the output, if anything is.                                             */
-      const int bad = posix_fallocate(o->fd, (off_t) off, (off_t) len) != 0;
-      pthread_mutex_lock(&o->mx);
-      o->upto = bad ? o->n : off + len;
-      pthread_cond_broadcast(&o->cv);
-      pthread_mutex_unlock(&o->mx);
-      if (bad) break;
-    }
-  return NULL;
-}
-
-static int outfile_begin(outfile *o, FILE *f, size_t expect)
-{ memset(o, 0, sizeof(*o));
-  o->fd = fileno(f); o->n = expect;
-  { const size_t least = (size_t) dx_test_num("outfile_min", (long long) 1 << 30);          /* (tests: that way from this size on) */
-    if (expect < least || expect == 0 || !file_is_ours(f)) return 0;
-  }
-  pthread_mutex_init(&o->mx, NULL);
-  pthread_cond_init(&o->cv, NULL);
-  o->threaded = pthread_create(&o->th, NULL, outfile_alloc, o) == 0;
-  if (!o->threaded) (void) outfile_alloc(o);
-  return 1;
-}
-
-static int sink_outfile(void *user, uint8_t *data, size_t len, size_t at)
-{ outfile *o = user;
-  const size_t want = at + len < o->n ? at + len : o->n;    /* (behind the expected size: the write allocates) */
-  int bad;
-  pthread_mutex_lock(&o->mx);
-  while (o->upto < want && !o->failed) pthread_cond_wait(&o->cv, &o->mx);
-  bad = o->failed;
-  pthread_mutex_unlock(&o->mx);
-  return bad ? 1 : sink_pwrite(&o->fd, data, len, at);
-}
-
-static int outfile_end(outfile *o, size_t size)             /* 0: the file is complete, `size` bytes long */
-{ int bad;
-  if (o->threaded) pthread_join(o->th, NULL);
-  bad = o->failed;
-  pthread_cond_destroy(&o->cv);
-  pthread_mutex_destroy(&o->mx);
-  return bad || ftruncate(o->fd, (off_t) size) != 0 || lseek(o->fd, (off_t) size, SEEK_SET) < 0;
-}
-
-static int report_failure(dx_ctx *ctx, int tool, const uint8_t *in, size_t n, int rc, uint64_t line, int code)
-{ if (rc == DX_E_FORMAT && (tool == TOOL_DEXTA || tool == TOOL_DEXAR || tool == TOOL_DEXQV))
-    { report_text_error(tool, line, code);
-      return 1;
-    }
-  if (rc == DX_E_FORMAT && n >= 2 && (tool == TOOL_UNDEXTA || tool == TOOL_UNDEXAR))
-    { uint16_t key;
-      memcpy(&key, in, 2);
-      if (key != 0x55aa && key != 0xaa55 && !(tool == TOOL_UNDEXTA && (key == 0x33cc || key == 0xcc33)))
-        { fprintf(stderr, "%s: Not a .%s file, endian key invalid\n", Prog, TOOLS[tool].what);   /* undexta.c:156 */
-          return 1;
-        }
-    }
-  if (rc == DX_E_FORMAT)
-    { fprintf(stderr, "%s: System error, read failed!\n", Prog);                                 /* DB.h:136-139 */
-      return 2;
-    }
-  { const char *why = dx_last_error(ctx);
-    if (why == NULL || why[0] == '\0')                    /* (host-side failures carry a code only) */
-      why = rc == DX_E_DEGENERATE ? "a stream that needs a Huffman scheme holds no symbols (e.g. a deletion line of nothing but its run "
-                                    "character, or an empty file): the reference reads out of bounds there (QV.c:201), nothing is written"
-          : rc == DX_E_NOMEM      ? "out of memory"
-          : rc == DX_E_UNSUPPORTED ? "a code longer than 16 bits: the reference would write a file its own decoder cannot read"
-          : "failed";
-    fprintf(stderr, "%s: %s (libdexgpu error %d)\n", Prog, why, rc);
-  }
-  return 1;
-}
-
-/* The GPU contexts are opened on a second thread while the first input file is being read
-   (HIP initialisation and a large read each take a few hundred milliseconds). */
 static dx_ctx *Ctx0 = NULL;
+
 static void *open_contexts(void *arg)
 { dx_ctx *ctx = NULL;
   int     k;
@@ -426,26 +295,327 @@ static void *open_contexts(void *arg)
 static pthread_t Opener;
 static int       Opening = 0;
 
-/* leave only after the opener thread is done: exit() while HIP initialises on another thread is unsafe */
-static void leave(int code)
+/* Ctx0, Ctxs and Nctx are the opener's until this has waited for it */
+static dx_ctx *opened(void)
 { if (Opening)
     { pthread_join(Opener, NULL);
       Opening = 0;
     }
-  exit(code);
+  return Ctx0;
 }
 
-/* DEXGPU_TIMING=1: wall-clock marks on stderr (where an end-to-end run spends its time) */
-#include <time.h>
-static void tmark(const char *what)
-{ static double t0 = -1.0;
-  struct timespec ts;
-  double now;
-  if (getenv("DEXGPU_TIMING") == NULL) return;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  now = ts.tv_sec + 1e-9 * ts.tv_nsec;
-  if (t0 < 0) t0 = now;
-  fprintf(stderr, "[%s %8.1f ms] %s\n", Prog, (now - t0) * 1e3, what);
+/* leave only after the opener thread is done: exit() while HIP initialises on another thread is unsafe */
+static void leave(int code) { (void) opened(); exit(code); }
+
+/* a route takes the context when it has nothing left to do beside the opener */
+static dx_ctx *context(void)
+{ dx_ctx *ctx = opened();
+  tmark("GPU context open");
+  return ctx;
+}
+
+/* Is there but one context?  Without DEXGPU_DEVICES the opener leaves Ctxs and Nctx alone and the environment says so: the
+   opener goes on beside the reading of the input.  With it the count is the opener's to give, so it is waited for first. */
+static int one_context(void)
+{ const char *devs = getenv("DEXGPU_DEVICES");
+  if (devs != NULL && *devs != '\0') (void) opened();
+  return Nctx <= 1;
+}
+
+/* ---- sinks and sources of the file drivers ------------------------------------------------------ */
+
+/* the output file at its offset */
+static int sink_pwrite(void *user, uint8_t *data, size_t len, size_t at)
+{ const int fd = *(int *) user;
+  size_t done = 0;
+  while (done < len)
+    { ssize_t k = pwrite(fd, data + done, len - done, (off_t) (at + done));
+      if (k <= 0) return 1;
+      done += (size_t) k;
+    }
+  return 0;
+}
+
+/* ... sink_pwrite's user for a run's output; the end of the run moves the stream's position behind what was written */
+static void *at_offsets(job *f) { f->seek = 1; return &f->out_fd; }
+
+/* a pipe: the chunks come in file order (dx_file_pack2_stream) */
+static int sink_stream(void *user, uint8_t *data, size_t len, size_t at)
+{ (void) at;
+  return fwrite(data, 1, len, (FILE *) user) != len;
+}
+
+static int sink_memory(void *user, uint8_t *data, size_t len, size_t at)
+{ memcpy((uint8_t *) user + at, data, len);
+  return 0;
+}
+
+/* dx_read_fn over a descriptor: a pipe gives what it has, so ask until the want is met or the input ends */
+static long read_fd(void *user, void *buf, size_t want)
+{ const int fd = *(int *) user;
+  size_t got = 0;
+  while (got < want)
+    { const ssize_t k = read(fd, (uint8_t *) buf + got, want - got);
+      if (k < 0) return -1;
+      if (k == 0) break;
+      got += (size_t) k;
+    }
+  return (long) got;
+}
+
+/* ... with the input's first bytes looked at beforehand (a job's key) */
+typedef struct { int fd; const uint8_t *pre; size_t npre, given; } peek_fd;
+static long read_peeked(void *user, void *buf, size_t want)
+{ peek_fd *p = user;
+  size_t got = 0;
+  while (p->given < p->npre && got < want) ((uint8_t *) buf)[got++] = p->pre[p->given++];
+  if (got < want)
+    { const long k = read_fd(&p->fd, (uint8_t *) buf + got, want - got);
+      if (k < 0) return -1;
+      got += (size_t) k;
+    }
+  return (long) got;
+}
+
+/* ... and a large output file whose size is known (undexqv: the plan's) or can be guessed (dexqv: three tenths of the text):
+   a helper thread allocates its pages a stretch at a time while the text is still on its way -- one posix_fallocate call for
+   20 GB takes a second during which nothing else goes on --, and the sink writes a chunk (pwrite, in order, one thread) as soon
+   as the pages under it are there; what the guess leaves out the write allocates itself, what it has too much ftruncate takes
+   back.  For dexqv, whose output is ready while its pages can still be laid out beside the upload (5.7 GB: 0.93 -> 0.49 s).
+   (Measured and not kept for undexqv's 20 GB of text: the chunks copied into a shared mapping of the file by six threads -- every
+   page of the mapping faults once: 3.1 s where one thread's pwrite takes 2.0, and several threads' pwrite queue up behind the
+   inode's lock; the allocator beside the writer -- the two take turns at that lock: 2.1 - 4.5 s; the file allocated whole, then
+   written, is what undexqv does: 0.9 + 2.0 s.)  A full file system is an error return of posix_fallocate or pwrite.       */
+#define OUT_STRETCH ((size_t) 256 << 20)
+typedef struct
+  { size_t n; int fd; size_t upto;
+    pthread_mutex_t mx; pthread_cond_t cv; pthread_t th; int threaded;
+  } outfile;
+
+static void *outfile_alloc(void *arg)
+{ outfile *o = arg;
+  size_t off;
+  for (off = 0; off < o->n; off += OUT_STRETCH)
+    { const size_t len = o->n - off < OUT_STRETCH ? o->n - off : OUT_STRETCH;
+      /* The size is a guess and laying pages out ahead is a convenience: when the file system will not (ENOSPC on an
+         over-estimate, EOPNOTSUPP / EINVAL where there is no fallocate) the writer simply goes on without -- pwrite
+         reports what is really wrong with the output, if anything is.                                             */
+      const int bad = posix_fallocate(o->fd, (off_t) off, (off_t) len) != 0;
+      pthread_mutex_lock(&o->mx);
+      o->upto = bad ? o->n : off + len;
+      pthread_cond_broadcast(&o->cv);
+      pthread_mutex_unlock(&o->mx);
+      if (bad) break;
+    }
+  return NULL;
+}
+
+static int outfile_begin(outfile *o, FILE *f, size_t expect)
+{ memset(o, 0, sizeof(*o));
+  o->fd = fileno(f); o->n = expect;
+  { const size_t least = (size_t) dx_test_num("outfile_min", (long long) 1 << 30);          /* (tests: that way from this size on) */
+    if (expect < least || expect == 0 || !file_is_ours(f)) return 0;
+  }
+  pthread_mutex_init(&o->mx, NULL);
+  pthread_cond_init(&o->cv, NULL);
+  o->threaded = pthread_create(&o->th, NULL, outfile_alloc, o) == 0;
+  if (!o->threaded) (void) outfile_alloc(o);
+  return 1;
+}
+
+static int sink_outfile(void *user, uint8_t *data, size_t len, size_t at)
+{ outfile *o = user;
+  const size_t want = at + len < o->n ? at + len : o->n;    /* (behind the expected size: the write allocates) */
+  pthread_mutex_lock(&o->mx);
+  while (o->upto < want) pthread_cond_wait(&o->cv, &o->mx);
+  pthread_mutex_unlock(&o->mx);
+  return sink_pwrite(&o->fd, data, len, at);
+}
+
+static int outfile_end(outfile *o, size_t size)             /* 0: the file is complete, `size` bytes long */
+{ if (o->threaded) pthread_join(o->th, NULL);
+  pthread_cond_destroy(&o->cv);
+  pthread_mutex_destroy(&o->mx);
+  return ftruncate(o->fd, (off_t) size) != 0 || lseek(o->fd, (off_t) size, SEEK_SET) < 0;
+}
+
+/* ---- the routes, in the order they are asked ---------------------------------------------------- */
+
+/* A route's answer when its precondition does not hold: the next one is asked (as after DX_E_AGAIN, a driver's own "not this way"). */
+#define NOT_MINE 1
+
+/* the size of a regular file, -1 of anything else */
+static off_t file_size(FILE *f)
+{ struct stat st;
+  return fstat(fileno(f), &st) == 0 && S_ISREG(st.st_mode) ? st.st_size : -1;
+}
+
+static int letters(const options *o) { return o->tool == TOOL_UNDEXAR ? DX_LETTERS_ARROW : (o->upper ? DX_LETTERS_UPPER : DX_LETTERS_LOWER); }
+
+/* 1. A large .quiva is read from its file straight into the buffers that go to the GPU (dx_file_dexqv_fd_to): no image of it in
+   this process, whose pages a mapping brings in one by one and gives back one by one (a second and a half of the two and a half
+   a 20 GB file took).  DX_E_AGAIN: the driver wants it in memory after all. */
+static int dexqv_from_descriptor(const options *o, job *f)
+{ const off_t size = file_size(f->input);
+  outfile of;
+  int rc;
+  if (o->tool != TOOL_DEXQV || o->pipe || !one_context() || size <= 0 ||
+      size < (off_t) dx_test_num("fd_min", (long long) 256 << 20) || !file_is_ours(f->output))       /* (tests: that way from this size on) */
+    return NOT_MINE;
+  f->ctx = context();
+  if (!outfile_begin(&of, f->output, (size_t) size / 10 * 3))                                          /* (a .dexqv is about three tenths of its .quiva) */
+    return dx_file_dexqv_fd_to(f->ctx, fileno(f->input), (size_t) size, o->lossy, sink_pwrite, at_offsets(f), &f->out_len, &f->line, &f->code);
+  rc = dx_file_dexqv_fd_to(f->ctx, fileno(f->input), (size_t) size, o->lossy, sink_outfile, &of, &f->out_len, &f->line, &f->code);
+  if (outfile_end(&of, rc == DX_OK ? f->out_len : 0) && rc == DX_OK) rc = DX_E_IO;
+  return rc;
+}
+
+/* 2. dexta -i / dexar -i, and a file too large to hold beside its image (8 GiB and more): the text goes through the device a chunk
+   of whole records at a time (dx_file_pack2_stream) -- as the reference reads record after record (dexta.c:104-205), with a
+   chunk's memory whatever the input's size.  (Smaller files stay whole: a mapping, one upload, one pass -- 0.9 s for 4 GB where
+   the pieces, one after the other, take 1.6.) */
+static int pack2_streamed(const options *o, job *f)
+{ const off_t size = file_size(f->input);
+  int fdin = fileno(f->input);
+  if ((o->tool != TOOL_DEXTA && o->tool != TOOL_DEXAR) || !one_context() ||
+      !(o->pipe || (size >= 0 && size >= (off_t) dx_test_num("fd_min", (long long) 8 << 30) && file_is_ours(f->output))))
+    return NOT_MINE;
+  f->ctx = context();
+  if (o->pipe || !file_is_ours(f->output))          /* (a pipe: 64 MiB at a time -- the memory stays small, the pipe sets the pace) */
+    return dx_file_pack2_stream(f->ctx, o->tool == TOOL_DEXAR, read_fd, &fdin, (size_t) dx_test_num("stream_chunk", (long long) 64 << 20),
+                                sink_stream, f->output, &f->out_len, &f->line, &f->code);
+  return dx_file_pack2_stream(f->ctx, o->tool == TOOL_DEXAR, read_fd, &fdin, 0, sink_pwrite, at_offsets(f), &f->out_len, &f->line, &f->code);
+}
+
+/* 3. undexta -i / undexar -i: the image through the device a chunk of whole records at a time, their text out in order
+   (the reference reads and writes record after record, undexta.c:175-271) */
+static int unpack2_streamed(const options *o, job *f)
+{ peek_fd pk = { fileno(f->input), f->key, 0, 0 };
+  long k;
+  if ((o->tool != TOOL_UNDEXTA && o->tool != TOOL_UNDEXAR) || !o->pipe) return NOT_MINE;
+  k = read_fd(&pk.fd, f->key, 2);
+  pk.npre = f->nkey = k > 0 ? (size_t) k : 0;
+  f->ctx = context();
+  return dx_file_unpack2_stream(f->ctx, letters(o), read_peeked, &pk, 0, (uint32_t) o->width, sink_stream, f->output, &f->out_len);
+}
+
+/* Every route behind this one has the whole input before it. */
+static int read_input(const options *o, job *f)
+{ (void) o;
+  f->in = slurp(f->input, &f->n, &f->mapped);
+  tmark("input read");
+  f->nkey = f->in == NULL ? 0 : (f->n < 2 ? f->n : 2);
+  if (f->nkey > 0) memcpy(f->key, f->in, f->nkey);
+  return NOT_MINE;
+}
+
+/* 4. undexqv: the text goes from the GPU into the output file chunk by chunk (no image of it in this process): its size comes
+   from the host walk over the record stream, which runs while the GPU context is still being opened, and so does the
+   allocation of the file's pages. */
+static int undexqv_by_plan(const options *o, job *f)
+{ dx_undexqv_plan *plan = NULL;
+  int rc;
+  if (o->tool != TOOL_UNDEXQV || f->in == NULL || !one_context()) return NOT_MINE;
+  if (f->n >= ((size_t) 256 << 20))                  /* a large file: its records are walked on the GPU (dx_file_undexqv_plan_on) */
+    rc = dx_file_undexqv_plan_on(f->ctx = opened(), f->in, f->n, &plan, &f->out_len);
+  else
+    rc = dx_file_undexqv_plan(f->in, f->n, &plan, &f->out_len);
+  tmark("records walked");
+  if (rc != DX_OK) return rc;
+  { const int direct = file_is_ours(f->output) && (f->out_len == 0 || posix_fallocate(f->out_fd, 0, (off_t) f->out_len) == 0) &&
+                       ftruncate(f->out_fd, (off_t) f->out_len) == 0;
+    tmark("output file allocated");
+    f->ctx = context();
+    if (direct)
+      rc = dx_file_undexqv_run(f->ctx, plan, o->upper, sink_pwrite, at_offsets(f));
+    else                                             /* a pipe: through memory */
+      { uint8_t *out = malloc(f->out_len + 16);
+        rc = out == NULL ? DX_E_NOMEM : dx_file_undexqv_run(f->ctx, plan, o->upper, sink_memory, out);
+        if (rc == DX_OK && f->out_len > 0 && fwrite(out, 1, f->out_len, f->output) != f->out_len) rc = DX_E_IO;
+        free(out);
+      }
+  }
+  dx_file_undexqv_plan_free(plan);
+  return rc;
+}
+
+/* 5. dexqv on one context, undexta, undexar: the output goes from the GPU into the output file chunk by chunk, if that is a
+   regular file of ours */
+static int into_our_file(const options *o, job *f)
+{ const int qv = o->tool == TOOL_DEXQV;
+  if (f->in == NULL || !(qv ? one_context() : (o->tool == TOOL_UNDEXTA || o->tool == TOOL_UNDEXAR)) || !file_is_ours(f->output))
+    return NOT_MINE;
+  f->ctx = context();
+  if (qv)
+    return dx_file_dexqv_to(f->ctx, f->in, f->n, o->lossy, sink_pwrite, at_offsets(f), &f->out_len, &f->line, &f->code);
+  return dx_file_unpack2_to(f->ctx, letters(o), f->in, f->n, (uint32_t) o->width, sink_pwrite, at_offsets(f), &f->out_len);
+}
+
+/* 6. Everything else -- a file over several contexts among it -- is converted whole in memory and its image written whole. */
+static int whole_in_memory(const options *o, job *f)
+{ uint8_t *out = NULL;
+  int rc;
+  f->ctx = context();
+  if (f->in == NULL)
+    { fprintf(stderr, "%s: Out of memory (Allocating read buffer)\n", Prog);
+      leave(1);
+    }
+  if (o->tool == TOOL_DEXQV && Nctx > 1)
+    rc = dx_file_dexqv_sharded(Ctxs, Nctx, f->in, f->n, o->lossy, &out, &f->out_len, &f->line, &f->code);
+  else if ((o->tool == TOOL_DEXTA || o->tool == TOOL_DEXAR) && Nctx > 1)
+    rc = dx_file_pack2_sharded(Ctxs, Nctx, o->tool == TOOL_DEXAR, f->in, f->n, &out, &f->out_len, &f->line, &f->code);
+  else if (o->tool == TOOL_DEXTA || o->tool == TOOL_DEXAR)
+    rc = dx_file_pack2(f->ctx, o->tool == TOOL_DEXAR, f->in, f->n, &out, &f->out_len, &f->line, &f->code);
+  else if (o->tool == TOOL_DEXQV)
+    rc = dx_file_dexqv(f->ctx, f->in, f->n, o->lossy, &out, &f->out_len, &f->line, &f->code);
+  else if (o->tool == TOOL_UNDEXQV)
+    rc = dx_file_undexqv(f->ctx, f->in, f->n, o->upper, &out, &f->out_len);
+  else
+    rc = dx_file_unpack2(f->ctx, letters(o), f->in, f->n, (uint32_t) o->width, &out, &f->out_len);
+  if (rc != DX_OK) return rc;
+  tmark("converted (index, copies, kernels)");
+  if (write_image(f->output, out, f->out_len) != 0) rc = DX_E_IO;
+  dx_file_free(out);
+  return rc;
+}
+
+static int (*const ROUTES[])(const options *, job *) =
+  { dexqv_from_descriptor, pack2_streamed, unpack2_streamed, read_input, undexqv_by_plan, into_our_file, whole_in_memory };
+
+/* ---- a file's beginning and end ----------------------------------------------------------------- */
+
+/* a route's failure in the reference's words; the exit status */
+static int report_failure(int tool, const job *f, int rc)
+{ if (rc == DX_E_IO)
+    { fprintf(stderr, "%s: System error, write failed!\n", Prog);
+      return 2;
+    }
+  if (rc == DX_E_FORMAT && (tool == TOOL_DEXTA || tool == TOOL_DEXAR || tool == TOOL_DEXQV))
+    { report_text_error(tool, f->line, f->code);
+      return 1;
+    }
+  if (rc == DX_E_FORMAT && f->nkey >= 2 && (tool == TOOL_UNDEXTA || tool == TOOL_UNDEXAR))
+    { uint16_t key;
+      memcpy(&key, f->key, 2);
+      if (key != 0x55aa && key != 0xaa55 && !(tool == TOOL_UNDEXTA && (key == 0x33cc || key == 0xcc33)))
+        { fprintf(stderr, "%s: Not a .%s file, endian key invalid\n", Prog, TOOLS[tool].what);   /* undexta.c:156 */
+          return 1;
+        }
+    }
+  if (rc == DX_E_FORMAT)
+    { fprintf(stderr, "%s: System error, read failed!\n", Prog);                                 /* DB.h:136-139 */
+      return 2;
+    }
+  { const char *why = dx_last_error(f->ctx);
+    if (why == NULL || why[0] == '\0')                    /* (host-side failures carry a code only) */
+      why = rc == DX_E_DEGENERATE ? "a stream that needs a Huffman scheme holds no symbols (e.g. a deletion line of nothing but its run "
+                                    "character, or an empty file): the reference reads out of bounds there (QV.c:201), nothing is written"
+          : rc == DX_E_NOMEM      ? "out of memory"
+          : rc == DX_E_UNSUPPORTED ? "a code longer than 16 bits: the reference would write a file its own decoder cannot read"
+          : "failed";
+    fprintf(stderr, "%s: %s (libdexgpu error %d)\n", Prog, why, rc);
+  }
+  return 1;
 }
 
 /* DEXGPU_VERIFY=1 (dexta, dexar, dexqv of a file): before the source goes, is it what the file just written gives back?  Both as
@@ -481,27 +651,89 @@ static int verified_on_disk(dx_ctx *ctx, int tool, const char *src, const char *
   return ok;
 }
 
-int dex_tool_main(int tool, int argc, char *argv[])
-{ const tool_t *t = &TOOLS[tool];
-  int     flags[128], i, j, k, width = 80;
-  int     VERBOSE, KEEP, PIPE, UPPER, LOSSY;
-  dx_ctx *ctx = NULL;
+/* the files behind a name (dexta.c:87-94), or the standard streams */
+static void begin(const options *o, const char *name, job *f)
+{ const tool_t *t = &TOOLS[o->tool];
+  memset(f, 0, sizeof(*f));
+  if (o->pipe)
+    { f->input  = stdin;
+      f->output = stdout;
+      f->root   = strdup("Standard Input");
+    }
+  else
+    { f->pwd  = path_to(name);
+      f->root = root_of(name, t->src_ext);
+      f->src  = catenate(f->pwd, f->root, t->src_ext);
+      f->dst  = catenate(f->pwd, f->root, t->dst_ext);
+      if ((f->input = fopen(f->src, "r")) == NULL)
+        { fprintf(stderr, "%s: Cannot open %s for 'r'\n", Prog, f->src);   /* Fopen, DB.c:103-110 */
+          leave(1);
+        }
+      if ((f->output = fopen(f->dst, "w+")) == NULL)         /* (readable too: a large output is written through a shared mapping, which wants that) */
+        { fprintf(stderr, "%s: Cannot open %s for 'w'\n", Prog, f->dst);
+          leave(1);
+        }
+    }
+  f->out_fd = fileno(f->output);
+  if (o->verbose)
+    { fprintf(stderr, "Processing '%s' ...\n", f->root);
+      fflush(stderr);
+    }
+}
 
-  Prog = t->name;
+/* The one end of a file's run, whichever route it took and whatever that answered. */
+static void end(const options *o, job *f, int rc)
+{ if (rc == DX_OK && f->seek && lseek(f->out_fd, (off_t) f->out_len, SEEK_SET) < 0) rc = DX_E_IO;
+  if (rc == DX_OK)
+    { if (f->in != NULL) unslurp(f->in, f->n, f->mapped);
+      tmark("output written");
+      if (!o->pipe) fclose(f->input);
+      if (o->pipe ? fflush(f->output) != 0 : fclose(f->output) != 0)   /* a deferred write error (ENOSPC, quota, NFS) surfaces here: */
+        rc = DX_E_IO;                                                  /* the source must survive it */
+    }
+  if (rc != DX_OK)
+    leave(report_failure(o->tool, f, rc));
+  if (!o->pipe)
+    { const char *verify = getenv("DEXGPU_VERIFY");
+      if ((o->tool == TOOL_DEXTA || o->tool == TOOL_DEXAR || o->tool == TOOL_DEXQV) && verify != NULL && atoi(verify) != 0)
+        { if (!verified_on_disk(f->ctx, o->tool, f->src, f->dst, o->lossy, o->verbose))
+            leave(3);                                    /* (the reference's tools leave with 1 and 2; the files that follow are not touched) */
+          tmark("verified");
+        }
+      if (!o->keep) unlink(f->src);
+    }
+  free(f->root); free(f->pwd); free(f->src); free(f->dst);
+  if (o->verbose)
+    { fprintf(stderr, "Done\n");
+      fflush(stderr);
+    }
+}
+
+/* ---- the tool ----------------------------------------------------------------------------------- */
+
+/* The options and, in argv[1..], the file names; the number of both is returned.  Argument errors leave here, in the reference's
+   words, before any thread is started. */
+static int parse_arguments(int tool, int argc, char *argv[], options *o)
+{ const tool_t *t = &TOOLS[tool];
+  int flags[128], i, j, k;
+
   memset(flags, 0, sizeof(flags));
+  memset(o, 0, sizeof(*o));
+  o->tool  = tool;
+  o->width = 80;
 
   j = 1;                                                   /* ARG_INIT / ARG_FLAGS, DB.h:79-91 */
   for (i = 1; i < argc; i++)
     if (argv[i][0] == '-')
       { if (argv[i][1] == 'w' && (tool == TOOL_UNDEXTA || tool == TOOL_UNDEXAR))
           { char *eptr;                                    /* ARG_NON_NEGATIVE, DB.h:105-115 */
-            width = (int) strtol(argv[i] + 2, &eptr, 10);
+            o->width = (int) strtol(argv[i] + 2, &eptr, 10);
             if (*eptr != '\0' || argv[i][2] == '\0')
               { fprintf(stderr, "%s: -%c '%s' argument is not an integer\n", Prog, argv[i][1], argv[i] + 2);
                 exit(1);
               }
-            if (width < 0)
-              { fprintf(stderr, "%s: %s must be non-negative (%d)\n", Prog, "Line width", width);
+            if (o->width < 0)
+              { fprintf(stderr, "%s: %s must be non-negative (%d)\n", Prog, "Line width", o->width);
                 exit(1);
               }
             continue;
@@ -518,13 +750,13 @@ int dex_tool_main(int tool, int argc, char *argv[])
       argv[j++] = argv[i];
   argc = j;
 
-  VERBOSE = flags['v'];
-  KEEP    = flags['k'];
-  PIPE    = flags['i'];
-  UPPER   = flags['U'];
-  LOSSY   = flags['l'];
+  o->verbose = flags['v'];
+  o->pipe    = flags['i'];
+  o->keep    = flags['k'] || o->pipe;
+  o->upper   = flags['U'];
+  o->lossy   = flags['l'];
 
-  if ((t->pipe_ok && ((PIPE && argc > 1) || (!PIPE && argc <= 1))) || (!t->pipe_ok && argc == 1))
+  if ((t->pipe_ok && ((o->pipe && argc > 1) || (!o->pipe && argc <= 1))) || (!t->pipe_ok && argc == 1))
     { fprintf(stderr, "Usage: %s %s\n", Prog, t->usage);   /* e.g. dexta.c:47-54 */
       fprintf(stderr, "\n");
       for (k = 0; k < 4; k++)
@@ -532,288 +764,51 @@ int dex_tool_main(int tool, int argc, char *argv[])
           fprintf(stderr, "%s", t->help[k]);
       exit(1);
     }
-  if (PIPE)
-    { KEEP = 1;
-      argc = 2;
-    }
-  if (width == 0)
+  if (o->width == 0)
     { fprintf(stderr, "%s: Line width must be positive (the reference never terminates on -w0)\n", Prog);
       exit(1);
     }
+  return o->pipe ? 2 : argc;                               /* (-i: one run, on the standard streams) */
+}
+
+int dex_tool_main(int tool, int argc, char *argv[])
+{ options o;
+  int     i, k;
+
+  Prog = TOOLS[tool].name;
+  argc = parse_arguments(tool, argc, argv, &o);
 
   tmark("start");
 #ifdef F_SETPIPE_SZ
-  if (PIPE) (void) fcntl(0, F_SETPIPE_SZ, 1 << 20);        /* (a pipe's 64 KB are 2 GB/s at best; no harm where stdin is none or the size is refused) */
+  if (o.pipe) (void) fcntl(0, F_SETPIPE_SZ, 1 << 20);      /* (a pipe's 64 KB are 2 GB/s at best; no harm where stdin is none or the size is refused) */
 #endif
   Opening = pthread_create(&Opener, NULL, open_contexts, NULL) == 0;
   if (!Opening) open_contexts(NULL);
   for (i = 1; i < argc; i++)
-    { char    *pwd = NULL, *root, *src = NULL, *dst = NULL;
-      FILE    *input, *output;
-      uint8_t *in, *out = NULL;
-      size_t   n = 0, out_len = 0;
-      int      st, mapped = 0;
-
-      if (PIPE)
-        { input  = stdin;
-          output = stdout;
-          root   = strdup("Standard Input");
+    { job    f;
+      int    rc = NOT_MINE;
+      size_t r;
+      begin(&o, argv[i], &f);
+      for (r = 0; r < sizeof(ROUTES) / sizeof(ROUTES[0]) && (rc == NOT_MINE || rc == DX_E_AGAIN); r++)
+        { f.seek = 0;                                      /* (what a route that passed the file on has set) */
+          rc = ROUTES[r](&o, &f);
         }
-      else
-        { pwd  = path_to(argv[i]);                         /* dexta.c:87-94 */
-          root = root_of(argv[i], t->src_ext);
-          src  = catenate(pwd, root, t->src_ext);
-          dst  = catenate(pwd, root, t->dst_ext);
-          if ((input = fopen(src, "r")) == NULL)
-            { fprintf(stderr, "%s: Cannot open %s for 'r'\n", Prog, src);   /* Fopen, DB.c:103-110 */
-              leave(1);
-            }
-          if ((output = fopen(dst, "w+")) == NULL)           /* (readable too: a large output is written through a shared mapping, which wants that) */
-            { fprintf(stderr, "%s: Cannot open %s for 'w'\n", Prog, dst);
-              leave(1);
-            }
-        }
-
-      if (VERBOSE)
-        { fprintf(stderr, "Processing '%s' ...\n", root);
-          fflush(stderr);
-        }
-
-      if (tool == TOOL_DEXQV && Nctx <= 1 && !PIPE)
-        { /* a large .quiva is read from its file straight into the buffers that go to the GPU (dx_file_dexqv_fd_to): no image
-             of it in this process, whose pages a mapping brings in one by one and gives back one by one (a second and a half
-             of the two and a half a 20 GB file took) */
-          struct stat st;
-          const off_t least = (off_t) dx_test_num("fd_min", (long long) 256 << 20);         /* (tests: that way from this size on) */
-          if (fstat(fileno(input), &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= least && st.st_size > 0 && file_is_ours(output))
-            { uint64_t line = 0;
-              int      code = 0, rc, fd = fileno(output);
-              if (Opening)
-                { pthread_join(Opener, NULL);
-                  Opening = 0;
-                }
-              ctx = Ctx0;
-              tmark("GPU context open");
-              { outfile of;                                 /* (a .dexqv is about three tenths of its .quiva) */
-                if (outfile_begin(&of, output, (size_t) st.st_size / 10 * 3))
-                  { rc = dx_file_dexqv_fd_to(ctx, fileno(input), (size_t) st.st_size, LOSSY, sink_outfile, &of, &out_len, &line, &code);
-                    if (outfile_end(&of, rc == DX_OK ? out_len : 0) && rc == DX_OK) rc = DX_E_IO;
-                  }
-                else
-                  { rc = dx_file_dexqv_fd_to(ctx, fileno(input), (size_t) st.st_size, LOSSY, sink_pwrite, &fd, &out_len, &line, &code);
-                    if (rc == DX_OK && lseek(fd, (off_t) out_len, SEEK_SET) < 0) rc = DX_E_IO;
-                  }
-              }
-              if (rc == DX_E_IO)
-                { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-                  leave(2);
-                }
-              if (rc == DX_OK)
-                { tmark("output written");
-                  goto written;
-                }
-              if (rc != DX_E_AGAIN)
-                leave(report_failure(ctx, tool, NULL, 0, rc, line, code));
-            }                                              /* (DX_E_AGAIN: through memory, below) */
-        }
-      if ((tool == TOOL_DEXTA || tool == TOOL_DEXAR) && Nctx <= 1)
-        { /* dexta -i / dexar -i, and a file too large to hold beside its image (8 GiB and more): the text goes through the device a
-             chunk of whole records at a time (dx_file_pack2_stream) -- as the reference reads record after record (dexta.c:104-205),
-             with a chunk's memory whatever the input's size.  (Smaller files stay whole: a mapping, one upload, one pass -- 0.9 s
-             for 4 GB where the pieces, one after the other, take 1.6.) */
-          struct stat st;
-          const off_t least = (off_t) dx_test_num("fd_min", (long long) 8 << 30);
-          const int   isfile = fstat(fileno(input), &st) == 0 && S_ISREG(st.st_mode);
-          if (PIPE || (isfile && st.st_size >= least && file_is_ours(output)))
-            { uint64_t line = 0;
-              int      code = 0, rc, fdin = fileno(input), fdout = fileno(output);
-              if (Opening)
-                { pthread_join(Opener, NULL);
-                  Opening = 0;
-                }
-              ctx = Ctx0;
-              tmark("GPU context open");
-              if (PIPE || !file_is_ours(output))
-                rc = dx_file_pack2_stream(ctx, tool == TOOL_DEXAR, read_fd, &fdin, (size_t) dx_test_num("stream_chunk", (long long) 64 << 20),
-                                          sink_stream, output, &out_len, &line, &code);          /* (a pipe: 64 MiB at a time -- the memory stays small, the pipe sets the pace) */
-              else
-                { rc = dx_file_pack2_stream(ctx, tool == TOOL_DEXAR, read_fd, &fdin, 0, sink_pwrite, &fdout, &out_len, &line, &code);
-                  if (rc == DX_OK && lseek(fdout, (off_t) out_len, SEEK_SET) < 0) rc = DX_E_IO;
-                }
-              if (rc == DX_E_IO)
-                { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-                  leave(2);
-                }
-              if (rc != DX_OK)
-                leave(report_failure(ctx, tool, NULL, 0, rc, line, code));
-              tmark("output written");
-              goto written;
-            }
-        }
-      if ((tool == TOOL_UNDEXTA || tool == TOOL_UNDEXAR) && PIPE)
-        { /* undexta -i / undexar -i: the image through the device a chunk of whole records at a time, their text out in order
-             (the reference reads and writes record after record, undexta.c:175-271) */
-          int     rc;
-          peek_fd pk = { fileno(input), { 0, 0 }, 0, 0 };
-          { const long k = read_fd(&pk.fd, pk.pre, 2);
-            pk.npre = k > 0 ? (size_t) k : 0;
-          }
-          if (Opening)
-            { pthread_join(Opener, NULL);
-              Opening = 0;
-            }
-          ctx = Ctx0;
-          tmark("GPU context open");
-          rc = dx_file_unpack2_stream(ctx, tool == TOOL_UNDEXAR ? DX_LETTERS_ARROW : (UPPER ? DX_LETTERS_UPPER : DX_LETTERS_LOWER),
-                                      read_peeked, &pk, 0, (uint32_t) width, sink_stream, output, &out_len);
-          if (rc == DX_E_IO)
-            { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-              leave(2);
-            }
-          if (rc != DX_OK)
-            leave(report_failure(ctx, tool, pk.pre, pk.npre, rc, 0, 0));
-          tmark("output written");
-          goto written;
-        }
-      in = slurp(input, &n, &mapped);
-      tmark("input read");
-      if (tool == TOOL_UNDEXQV && in != NULL && Nctx <= 1)
-        { /* The text goes from the GPU into the output file chunk by chunk (no image of it in this process):
-             its size comes from the host walk over the record stream, which runs while the GPU context is
-             still being opened, and so does the allocation of the file's pages. */
-          dx_undexqv_plan *plan = NULL;
-          int              rc, direct, fd = fileno(output);
-          if (n >= ((size_t) 256 << 20))                  /* a large file: its records are walked on the GPU (dx_file_undexqv_plan_on) */
-            { if (Opening)
-                { pthread_join(Opener, NULL);
-                  Opening = 0;
-                }
-              rc = dx_file_undexqv_plan_on(Ctx0, in, n, &plan, &out_len);
-            }
-          else
-            rc = dx_file_undexqv_plan(in, n, &plan, &out_len);
-          tmark("records walked");
-          if (rc == DX_OK)
-            { direct = file_is_ours(output) &&
-                       (out_len == 0 || posix_fallocate(fd, 0, (off_t) out_len) == 0) && ftruncate(fd, (off_t) out_len) == 0;
-              tmark("output file allocated");
-              if (Opening)
-                { pthread_join(Opener, NULL);
-                  Opening = 0;
-                }
-              ctx = Ctx0;
-              tmark("GPU context open");
-              if (direct)
-                { rc = dx_file_undexqv_run(ctx, plan, UPPER, sink_pwrite, &fd);
-                  if (rc == DX_OK && lseek(fd, (off_t) out_len, SEEK_SET) < 0) rc = DX_E_IO;
-                }
-              else                                        /* a pipe: through memory */
-                { out = malloc(out_len + 16);
-                  rc  = out == NULL ? DX_E_NOMEM : dx_file_undexqv_run(ctx, plan, UPPER, sink_memory, out);
-                  if (rc == DX_OK && out_len > 0 && fwrite(out, 1, out_len, output) != out_len) rc = DX_E_IO;
-                  free(out);
-                }
-              dx_file_undexqv_plan_free(plan);
-            }
-          if (rc == DX_E_IO)
-            { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-              leave(2);
-            }
-          if (rc != DX_OK)
-            leave(report_failure(Ctx0, tool, in, n, rc, 0, 0));
-          unslurp(in, n, mapped);
-          tmark("output written");
-          goto written;
-        }
-      if (Opening)
-        { pthread_join(Opener, NULL);
-          Opening = 0;
-        }
-      ctx = Ctx0;
-      tmark("GPU context open");
-      if (in == NULL)
-        { fprintf(stderr, "%s: Out of memory (Allocating read buffer)\n", Prog);
-          leave(1);
-        }
-      if ((tool == TOOL_DEXQV && Nctx <= 1) || tool == TOOL_UNDEXTA || tool == TOOL_UNDEXAR)
-        { /* the output goes from the GPU into the output file chunk by chunk, if that is a regular file of ours */
-          int         fd = fileno(output);
-          if (file_is_ours(output))
-            { uint64_t line = 0;
-              int      code = 0, rc;
-              if (tool == TOOL_DEXQV)
-                rc = dx_file_dexqv_to(ctx, in, n, LOSSY, sink_pwrite, &fd, &out_len, &line, &code);
-              else
-                rc = dx_file_unpack2_to(ctx, tool == TOOL_UNDEXAR ? DX_LETTERS_ARROW : (UPPER ? DX_LETTERS_UPPER : DX_LETTERS_LOWER),
-                                        in, n, (uint32_t) width, sink_pwrite, &fd, &out_len);
-              if (rc == DX_OK && lseek(fd, (off_t) out_len, SEEK_SET) < 0) rc = DX_E_IO;
-              if (rc == DX_E_IO)
-                { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-                  leave(2);
-                }
-              if (rc != DX_OK)
-                leave(report_failure(ctx, tool, in, n, rc, line, code));
-              unslurp(in, n, mapped);
-              tmark("output written");
-              goto written;
-            }
-        }
-      st = convert(ctx, tool, in, n, UPPER, LOSSY, width, &out, &out_len);
-      if (st != 0)
-        leave(st);
-      tmark("converted (index, copies, kernels)");
-      if (write_image(output, out, out_len) != 0)
-        { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-          leave(2);
-        }
-      dx_file_free(out);
-      unslurp(in, n, mapped);
-      tmark("output written");
-written:
-
-      if (!PIPE)
-        { fclose(input);
-          if (fclose(output) != 0)                         /* a deferred write error (ENOSPC, quota, NFS) surfaces here: */
-            { fprintf(stderr, "%s: System error, write failed!\n", Prog);   /* the source must survive it */
-              leave(2);
-            }
-          if ((tool == TOOL_DEXTA || tool == TOOL_DEXAR || tool == TOOL_DEXQV) && getenv("DEXGPU_VERIFY") != NULL && atoi(getenv("DEXGPU_VERIFY")) != 0)
-            { if (Opening)
-                { pthread_join(Opener, NULL);
-                  Opening = 0;
-                }
-              if (!verified_on_disk(Ctx0, tool, src, dst, LOSSY, VERBOSE))
-                leave(3);                                  /* (the reference's tools leave with 1 and 2; the files that follow are not touched) */
-              tmark("verified");
-            }
-          if (!KEEP)
-            unlink(src);
-        }
-      else if (fflush(output) != 0)
-        { fprintf(stderr, "%s: System error, write failed!\n", Prog);
-          leave(2);
-        }
-      free(root); free(pwd); free(src); free(dst);
-
-      if (VERBOSE)
-        { fprintf(stderr, "Done\n");
-          fflush(stderr);
-        }
+      end(&o, &f, rc);
     }
 
   /* Every output is closed (fclose has reported what there was to report), every input is released: nothing is left but to give
      back what the process holds on the device and in the HIP runtime -- 0.2 s of a 0.45 s run on a 1 GB file (r03c_cli_timing),
      which the system does by itself when the process ends.  DEXGPU_TEARDOWN=1: the orderly way (leak checkers).               */
+  (void) opened();                                         /* (never while HIP comes up on another thread) */
   if (getenv("DEXGPU_TEARDOWN") == NULL && getenv("LD_PRELOAD") == NULL && getenv("ROCP_TOOL_LIBRARIES") == NULL &&
       getenv("ROCPROFILER_REGISTER_ROOT") == NULL)        /* (a profiler, a sanitizer or a coverage run writes its output at exit) */
-    { if (Opening) { pthread_join(Opener, NULL); Opening = 0; }      /* (never while HIP comes up on another thread) */
-      tmark("leaving");
+    { tmark("leaving");
       fflush(NULL);
       _exit(0);
     }
   if (Nctx > 0)
     for (k = 0; k < Nctx; k++) dx_close(Ctxs[k]);
   else
-    dx_close(ctx);
+    dx_close(Ctx0);
   exit(0);
 }

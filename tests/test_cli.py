@@ -1,6 +1,7 @@
 """The six drop-in tools: same command-line surface, files, messages and exit codes as the
 reference's (compared live against oracle/_ref where present)."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -254,3 +255,87 @@ def test_cli_large_file_paths_on_small_files(tmp_path):
             r = subprocess.run([os.path.join(O.REF_BIN if isref else BIN, "dexqv"), "-k", name], cwd=str(d), env=env, capture_output=True)
             outs.append((r.returncode, r.stderr, _read(d / (name + ".dexqv")) if (d / (name + ".dexqv")).exists() and r.returncode == 0 else None))
         assert outs[0] == outs[1], name
+
+
+# ---- the routes a file can take through a tool (cli_common.c's header lists them) ---------------------------------------------------
+def tool_marks(stderr: bytes, tool: str):
+    """names of the tool's own DEXGPU_TIMING marks (the library's carry dx_open / dx_file in the bracket), `leaving` left out:
+    whether it is printed depends on LD_PRELOAD"""
+    names = [m.group(1).strip() for m in re.finditer(r"(?m)^\[%s\s+[\d.]+ ms\] (.*)$" % tool, stderr.decode(errors="replace"))]
+    return [n for n in names if n != "leaving"]
+
+
+def timed(tool, args, cwd, stdin=None, **env):
+    e = dict(os.environ, DEXGPU_TIMING="1")
+    e.pop("DEXGPU_DEVICES", None)
+    e.update(env)
+    r = run(tool, args, cwd, stdin=stdin, env=e)
+    assert r.returncode == 0, r.stderr
+    return r
+
+
+STREAMED = ["start", "GPU context open", "output written"]
+PLANNED = ["start", "input read", "records walked", "output file allocated", "GPU context open", "output written"]
+CHUNKED = ["start", "input read", "GPU context open", "output written"]
+WHOLE = ["start", "input read", "GPU context open", "converted (index, copies, kernels)", "output written"]
+# (tool, arguments, input: a file's kind or "-" for standard input, DEXGPU_TEST keys, other environment, the marks)
+ROUTE_CASES = [
+    ("1_descriptor_pwrite",    "dexqv",   ["-k", "x"], "quiva", dict(fd_min=1), {}, STREAMED),
+    ("1_descriptor_outfile",   "dexqv",   ["-k", "x"], "quiva", dict(fd_min=1, outfile_min=1), {}, STREAMED),
+    ("1_then_5_small_file",    "dexqv",   ["-k", "x"], "small_quiva", dict(fd_min=1), {},
+     ["start", "GPU context open", "input read", "GPU context open", "output written"]),
+    ("2_pack2_pipe",           "dexta",   ["-i"],      "-fasta", dict(stream_chunk=20000), {}, STREAMED),
+    ("2_pack2_large_file",     "dexar",   ["-k", "x"], "arrow", dict(stream_chunk=20000, fd_min=1), {}, STREAMED),
+    ("3_unpack2_pipe",         "undexta", ["-i"],      "-dexta", {}, {}, STREAMED),
+    ("4_undexqv_plan",         "undexqv", ["-k", "x"], "dexqv", dict(device_walk_min=0), {}, PLANNED),
+    ("5_dexqv_into_file",      "dexqv",   ["-k", "x"], "quiva", {}, {}, CHUNKED),
+    ("5_undexta_into_file",    "undexta", ["-k", "x"], "dexta", {}, {}, CHUNKED),
+    ("5_undexar_into_file",    "undexar", ["-k", "x"], "dexar", {}, {}, CHUNKED),
+    ("6_dexta_whole",          "dexta",   ["-k", "x"], "fasta", {}, {}, WHOLE),
+    ("6_dexqv_three_contexts", "dexqv",   ["-k", "x"], "quiva", {}, {"DEXGPU_DEVICES": "0,0,0"}, WHOLE),
+]
+
+
+def route_inputs():
+    fa = synth.make_seqfile("fasta", 400, seed=21, mean=900, width=60).text
+    ar = synth.make_seqfile("arrow", 400, seed=21, mean=900, width=60).text
+    qv = synth.make_quiva(60, seed=9, mean=8000).text                 # ~2.4 MB (the descriptor route takes 1 MiB and more)
+    return {"fasta": fa, "arrow": ar, "quiva": qv, "small_quiva": synth.make_quiva(3, seed=10, mean=500).text,
+            "dexta": O.dexta(fa), "dexar": O.dexar(ar), "dexqv": O.dexqv(qv)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ROUTE_CASES, ids=[c[0] for c in ROUTE_CASES])
+def test_cli_stage_marks_per_route(tmp_path, case):
+    """Which route a file took shows in the tool's stage marks (DEXGPU_TIMING=1), brought down to small files by the thresholds of
+    DEXGPU_TEST.  The lists are those of the commit before the routes became functions, read off its source (no GPU was to be
+    had to run its binaries beside the new ones: profiles/cli_refactor_cli.txt); the one-shot ones are the names its tools
+    printed in profiles/files_refactor_cli.txt, lines 17-20."""
+    _, tool, args, source, keys, env, want = case
+    data = route_inputs()[source.lstrip("-")]
+    if keys:
+        env = dict(env, DEXGPU_TEST=test_env(**keys))
+    if source.startswith("-"):
+        r = timed(tool, args, tmp_path, stdin=data, **env)
+    else:
+        _write(tmp_path / ("x." + source.replace("small_", "")), data)
+        r = timed(tool, args, tmp_path, **env)
+    assert tool_marks(r.stderr, tool) == want, r.stderr
+
+
+@pytest.mark.gpu
+def test_cli_device_count_is_honoured_for_large_files(tmp_path):
+    """DEXGPU_DEVICES shards a "large" file (DEXGPU_TEST=fd_min=1) too: the device list is read before the route is chosen.
+    The commit before this test fails it for dexqv: its main thread read the number of contexts while the thread that opens
+    them was still at it, saw none, and sent the file down the single-context descriptor route (`dexqv: begin`)."""
+    inputs = route_inputs()
+    env = {"DEXGPU_DEVICES": "0,0,0", "DEXGPU_TEST": test_env(fd_min=1)}
+    for tool, kind, ext, want in (("dexqv", "quiva", "dexqv", O.dexqv), ("dexta", "fasta", "dexta", O.dexta), ("dexar", "arrow", "dexar", O.dexar)):
+        _write(tmp_path / ("x." + kind), inputs[kind])
+        r = timed(tool, ["-k", "x"], tmp_path, **env)
+        assert "converted (index, copies, kernels)" in tool_marks(r.stderr, tool), r.stderr
+        assert b"dexqv: begin" not in r.stderr
+        assert _read(tmp_path / ("x." + ext)) == want(inputs[kind]), tool
+    os.remove(tmp_path / "x.quiva")
+    timed("undexqv", ["-k", "x"], tmp_path, **env)
+    assert _read(tmp_path / "x.quiva") == O.undexqv(inputs["dexqv"])
