@@ -15,7 +15,7 @@ CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 # verify/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
 HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
-C_OBJ    = $(BUILD)/dx_host.o $(BUILD)/dx_files.o $(BUILD)/dx_compat.o
+C_OBJ    = $(BUILD)/dx_host.o $(BUILD)/dx_walk_host.o $(BUILD)/dx_files.o $(BUILD)/dx_compat.o
 TOOLS    = dexta undexta dexar undexar dexqv undexqv
 
 all: lib cli
@@ -30,7 +30,7 @@ $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/dx_internal.hpp $(CSRC)/dx_device.hpp $(CSRC
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.res; rc=$$?; \
 	  grep -v "kernel-resource-usage\|^ *[0-9]* | \|^ *| *^" $(BUILD)/$*.res >&2; exit $$rc
 
-$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h include/dexgpu.h include/dexcompat.h
+$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_host.h $(CSRC)/dx_env.h include/dexgpu.h include/dexcompat.h
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 

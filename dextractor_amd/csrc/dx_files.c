@@ -18,24 +18,18 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include "dexgpu.h"
 #include "dx_env.h"
+#include "dx_host.h"
 
 void dx_file_free(void *p) { free(p); }
 
 /* DEXGPU_TIMING=1: where a file driver spends its time (stderr; the tools print their own marks beside these) */
-#include <time.h>
-#include <unistd.h>
 static void fmark(const char *what)
 { static double t0 = -1.0;
-  struct timespec ts;
-  double now;
-  if (getenv("DEXGPU_TIMING") == NULL) return;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  now = ts.tv_sec + 1e-9 * ts.tv_nsec;
-  if (t0 < 0) t0 = now;
-  fprintf(stderr, "[dx_file %8.1f ms] %s\n", (now - t0) * 1e3, what);
+  dx_mark("dx_file", &t0, what);
 }
 
 #define TRY(x) do { rc = (x); if (rc != DX_OK) goto done; } while (0)
@@ -561,10 +555,8 @@ static void rd(rsrc *r, void *dst, size_t k)
   memcpy(dst, r->p + r->at, k);
   r->at += k;
 }
-static uint16_t sw16(uint16_t v) { return (uint16_t) ((v << 8) | (v >> 8)); }
-static uint32_t sw32(uint32_t v) { return (v << 24) | ((v & 0xff00u) << 8) | ((v >> 8) & 0xff00u) | (v >> 24); }
-static int32_t  rd_i32(rsrc *r, int flip) { uint32_t v; rd(r, &v, 4); return (int32_t) (flip ? sw32(v) : v); }
-static uint16_t rd_u16(rsrc *r, int flip) { uint16_t v; rd(r, &v, 2); return flip ? sw16(v) : v; }
+static int32_t  rd_i32(rsrc *r, int flip) { uint32_t v; rd(r, &v, 4); return (int32_t) (flip ? flip32(v) : v); }
+static uint16_t rd_u16(rsrc *r, int flip) { uint16_t v; rd(r, &v, 2); return flip ? flip16(v) : v; }
 
 typedef struct { char *p; size_t len, cap; } tbuf;
 
@@ -1363,32 +1355,17 @@ static int plan_layout(dx_undexqv_plan *p)
 #define DX_DEVICE_WALK_MIN ((size_t) 256 << 20)
 int dx_file_undexqv_plan_on(dx_ctx *ctx, const uint8_t *img, size_t n, dx_undexqv_plan **plan, size_t *out_len)
 { dx_undexqv_plan *p;
-  uint16_t key;
-  size_t   at = 2, used = 0;
+  size_t   at = 0;
   int      rc, keep = 0;
   const size_t least = (size_t) dx_test_num("device_walk_min", (long long) DX_DEVICE_WALK_MIN);
 
   if (img == NULL || plan == NULL || out_len == NULL) return DX_E_ARG;
   if (ctx == NULL || n < least || n < 16 || dx_test_on("host_walk"))
     return dx_file_undexqv_plan(img, n, plan, out_len);
-  memcpy(&key, img, 2);
-  if (key != 0x55aa && key != 0xaa55)
-    return dx_file_undexqv_plan(img, n, plan, out_len);
   *plan = NULL; *out_len = 0;
   p = calloc(1, sizeof(*p));
   if (p == NULL) return DX_E_NOMEM;
-  p->x.newv = 1;
-  { uint16_t k2 = 0;                                      /* the coding, as dx_qv_walk reads it (QV.c:1222-1256) */
-    uint32_t pl = 0;
-    memcpy(&k2, img + at, 2);
-    memcpy(&pl, img + at + 6, 4);
-    if (k2 != 0x33cc) pl = ((pl & 0xffu) << 24) | ((pl & 0xff00u) << 8) | ((pl >> 8) & 0xff00u) | (pl >> 24);
-    rc = (uint64_t) pl > (uint64_t) (n - at - 10) ? DX_E_FORMAT : DX_OK;
-    if (rc == DX_OK && (p->x.prefix = malloc((size_t) pl + 1)) == NULL) rc = DX_E_NOMEM;
-    if (rc == DX_OK) rc = dx_qv_read_coding(img + at, n - at, &p->x.coding, &p->x.flip, p->x.prefix, (size_t) pl + 1, &used);
-  }
-  if (rc != DX_OK) goto host;
-  at += used;
+  if (dx_qv_read_head(img, n, &p->x, &at) != DX_OK || !p->x.newv) goto host;     /* the head, as dx_qv_walk reads it */
   { /* image, walk scratch (records 0.7, the lanes' words for the group index 1.1 of the image) and index (0.3) must fit together;
        asked before anything goes up (dx_qv_walk_device asks again, to the byte) */
     uint64_t fr = 0, all = 0;

@@ -1,0 +1,23 @@
+/*
+ * dx_host.h -- what the library's host C files (dx_host.c, dx_walk_host.c, dx_files.c) share among themselves; no part of the C-ABI.
+ */
+#ifndef DX_HOST_H
+#define DX_HOST_H
+#include <stddef.h>
+#include <stdint.h>
+#include "dexgpu.h"
+
+static inline uint16_t flip16(uint16_t v) { return (uint16_t) ((v << 8) | (v >> 8)); }
+static inline uint32_t flip32(uint32_t v)
+{ return (v << 24) | ((v & 0xff00u) << 8) | ((v >> 8) & 0xff00u) | (v >> 24); }
+
+/* DEXGPU_TIMING=1: "[tag  12.3 ms] what" on stderr, the time since the watch *t0 was started: by its first mark when it
+   is set to a negative value beforehand, or anew by a mark with what == NULL (which prints nothing) */
+void dx_mark(const char *tag, double *t0, const char *what);
+
+/* The head of a .dexqv image (undexqv.c:103-110, QV.c:1222-1256): the 0x55aa key of the newer layout when it is there, then
+   the coding with the prefix in front of it.  Fills newv, flip, coding and prefix (malloc'd, also when the coding behind it
+   does not read: dx_qv_index_free) of *x, which the caller has zeroed; *first = the offset of the first record. */
+int dx_qv_read_head(const uint8_t *img, size_t n, dx_qv_index *x, size_t *first);
+
+#endif

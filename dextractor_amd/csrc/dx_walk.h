@@ -1,8 +1,8 @@
 /*
- * dx_walk.h -- what the host (dx_host.c: the look-up tables of the record walk) and the device walk (dx_qv_walk.hip) share.
+ * dx_walk.h -- what the host (dx_walk_host.c: the look-up tables of the record walk) and the device walk (dx_qv_walk.hip) share.
  *
  * A bare .dexqv stores no record or segment lengths (QV.c:1428-1481, undexqv.c:119-208): a segment's end is known only
- * after every code of it has been passed.  The tables below are the host walk's (dx_host.c: wlut, mwlut, rwlut), packed
+ * after every code of it has been passed.  The tables below are the host walk's (dx_walk_host.c: wlut, mwlut, rwlut), packed
  * to 16 bits an entry so that the six a walk needs fit a workgroup's LDS twice over per CU.
  *
  * One blob, WALK_BLOB_BYTES long, little endian:

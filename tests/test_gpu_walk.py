@@ -1,5 +1,5 @@
 """The record walk of a bare .dexqv on the device (dx_qv_walk_device, csrc/dx_qv_walk.hip) against the host walk
-(dx_qv_walk, dx_host.c) and the oracle's undexqv: undexqv.c:119-208, QV.c:1428-1481.  The device walk keeps only offsets on an
+(dx_qv_walk, dx_walk_host.c) and the oracle's undexqv: undexqv.c:119-208, QV.c:1428-1481.  The device walk keeps only offsets on an
 unbroken chain of lane walks from the first record, so its index must be the host's word for word -- on many pieces and few,
 records shorter and longer than a piece, headers with leading 255s, empty entries, every table kind."""
 import numpy as np

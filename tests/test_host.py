@@ -263,7 +263,7 @@ def test_walk_byteswapped_file():
 
 
 def test_walk_on_several_threads_equals_front_to_back(monkeypatch):
-    """Large images are walked by several host threads from guessed-and-verified record starts (dx_host.c):
+    """Large images are walked by several host threads from guessed-and-verified record starts (dx_walk_host.c):
     same index as the front-to-back walk; a damaged image is still rejected."""
     c = synth.make_quiva(900, seed=77, mean=9000)
     dx = O.dexqv(c.text)
@@ -300,6 +300,120 @@ def test_walk_older_layout():
     assert (w2["seg"] == w["seg"]).all() and (w2["hdr4"] == w["hdr4"]).all() and (w2["len"] == w["len"]).all()
     assert (np.diff(w["hdr_off"]) - np.diff(w2["hdr_off"]) == 6).all()
     assert int(w2["rec_off"][-1]) == len(leg) and w2["prefix"] == w["prefix"]
+
+
+def _group_index_by_the_layout(txt, dx):
+    """The group index of a .dexqv image as dx_layout.h and run_groups (dx_walk_host.c) say it is, from the symbols of the
+    text and the code lengths of the image's coding -> (gidx, gidx_off, gidx_none)."""
+    RUN_NONE, SUB_NONE = 0xffffffff, 255
+    cd = api.qv_read_coding(dx[2:])[0]                        # (behind the 0x55aa key)
+    lens = [np.array(cd.s[s].lens[:], np.int64) for s in range(6)]
+    lit = []                                                  # symbols a type-2 scheme writes as the escape code + 8 literal bits
+    for s in range(4):
+        b = np.array(cd.s[s].bits[:], np.int64)
+        lit.append(8 * ((cd.s[s].type == 2) & (b == b[255]) & (lens[s] == lens[s][255])))
+
+    def share(s, sym):                                        # a byte per 16 symbols: the group's code bits minus its symbols
+        L = len(sym)
+        ng = (L + 15) >> 4
+        cost = np.zeros(16 * ng, np.int64)
+        cost[:L] = (lens[s] + lit[s])[sym]
+        valid = np.minimum(16, L - 16 * np.arange(ng))
+        byte = np.zeros(4 * ((ng + 3) >> 2), np.uint8)
+        byte[:ng] = (cost.reshape(ng, 16).sum(1) - valid) & 0xff
+        if L and (cd.s[s].type == 2 or (cost.reshape(ng, 16).sum(1) - valid > 254).any()):
+            byte[0] = SUB_NONE
+        return byte.view("<u4")
+
+    def runs(s, rs, runchar, sym):                            # -> header word, the passes' 64 words each
+        L = len(sym)
+        at = np.flatnonzero(sym != runchar)                   # a token: the run in front of a symbol, and the symbol
+        run = np.diff(at, prepend=-1) - 1
+        tb = lens[rs][np.minimum(run, 255)] + 16 * (run >= 255) + (lens[s] + lit[s])[sym[at]]
+        ts = run + 1
+        cnt, words, none = len(at), [], len(at) > L + 8
+        for k0 in range(0, cnt, 512):
+            m = min(512, cnt - k0)
+            T = (m + 63) >> 6                                 # lane l: T tokens from l * T on
+            nb, span = np.zeros(64 * T, np.int64), np.zeros(64 * T, np.int64)
+            nb[:m], span[:m] = tb[k0:k0 + m], ts[k0:k0 + m]
+            nb, span = nb.reshape(64, T).sum(1), span.reshape(64, T).sum(1)
+            none = none or (span > 0xffff).any() or (nb > 0xffff).any() or nb.sum() > 13312
+            words.append(((nb | (span << 16)) & 0xffffffff).astype(np.uint32))
+        return (RUN_NONE if none else cnt), words
+
+    off, ln, _, _ = api.index_quiva(txt)
+    text = np.frombuffer(txt, np.uint8)
+    out, offs, nones = [], [0], 0
+    for o, L in zip(off.astype(np.int64), ln.astype(np.int64)):
+        d, _, i, m, s = (text[o + k * (L + 1): o + k * (L + 1) + L] for k in range(5))
+        sw = (((L + 15) >> 4) + 3) >> 2
+        hd, gd, hs, gs = RUN_NONE, [], RUN_NONE, []
+        if cd.delChar >= 0:
+            hd, gd = runs(0, 4, cd.delChar, d)
+        if cd.subChar >= 0:
+            hs, gs = runs(3, 5, cd.subChar, s)
+        nones += (cd.delChar >= 0 and hd == RUN_NONE) + (cd.subChar >= 0 and hs == RUN_NONE)
+        entry = [np.zeros(sw, np.uint32) if cd.delChar >= 0 else share(0, d), share(1, i), share(2, m),
+                 np.zeros(sw, np.uint32) if cd.subChar >= 0 else share(3, s),
+                 np.array([hd, hs, len(gd)], np.uint32)] + gd + gs            # three header words at dxl_run_base(L) = 4 * sw
+        out.append(np.concatenate(entry).astype(np.uint32))
+        offs.append(offs[-1] + len(out[-1]))
+    return (np.concatenate(out) if out else np.zeros(0, np.uint32)), np.array(offs, np.uint64), nones
+
+
+def _quiva_that_reaches_every_branch_of_the_group_index():
+    """One .quiva: entries of 0, 1, 15, 16, 17 and 65 symbols; deletion and substitution lines of exactly 0, 1, 512 and 513
+    tokens (an entry's lines are prefixes of its streams, so a length is read off the stream); an entry with a run of 300
+    in both run-coded lines (a literal run); enough symbols behind them for the coding to take a substitution run character."""
+    seed, prof = 4242, synth.pacbio_profile()
+    lens = [0, 1, 15, 16, 17, 65]
+    for line, runchar in ((0, ord("2")), (4, ord("?"))):
+        for want in (0, 1, 512, 513):
+            tok = np.cumsum(synth.qv_lines(seed, len(lens), 6000, prof)[line] != runchar)
+            L = int(np.searchsorted(tok, want, side="right")) if want == 0 else int(np.searchsorted(tok, want)) + 1
+            assert L >= 1 and tok[L - 1] == want
+            lens.append(L)
+    lens += [10000] * 20
+    c = synth.make_quiva(len(lens), seed=seed, prof=prof, lens=np.array(lens, np.uint32))
+    t = bytearray(c.text)
+    o, L = int(c.off[-1]), lens[-1]
+    for line, ch in ((0, b"2"), (1, b"N"), (4, b"?")):
+        t[o + line * (L + 1) + 1000: o + line * (L + 1) + 1300] = ch * 300
+    return bytes(t)
+
+
+def test_host_walk_group_index_is_what_the_layout_says():
+    """The words of dx_qv_walk_indexed's group index (otherwise checked only by decoding with them on a GPU) against
+    dx_layout.h and run_groups restated in numpy: a plain line's share is one byte per 16 symbols holding the group's code
+    bits minus its symbols, DXL_SUB_NONE in byte 0 for an escape scheme; three header words at dxl_run_base(L); 64 words per
+    pass of 512 tokens, lane l of a pass of m tokens taking (m + 63) >> 6 tokens from l times that on, a word being
+    bits | positions << 16."""
+    synthetic = _quiva_that_reaches_every_branch_of_the_group_index()
+    seen = set()
+    for name, txt in (("synthetic", synthetic), ("qv_type2", None), ("qv_nodel", None), ("qv_runs", None)):
+        if txt is None:
+            txt, dx = O.golden(name + ".quiva"), O.golden(name + ".dexqv")
+        else:
+            dx = O.dexqv(txt)
+        w = api.qv_walk(dx, index=True)
+        gidx, gidx_off, none = _group_index_by_the_layout(txt, dx)
+        assert (w["gidx_off"] == gidx_off).all(), name
+        assert len(w["gidx"]) == len(gidx) and (w["gidx"] == gidx).all(), (name, np.flatnonzero(w["gidx"] != gidx)[:8])
+        assert w["gidx_none"] == none, name
+        if name == "synthetic":                               # the token counts the oracle's encoder actually produced
+            assert (w["delChar"], w["subChar"]) == (ord("2"), ord("?"))
+            assert list(w["len"][:6]) == [0, 1, 15, 16, 17, 65]
+            for i in range(w["n"]):
+                rb = int(w["gidx_off"][i]) + 4 * (((int(w["len"][i]) + 15 >> 4) + 3) >> 2)
+                seen |= {("del", int(w["gidx"][rb])), ("sub", int(w["gidx"][rb + 1]))}
+            assert {(k, c) for k in ("del", "sub") for c in (0, 1, 512, 513)} <= seen
+        if name == "qv_type2":
+            assert any(api.qv_read_coding(dx[2:])[0].s[s].type == 2 for s in range(4))
+        if name == "qv_nodel":
+            assert w["delChar"] < 0
+        if name == "qv_runs":
+            assert none >= 1                                  # a line whose group does not fit its word: DXL_RUN_NONE
 
 
 def test_out_bound_covers_the_encoded_size():

@@ -1,4 +1,4 @@
-"""dx_host.c (indexers, .dexqv boundary walk, table builder) compiled with AddressSanitizer + UBSan
+"""dx_host.c and dx_walk_host.c (indexers, table builder, .dexqv boundary walk) compiled with AddressSanitizer + UBSan
 and driven over the golden files plus truncated and bit-damaged copies of them: no out-of-bounds
 access, whatever the bytes.  CPU only."""
 import glob
@@ -17,7 +17,8 @@ def test_host_code_under_asan(tmp_path):
     exe = str(tmp_path / "host_asan")
     cc = ["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host_asan", "driver.c"),
-          os.path.join(ROOT, "dextractor_amd", "csrc", "dx_host.c"), "-o", exe, "-lm"]
+          os.path.join(ROOT, "dextractor_amd", "csrc", "dx_host.c"),
+          os.path.join(ROOT, "dextractor_amd", "csrc", "dx_walk_host.c"), "-o", exe, "-lm"]
     r = subprocess.run(cc, capture_output=True)
     if r.returncode != 0 and b"sanitize" in r.stderr:
         pytest.skip("this gcc has no sanitizer runtime")

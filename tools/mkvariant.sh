@@ -17,7 +17,7 @@ for o in dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk; do
     objs="$objs build/$o.o"
   fi
 done
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o tools/variants/libdexgpu_$name.so $objs build/dx_host.o build/dx_files.o build/dx_compat.o \
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o tools/variants/libdexgpu_$name.so $objs build/dx_host.o build/dx_walk_host.o build/dx_files.o build/dx_compat.o \
     -Wl,-rpath,/opt/rocm/lib -Wl,-soname,libdexgpu.so -lpthread
 for f in $files; do
   sed -n 's/.*remark: *//p' build_var/$name/$f.res | sed 's/ \[-Rpass-analysis=kernel-resource-usage\]//' | \
