@@ -12,8 +12,8 @@ EXTRA   ?=
 HIPFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall -Wno-unused-function $(EXTRA)
 CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 
-# verify/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
-HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify
+# verify/, records/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
+HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
 C_OBJ    = $(BUILD)/dx_host.o $(BUILD)/dx_walk_host.o $(BUILD)/dx_files.o $(BUILD)/dx_compat.o
 TOOLS    = dexta undexta dexar undexar dexqv undexqv
@@ -25,7 +25,7 @@ lib: $(LIB)
 # every device compile also leaves the kernels' register / LDS / scratch use in $(BUILD)/<file>.res (compiler remarks);
 # the library target condenses them into dextractor_amd/kernel_resources.txt, which tests/test_host.py checks:
 # some kernels must stay under a register count to share a CU with another kernel
-$(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/dx_internal.hpp $(CSRC)/dx_device.hpp $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_qv_fast.hpp $(CSRC)/dx_qv_short.hpp include/dexgpu.h
+$(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/dx_internal.hpp $(CSRC)/dx_device.hpp $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_host.h $(CSRC)/dx_qv_fast.hpp $(CSRC)/dx_qv_short.hpp include/dexgpu.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.res; rc=$$?; \
 	  grep -v "kernel-resource-usage\|^ *[0-9]* | \|^ *| *^" $(BUILD)/$*.res >&2; exit $$rc

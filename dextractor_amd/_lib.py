@@ -175,6 +175,11 @@ SIGNATURES = {
     "dx_entries_add": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "dx_entries_compress": (C.c_int, [_P, _P, C.c_int, C.POINTER(QVCoding), C.POINTER(_P), C.POINTER(C.c_size_t),
                                       C.POINTER(_P)]),
+    "dx_qv_walk_records": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_uint64, C.POINTER(QVCoding), C.c_int, _P, C.POINTER(C.c_uint64)]),
+    "dx_qv_walk_records_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(QVCoding), C.c_int, _P,
+                                            C.POINTER(C.c_uint64)]),
+    "dx_entries_uncompress": (C.c_int, [_P, C.POINTER(QVCoding), C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int,
+                                        C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "dx_synth_quiva": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.c_int,
                                  C.c_char_p, _P]),
 }

@@ -238,6 +238,74 @@ class Context:
         self._chk(self.lib.dx_qv_walk_device(self.h, d_img.ptr, nbytes, first, C.byref(coding), newv, flip, C.byref(x)))
         return DeviceIndex(self, x)
 
+    def qv_walk_records_device(self, d_buf, nbytes, d_start, d_len, n, coding, d_seg, flip=False):
+        """dx_qv_walk_records_device: the five segment sizes of the n records that start at d_buf + d_start[i] (no framing
+        bytes, d_len[i] symbols a line) into d_seg (n x 5 uint32) -- with d_start as d_rec_off what qv_decode takes.  Raises
+        DexGPUError (DX_E_FORMAT, .bad_entry = the first such i) when a record does not end inside the nbytes."""
+        bad = C.c_uint64()
+        rc = self.lib.dx_qv_walk_records_device(self.h, d_buf.ptr, int(nbytes), d_start.ptr, d_len.ptr, int(n), C.byref(coding),
+                                                int(bool(flip)), d_seg.ptr, C.byref(bad))
+        if rc != 0:
+            e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
+            e.bad_entry = bad.value if bad.value != 2**64 - 1 else None
+            raise e
+
+    def entries_compress(self, lines_per_entry, lossy=False):
+        """dx_entries_new / _add / _compress (QVcoding_Scan1 + Compress_Next_QVentry1 as a batch, what dex2DB writes into a
+        .qvs track): lines_per_entry = per entry its five lines (bytes of one length) -> (coding, records: bytes -- the bare
+        record stream --, coff: uint64 [n + 1], entry i's offset in it)."""
+        e = self.lib.dx_entries_new()
+        if not e:
+            raise MemoryError("dx_entries_new")
+        try:
+            for lines in lines_per_entry:
+                lines = [bytes(x) for x in lines]
+                if len(lines) != 5 or any(len(x) != len(lines[0]) for x in lines):
+                    raise ValueError("an entry is five lines of one length")
+                rc = self.lib.dx_entries_add(e, len(lines[0]), *lines)
+                if rc != 0:
+                    raise L.DexGPUError(rc, "dx_entries_add")
+            n = len(lines_per_entry)
+            coding, rec, nb, coff = L.QVCoding(), C.c_void_p(), C.c_size_t(), C.c_void_p()
+            self._chk(self.lib.dx_entries_compress(self.h, e, int(bool(lossy)), C.byref(coding), C.byref(rec), C.byref(nb), C.byref(coff)))
+            try:
+                records = C.string_at(rec.value, nb.value)
+                offs = np.ctypeslib.as_array(C.cast(coff, C.POINTER(C.c_uint64)), (n + 1,)).copy()
+            finally:
+                self.lib.dx_file_free(rec); self.lib.dx_file_free(coff)
+            return coding, records, offs
+        finally:
+            self.lib.dx_entries_free(e)
+
+    def entries_uncompress(self, coding, records, coff, rlen, ids=None, ascii=1, flip=False):
+        """dx_entries_uncompress (Load_QVentry, DB.c:2575-2621, for a selection at once): entry ids[j] (None: every entry of
+        rlen, in order) starts at records[coff[ids[j]]] and has rlen[ids[j]] symbols a line -> (text: bytes, toff: uint64
+        [len(ids) + 1]); its five lines, '\n' after each, are text[toff[j]: toff[j + 1]].  ascii as Load_QVentry's: 1 lower-case
+        tag line, 2 upper-case, 0 numbers.  One coding per call."""
+        coff = np.ascontiguousarray(coff, dtype=np.uint64)
+        rlen = np.ascontiguousarray(rlen, dtype=np.uint32)
+        if ids is None:
+            n_ids, idp = len(rlen), None
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            if len(ids) and int(ids.max()) >= min(len(rlen), len(coff)):
+                raise IndexError("an id beyond the entries of coff / rlen")
+            n_ids, idp = len(ids), ids.ctypes.data
+        if isinstance(records, np.ndarray):
+            records = np.ascontiguousarray(records, dtype=np.uint8)
+            rp, nb = records.ctypes.data_as(C.c_void_p), records.size
+        else:
+            rp, nb = records, len(records)
+        if ids is None and len(coff) < n_ids:
+            raise IndexError("fewer offsets than lengths")
+        out, n, toff = C.c_void_p(), C.c_size_t(), C.c_void_p()
+        self._chk(self.lib.dx_entries_uncompress(self.h, C.byref(coding), int(bool(flip)), rp, nb, coff.ctypes.data, rlen.ctypes.data,
+                                                 idp, n_ids, int(ascii), C.byref(out), C.byref(n), C.byref(toff)))
+        try:
+            return C.string_at(out.value, n.value), np.ctypeslib.as_array(C.cast(toff, C.POINTER(C.c_uint64)), (n_ids + 1,)).copy()
+        finally:
+            self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
+
     def index_quiva_device(self, d_text, nbytes):
         """GPU text front end -> (off uint64, len uint32, hdr4 int32 [n,4], prefix_len); raises
         DexGPUError(DX_E_FORMAT) with .line / .idx_code on a malformed image."""
@@ -569,6 +637,30 @@ def qv_walk(img: bytes, index=False):
                 "delChar": x.coding.delChar, "subChar": x.coding.subChar}
     finally:
         lib.dx_qv_index_free(C.byref(x))
+
+
+def qv_walk_records(buf, start, rlen, coding, flip=False):
+    """dx_qv_walk_records (host, no GPU): the five segment sizes of the records that start at buf[start[i]] (no framing bytes,
+    rlen[i] symbols a line) -> uint32 [n, 5].  Raises DexGPUError (DX_E_FORMAT, .bad_entry = the first such i) when a record
+    does not end inside buf."""
+    lib = L.load()
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    rlen = np.ascontiguousarray(rlen, dtype=np.uint32)
+    assert len(start) == len(rlen)
+    if isinstance(buf, np.ndarray):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        bp, nb = buf.ctypes.data_as(C.c_void_p), buf.size
+    else:
+        bp, nb = buf, len(buf)
+    seg = np.zeros((len(start), 5), np.uint32)
+    bad = C.c_uint64()
+    rc = lib.dx_qv_walk_records(bp, nb, start.ctypes.data, rlen.ctypes.data, len(start), C.byref(coding), int(bool(flip)),
+                                seg.ctypes.data, C.byref(bad))
+    if rc != 0:
+        e = L.DexGPUError(rc, f"dx_qv_walk_records: entry {bad.value}")
+        e.bad_entry = bad.value if bad.value != 2**64 - 1 else None
+        raise e
+    return seg
 
 
 def frame_headers(hdr4, cnr4=None, lwell=0):

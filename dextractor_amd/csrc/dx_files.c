@@ -23,6 +23,7 @@
 #include "dexgpu.h"
 #include "dx_env.h"
 #include "dx_host.h"
+#include "dx_walk.h"
 
 void dx_file_free(void *p) { free(p); }
 
@@ -2327,5 +2328,191 @@ done:
   if (d_out) (void) dx_free(ctx, d_out);
   dfree_all(&pool);
   free(hist); free(res); free(ro);
+  return rc;
+}
+
+/* ==========================================================================================
+ *  ... and the read side: Load_QVentry (DB.c:2575-2621) = a seek to DAZZ_READ.coff and
+ *  Uncompress_Next_QVentry (QV.c:1428-1481) with the read's length, for any read in any order -- as
+ *  a batch: the selected records' segment sizes by dx_qv_walk_records_device (a lane a record), then
+ *  dx_qv_decode with the entries' starts as d_rec_off and no framing bytes.
+ *
+ *  What travels: a record's size is not stored, but it has a bound -- every line's symbols at the
+ *  longest code of its scheme (a run-coded line: a token for every symbol), and the tags.  The
+ *  selection's spans [coff, coff + bound) are merged; when they cover less than HALF of the stream
+ *  they go up packed side by side (a slice's own spans per slice), else the whole stream goes up
+ *  once -- unless the stream, with a slice of 4 MB of text beside it, is more than the device has
+ *  free: then the packed way is taken whatever is selected, since a slice's spans are what has to
+ *  fit.  A record must end inside its span: one that does not is DX_E_FORMAT in either case.
+ * ========================================================================================== */
+typedef struct { uint64_t lo, hi, j; } rspan;
+
+static int rspan_cmp(const void *a, const void *b)
+{ const rspan *x = a, *y = b;
+  return x->lo < y->lo ? -1 : x->lo > y->lo ? 1 : x->j < y->j ? -1 : x->j > y->j;
+}
+
+/* bits a symbol of a line can take at most: the longest code, an escape's literal, and in a run-coded line a run code with its literal */
+static uint32_t line_bits_most(const dx_qv_coding *cd, int sym, int run)
+{ uint32_t m = 0, r = 0;
+  int i;
+  for (i = 0; i < 256; i++)
+    { if (cd->s[sym].lens[i] > (int32_t) m) m = (uint32_t) cd->s[sym].lens[i];
+      if (run >= 0 && cd->s[run].lens[i] > (int32_t) r) r = (uint32_t) cd->s[run].lens[i];
+    }
+  return m + (cd->s[sym].type == 2 ? 8u : 0u) + (run >= 0 ? r + 16u : 0u);
+}
+
+/* bytes a record of L symbols a line takes at most (bits: line_bits_most of its four coded lines), pad words and tags included */
+static uint64_t record_bytes_most(uint64_t L, const uint32_t bits[4])
+{ uint64_t most = (L + 3) >> 2;
+  int k;
+  for (k = 0; k < 4 && L > 0; k++) most += (L * bits[k] + 7) / 8 + 8;
+  return most;
+}
+
+/* sp[0 .. m): the spans of the stream that entries j0 .. j0 + m - 1 of the selection can reach, sp[k].j = k */
+static void spans_of(rspan *sp, uint64_t j0, uint64_t m, const uint64_t *ids, const uint64_t *coff, const uint32_t *len,
+                     const uint32_t bits[4], uint64_t nbytes)
+{ uint64_t k;
+  for (k = 0; k < m; k++)
+    { const uint64_t lo = coff[ids ? ids[j0 + k] : j0 + k], most = record_bytes_most(len[j0 + k], bits);
+      sp[k].lo = lo; sp[k].j = k;
+      sp[k].hi = nbytes - lo < most ? nbytes : lo + most;
+    }
+}
+
+/* The spans of sp[0 .. m), sorted here, merged and laid side by side: rel[sp[k].j] = where span k begins in that layout; with dst the
+   bytes are copied there.  Returns the layout's bytes. */
+static uint64_t spans_pack(rspan *sp, uint64_t m, const uint8_t *records, uint8_t *dst, uint64_t *rel)
+{ uint64_t k, base = 0, lo = 0, hi = 0;
+  qsort(sp, (size_t) m, sizeof(*sp), rspan_cmp);
+  for (k = 0; k < m; k++)
+    { if (k == 0 || sp[k].lo > hi)                        /* a gap: the run of spans so far is complete */
+        { if (dst != NULL && hi > lo) memcpy(dst + base, records + lo, (size_t) (hi - lo));
+          base += hi - lo;
+          lo = sp[k].lo; hi = sp[k].hi;
+        }
+      else if (sp[k].hi > hi) hi = sp[k].hi;
+      if (rel != NULL) rel[sp[k].j] = base + (sp[k].lo - lo);
+    }
+  if (dst != NULL && hi > lo) memcpy(dst + base, records + lo, (size_t) (hi - lo));
+  return base + (hi - lo);
+}
+
+int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
+                          const uint8_t *records, size_t nbytes, const uint64_t *coff, const uint32_t *rlen,
+                          const uint64_t *ids, uint64_t n_ids,
+                          int ascii, uint8_t **text, size_t *text_bytes, uint64_t **toff)
+{ dpool     all = { {0}, 0, ctx }, pool = { {0}, 0, ctx };
+  rspan    *sp = NULL;
+  uint64_t *to = NULL, *rel = NULL, j, j0, j1, covered;
+  uint32_t *len = NULL, *seg = NULL, bits[4];
+  uint8_t  *res = NULL, *stage = NULL;
+  void     *d_whole = NULL;
+  size_t    cap;
+  int       rc = DX_OK, whole;
+
+  if (ctx == NULL || coding == NULL || text == NULL || text_bytes == NULL || toff == NULL || ascii < 0 || ascii > 2) return DX_E_ARG;
+  if (n_ids > 0 && (coff == NULL || rlen == NULL || (records == NULL && nbytes > 0))) return DX_E_ARG;
+  *text = NULL; *text_bytes = 0; *toff = NULL;
+  to  = malloc((n_ids + 1) * sizeof(*to));
+  sp  = malloc((n_ids + 1) * sizeof(*sp));
+  rel = malloc((n_ids + 1) * sizeof(*rel));
+  len = malloc((n_ids + 1) * sizeof(*len));
+  seg = malloc((n_ids + 1) * 5 * sizeof(*seg));
+  if (!to || !sp || !rel || !len || !seg) { rc = DX_E_NOMEM; goto done; }
+
+  /* the text's layout, and every entry's span of the stream */
+  bits[0] = line_bits_most(coding, DX_DEL, coding->delChar >= 0 ? DX_DRUN : -1);
+  bits[1] = line_bits_most(coding, DX_INS, -1);
+  bits[2] = line_bits_most(coding, DX_MRG, -1);
+  bits[3] = line_bits_most(coding, DX_SUB, coding->subChar >= 0 ? DX_SRUN : -1);
+  to[0] = 0;
+  for (j = 0; j < n_ids; j++)
+    { const uint64_t id = ids ? ids[j] : j, L = rlen[id];
+      if (L > 0x7fffffffu || coff[id] > nbytes)
+        { rc = dx_entry_fail(ctx, id, coff[id], nbytes); goto done; }
+      len[j] = (uint32_t) L;
+      to[j + 1] = to[j] + 5 * (L + 1);
+    }
+  res = malloc((size_t) to[n_ids] + 16);
+  if (res == NULL) { rc = DX_E_NOMEM; goto done; }
+  if (n_ids == 0) goto deliver;
+
+  spans_of(sp, 0, n_ids, ids, coff, len, bits, nbytes);
+  covered = spans_pack(sp, n_ids, records, NULL, NULL);
+  whole   = 2 * covered >= nbytes && !dx_test_on("entries_packed");        /* (tests: the packed way whatever is selected) */
+  if (whole)                                              /* ... which the device must have room for, beside a slice of text */
+    { uint64_t fr = 0, all_b = 0;
+      if (dx_mem_info(ctx, &fr, &all_b) == DX_OK && fr != 0 && (double) nbytes + (double) ((size_t) 4 << 20) > 0.9 * (double) fr) whole = 0;
+    }
+  if (dx_test_on("entries_whole")) whole = 1;
+  cap = out_cap(ctx, whole ? nbytes : (size_t) covered, (size_t) to[n_ids], n_ids);
+  TRY(dx_qv_set_coding(ctx, coding, 0));
+  if (whole) TRY(dupload(&all, records, nbytes, &d_whole));
+  else                                                    /* (no slice's spans are more than the selection's) */
+    { stage = malloc((size_t) covered + 16);
+      if (stage == NULL) { rc = DX_E_NOMEM; goto done; }
+    }
+
+  for (j0 = 0; j0 < n_ids; j0 = j1)                       /* slices of whole entries: at most cap bytes of text each (0: all at once) */
+    { const uint64_t m_most = (uint64_t) 1 << 30;
+      void    *d_in = d_whole, *d_start, *d_len, *d_seg, *d_ooff, *d_out;
+      uint64_t m, in_bytes = nbytes, bad = UINT64_MAX;
+      for (j1 = j0 + 1; j1 < n_ids && j1 - j0 < m_most && (cap == 0 || to[j1 + 1] - to[j0] <= cap); j1++) ;
+      m = j1 - j0;
+      if (whole)
+        for (j = 0; j < m; j++) rel[j] = coff[ids ? ids[j0 + j] : j0 + j];
+      else                                                /* this slice's spans, packed */
+        { spans_of(sp, j0, m, ids, coff, len, bits, nbytes);
+          in_bytes = spans_pack(sp, m, records, stage, rel);
+          TRY(dupload(&pool, stage, (size_t) in_bytes, &d_in));
+        }
+      TRY(dupload(&pool, rel, m * 8, &d_start));
+      TRY(dupload(&pool, len + j0, m * 4, &d_len));
+      TRY(dalloc(&pool, m * 20, &d_seg));
+      TRY(dalloc(&pool, m * 8, &d_ooff));
+      for (j = 0; j < m; j++) rel[j] = to[j0 + j] - to[j0];   /* the entries' places in the slice's text */
+      TRY(dx_h2d(ctx, d_ooff, rel, m * 8));
+      TRY(dalloc(&pool, (size_t) (to[j1] - to[j0]), &d_out));
+      rc = dx_qv_walk_records_device(ctx, d_in, in_bytes, d_start, d_len, m, coding, flip, d_seg, &bad);
+      if (rc == DX_E_FORMAT && bad != UINT64_MAX)
+        { const uint64_t id = ids ? ids[j0 + bad] : j0 + bad;
+          rc = dx_entry_fail(ctx, id, coff[id], nbytes);
+        }
+      if (rc != DX_OK) goto done;
+      if (!whole)                                         /* a record ends inside its own span, not in a neighbour's bytes */
+        { TRY(dx_d2h(ctx, seg, d_seg, m * 20));
+          for (j = 0; j < m; j++)
+            { const uint64_t id = ids ? ids[j0 + j] : j0 + j;
+              uint64_t used = 0;
+              int k;
+              for (k = 0; k < 5; k++) used += seg[5 * j + k];
+              if (used > record_bytes_most(len[j0 + j], bits) || used > nbytes - coff[id])
+                { rc = dx_entry_fail(ctx, id, coff[id], nbytes); goto done; }
+            }
+        }
+      TRY(dx_qv_decode(ctx, d_in, d_start, NULL, d_seg, d_len, m, (ascii == 2 ? DX_DECODE_UPPER : 0) | (flip ? DX_DECODE_FLIP : 0), d_out, d_ooff));
+      TRY(dx_d2h(ctx, res + to[j0], d_out, (size_t) (to[j1] - to[j0])));
+      dfree_all(&pool);
+    }
+  if (ascii == 0)                                         /* DB.c:2605-2610: the tag line through Number_Read (DB.c:393-416) */
+    for (j = 0; j < n_ids; j++)
+      { uint8_t *t = res + to[j] + len[j] + 1;
+        uint32_t k;
+        for (k = 0; k < len[j]; k++)
+          t[k] = t[k] == 'c' ? 1 : t[k] == 'g' ? 2 : t[k] == 't' ? 3 : 0;
+      }
+
+deliver:
+  *text = res; *text_bytes = (size_t) to[n_ids]; *toff = to;
+  res = NULL; to = NULL;
+  rc = DX_OK;
+
+done:
+  dfree_all(&pool);
+  dfree_all(&all);
+  free(sp); free(rel); free(len); free(seg); free(stage); free(res); free(to);
   return rc;
 }

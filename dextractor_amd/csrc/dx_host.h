@@ -20,4 +20,9 @@ void dx_mark(const char *tag, double *t0, const char *what);
    does not read: dx_qv_index_free) of *x, which the caller has zeroed; *first = the offset of the first record. */
 int dx_qv_read_head(const uint8_t *img, size_t n, dx_qv_index *x, size_t *first);
 
+/* DX_E_FORMAT with the words for it (dx_last_error): entry `id` of a record stream of nbytes bytes, which starts at byte `at`, does
+   not end inside the stream.  Defined beside dx_qv_walk_records_device (records/dx_qv_records.hip: a context's error text is
+   written by the device files' dx_fail); dx_entries_uncompress names the caller's entry with it, not its place in a slice. */
+int dx_entry_fail(dx_ctx *ctx, uint64_t id, uint64_t at, uint64_t nbytes);
+
 #endif

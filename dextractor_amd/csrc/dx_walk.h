@@ -1,5 +1,6 @@
 /*
- * dx_walk.h -- what the host (dx_walk_host.c: the look-up tables of the record walk) and the device walk (dx_qv_walk.hip) share.
+ * dx_walk.h -- what the host (dx_walk_host.c: the look-up tables of the record walk) and the device walks (dx_qv_walk.hip: a framed
+ * stream from its first record on; records/dx_qv_records.hip: records at known starts) share.
  *
  * A bare .dexqv stores no record or segment lengths (QV.c:1428-1481, undexqv.c:119-208): a segment's end is known only
  * after every code of it has been passed.  The tables below are the host walk's (dx_walk_host.c: wlut, mwlut, rwlut), packed

@@ -418,6 +418,55 @@ static size_t walk_record(const walk_tabs *t, const uint8_t *img, size_t n, size
   return at;
 }
 
+/* ---- records at known starts ------------------------------------------------------------------------------------------- */
+
+/* The five segments of a record without framing bytes (a .qvs track: dex2DB.c:617-621, read back by Load_QVentry,
+   DB.c:2575-2621) at buf + at, rlen symbols a line: their sizes into seg.  0: a segment does not end inside the buffer. */
+static int walk_segments(const walk_tabs *t, const uint8_t *buf, size_t n, size_t at, uint32_t rlen, uint32_t seg[5])
+{ static const struct { int sym, run; } line[5] =
+    { { DX_DEL, DX_DRUN }, { -1, -1 }, { DX_INS, -1 }, { DX_MRG, -1 }, { DX_SUB, DX_SRUN } };
+  uint32_t clen = rlen;
+  int      k;
+  if (at > n) return 0;
+  if (rlen == 0)                                          /* QV.c:436-442: nothing is written for an empty stream */
+    { memset(seg, 0, 5 * sizeof(uint32_t)); return 1; }
+  for (k = 0; k < 5; k++)
+    { const int s = line[k].sym, run = line[k].run;
+      int64_t   b;
+      if (s < 0)
+        b = at + ((clen + 3) >> 2) <= n ? (int64_t) ((clen + 3) >> 2) : -1;
+      else if (run < 0 || t->lut[run] == NULL)
+        b = walk_plain(buf + at, buf + n, rlen, t->lut[s], t->mlut[s], t->esc[s], t->flip, NULL);
+      else
+        { uint32_t nn = 0;
+          b = walk_runs(buf + at, buf + n, rlen, t->lut[s], t->esc[s], t->lut[run], t->rlut[run - DX_DRUN], &nn, t->flip, NULL, NULL);
+          if (s == DX_DEL) clen = nn;
+        }
+      if (b < 0) return 0;
+      seg[k] = (uint32_t) b; at += (size_t) b;
+    }
+  return 1;
+}
+
+int dx_qv_walk_records(const uint8_t *buf, size_t nbytes, const uint64_t *start, const uint32_t *rlen, uint64_t n,
+                       const dx_qv_coding *cd, int flip, uint32_t *seg, uint64_t *bad_entry)
+{ walk_tabs t;
+  uint64_t  i;
+  int       rc;
+  if (bad_entry) *bad_entry = UINT64_MAX;
+  if (cd == NULL || (n > 0 && (start == NULL || rlen == NULL || seg == NULL)) || (buf == NULL && nbytes > 0)) return DX_E_ARG;
+  if (n == 0) return DX_OK;
+  rc = walk_tabs_build(cd, &t);
+  t.flip = flip != 0;
+  for (i = 0; i < n && rc == DX_OK; i++)
+    if (rlen[i] > 0x7fffffffu || !walk_segments(&t, buf, nbytes, (size_t) start[i], rlen[i], seg + 5 * i))
+      { if (bad_entry) *bad_entry = i;
+        rc = DX_E_FORMAT;
+      }
+  walk_tabs_free(&t);
+  return rc;
+}
+
 /* ---- the records of an image ------------------------------------------------------------------------------------------- */
 
 /* records of img[from, to) appended to a growing list; stops at `to` exactly (returns it), behind it

@@ -1,0 +1,366 @@
+// dx_qv_records.hip -- dx_qv_walk_records_device: the segment sizes of QV records whose starts and lengths are known.
+//
+// A .qvs track (dex2DB.c:617-621; read back by Load_QVentry, DB.c:2575-2621) is a stream of records without framing bytes: per
+// entry the deletion words, the tag bytes, the insertion, merge and substitution words (QV.c:1381-1426), found through one
+// offset per entry (DAZZ_READ.coff) and decoded with the entry's length (Uncompress_Next_QVentry, QV.c:1428-1481).  The five
+// segment sizes dx_qv_decode wants are not stored: a segment ends where its last code ends, by the pad rule (QV.c:436-442).  But
+// nothing has to be found or guessed here -- every start is given --, so one record is one unit and the walk is k_walk_records:
+//
+//   * ONE LANE per record; a lane that is done takes the next record nobody has taken (a counter), so a long record holds up
+//     its own lane only.  Records may come in any order, may repeat and need not tile the buffer;
+//   * the walk needs code LENGTHS only: the look-up tables are dx_walk_luts_build's (dx_walk.h), 16 bits an entry, 80 KB in
+//     LDS -- several whole codes (a whole run-and-symbol pair) per look-up of a 12-bit window;
+//   * the 64 lanes of a wave stand in 64 different segments, so the walk is ONE loop whose body is one look-up of whatever
+//     segment the lane is in; the segment is a state of the lane, not a loop of its own;
+//   * the bits come through a ring of the segment's next 16 words per lane in LDS, filled by the wave as a whole with two
+//     16-byte loads a turn, asked for two turns before they are wanted: no look-up waits for memory;
+//   * nothing outside [0, nbytes) is read: the buffer's last bytes come from a zero-padded copy, so bytes behind the end read
+//     as zero, and a segment that would end behind the buffer is reported (the smallest such entry), not followed;
+//   * a lane cannot run on over garbage: every step passes at least one of the rlen symbols the caller gave, and a segment
+//     that has passed more than 64 bits a symbol (no token takes more than 56) is reported as well.
+//
+// This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip): it shares the tables' layout with
+// the device walk of a framed stream (dx_qv_walk.hip) but none of its code; the kernel has no entry in the profiler's name table
+// and has not been timed yet (tools/walk_records_rate.py runs it beside k_walk_pieces on the same records, for rocprofv3
+// --kernel-trace --stats).
+#include "dx_internal.hpp"
+#include "dx_device.hpp"
+#include "dx_walk.h"
+extern "C" {
+#include "dx_host.h"              // dx_entry_fail
+}
+
+#include <stdlib.h>
+
+#define REC_BLOCK      1024u             // one workgroup a CU: 80 KB of tables and 68 KB of rings
+#define REC_RLEN_MAX   (1u << 22)        // symbols a lane walks (bits passed are counted in 32 bits); longer entries are the host's
+#define REC_SERVE      4u                // a power of two: every how many turns lanes end and begin records
+#define REC_BURSTS     4                 // bursts a turn (an even number: the two sets of loads take turns)
+#define REC_LOOKUPS    8                 // look-ups a burst
+#define RING_WORDS     16u
+#define RING_STRIDE    17u               // the ring and its first word once more behind it (a window's two words never wrap); odd:
+                                         // the rows of a wave start in 32 different banks
+#define RING_BURST     5u                // words from the lane's own on that a burst may touch: 8 look-ups of <= 12 bits, and the word behind
+#define RING_STEP      4u                // ... and a step of another kind: <= 16 + 16 + 16 + 8 bits
+#define REC_HOST       0xffffffffu       // seg[5i] of an entry left to the host
+
+struct rec_args
+{ const uint8_t  *buf;
+  uint64_t        n;                      // bytes of buf
+  const uint64_t *start;
+  const uint32_t *len;
+  uint64_t        cnt;                    // records
+  const uint16_t *w16, *mw, *rw, *r1, *one;     // the blob's tables (dx_walk.h)
+  const uint8_t  *tail;                   // buf's bytes from tail_at on, zeros behind them: 256 bytes
+  uint64_t        tail_at;
+  uint32_t        rlen_max;
+  int             delChar, subChar, flip;
+  int             esc[4];
+};
+
+struct rec_lds { uint16_t t[4][4096]; uint16_t r1[2][4096]; uint16_t one[4][4096]; uint32_t ring[REC_BLOCK][RING_STRIDE]; };
+
+// MSB-first reader over a segment's 32-bit words, by position: T bits have been passed, words [T >> 5, have) are in the ring
+struct rec_reader
+{ const uint8_t *seg;           // the segment's first byte
+  uint32_t *ring;
+  uint32_t T, have;             // have: a multiple of 4
+  uint32_t asked[2];            // 16-byte loads under way in either set: 0, 1, 2
+  u32x4    got[2][2];
+};
+
+// where 16 bytes at q are read from: the buffer itself, or the padded copy of its end
+__device__ __forceinline__ const uint8_t *rec_within(const rec_args &a, const uint8_t *q)
+{ const uint64_t off = (uint64_t) (q - a.buf), t = off - a.tail_at;
+  return off < a.tail_at ? q : a.tail + (t < 240u ? t : 240u);
+}
+
+__device__ __forceinline__ void rec_commit(rec_reader &r, const u32x4 &v, int flip)
+{ const uint32_t s = r.have & (RING_WORDS - 1u);
+  uint32_t *d = r.ring + s;
+  const uint32_t x = flip ? __builtin_bswap32(v.x) : v.x;
+  d[0] = x;
+  d[1] = flip ? __builtin_bswap32(v.y) : v.y;
+  d[2] = flip ? __builtin_bswap32(v.z) : v.z;
+  d[3] = flip ? __builtin_bswap32(v.w) : v.w;
+  if (s == 0u) r.ring[RING_WORDS] = x;
+  r.have += 4u;
+}
+
+// The wave's rings are seen to together: what set SET asked for two calls ago goes into the ring, and up to two loads go out for the
+// room that will be free.  Every call issues exactly two loads whatever its lanes want (a lane that wants nothing reads the padded
+// copy, one cache line for the whole wave): loads retire in order, so the wait in front of the commit is for all but the other set's
+// two -- were the loads conditional, it would be for everything outstanding, a memory round trip a burst.
+template <int SET>
+__device__ __forceinline__ void rec_pump(rec_reader &r, const rec_args &a, bool want)
+{ if (r.asked[SET] >= 1u) rec_commit(r, r.got[SET][0], a.flip);
+  if (r.asked[SET] == 2u) rec_commit(r, r.got[SET][1], a.flip);
+  const uint32_t ahead = r.have + 4u * r.asked[SET ^ 1], occ = ahead - (r.T >> 5);      // (occ <= 8: 8 more; <= 12: 4 more; the ring holds 16)
+  const uint32_t u = want && occ <= 12u ? (occ <= 8u ? 2u : 1u) : 0u;
+  const uint8_t *q = r.seg + 4ull * ahead;
+  r.asked[SET]  = u;
+  r.got[SET][0] = *(const u32x4_u *) (u >= 1u ? rec_within(a, q) : a.tail);
+  r.got[SET][1] = *(const u32x4_u *) (u == 2u ? rec_within(a, q + 16) : a.tail);
+}
+
+__device__ __forceinline__ void rec_open(rec_reader &r, const rec_args &a, const uint8_t *p)
+{ r.seg = p; r.T = 0u; r.have = 0u; r.asked[0] = 0u; r.asked[1] = 0u;           // (what is under way for the segment before is dropped)
+  const u32x4 c0 = *(const u32x4_u *) rec_within(a, p), c1 = *(const u32x4_u *) rec_within(a, p + 16);
+  rec_commit(r, c0, a.flip);
+  rec_commit(r, c1, a.flip);
+}
+
+__device__ __forceinline__ uint32_t rec_words(const rec_reader &r) { return r.have - (r.T >> 5); }
+
+__device__ __forceinline__ uint32_t rec_window(const rec_reader &r)            // the next 32 bits
+{ const uint32_t *p = r.ring + ((r.T >> 5) & (RING_WORDS - 1u));
+  const uint64_t two = ((uint64_t) p[0] << 32) | p[1];
+  return (uint32_t) ((two << (r.T & 31u)) >> 32);
+}
+
+__device__ __forceinline__ uint32_t rec_pad_words(uint32_t T, uint32_t last)   // QV.c:436-442
+{ const uint32_t olen = T & 31u, llen = (T - last) & 31u;
+  const uint32_t w = (T >> 5) + (olen ? 1u : 0u);
+  if (olen > 0) return w + ((llen > 16u && olen > llen) ? 1u : 0u);
+  return w + ((T > 0 && llen > 16u) ? 1u : 0u);
+}
+
+// One burst: REC_LOOKUPS look-ups of the common kind -- the window holds whole codes (a whole run-and-symbol pair) that stay
+// inside the line: skip their bits, count their symbols -- the same few instructions whichever line the lane is in, and no lane
+// branches on its own: a look-up that is none (0) or would pass the line's end changes nothing, and neither does any after it.
+// The one branch is the wave's: the burst is left once no lane of it has taken a look-up.
+template <int SET>
+__device__ __forceinline__ void rec_burst(rec_reader &r, const rec_args &a, const uint16_t *tab, uint32_t rlen,
+                                          uint32_t &j, uint32_t &nn, uint32_t &last, bool &more)
+{ rec_pump<SET>(r, a, more);
+  const bool ready = rec_words(r) >= RING_BURST;           // (a ring that is short: this burst without the lane)
+  uint32_t room = more && ready ? rlen - j : 0u;
+  bool took = false;
+  #pragma unroll 1
+  for (int it = 0; it < REC_LOOKUPS; it++)
+    { const uint32_t g = tab[rec_window(r) >> (32 - WALK_WIN)], cnt = g >> 8;
+      took = cnt - 1u < room;
+      const uint32_t c = took ? cnt : 0u;
+      r.T += took ? g & 15u : 0u; j += c; room -= c; nn += took ? 1u : 0u;
+      last = took ? (g >> 4) & 15u : last;
+      if (!__any(took)) break;
+    }
+  more = more && (took || !ready);
+}
+
+// seg[5i ..]: the sizes of record i's segments, REC_HOST in the first for an entry longer than rlen_max (res[1] counts them);
+// res[0]: the smallest i whose record does not lie inside the buffer (preset to all ones).  queue: the next record nobody has
+// taken (preset to the number of lanes launched).
+__global__ __launch_bounds__(REC_BLOCK, REC_BLOCK / 256)
+void k_walk_records(rec_args a, uint32_t *seg, unsigned long long *res, unsigned long long *queue)
+{ __shared__ rec_lds S;
+  { const uint32_t *from[6] = { (const uint32_t *) (a.delChar < 0 ? a.mw + DX_DEL * 4096u : a.rw), (const uint32_t *) (a.mw + DX_INS * 4096u),
+                                (const uint32_t *) (a.mw + DX_MRG * 4096u), (const uint32_t *) (a.subChar < 0 ? a.mw + DX_SUB * 4096u : a.rw + 4096u),
+                                (const uint32_t *) a.r1, (const uint32_t *) a.one };
+    uint32_t *to[6] = { (uint32_t *) S.t[0], (uint32_t *) S.t[1], (uint32_t *) S.t[2], (uint32_t *) S.t[3], (uint32_t *) S.r1, (uint32_t *) S.one };
+    const uint32_t words[6] = { 2048u, 2048u, 2048u, 2048u, 4096u, 8192u };
+    #pragma unroll
+    for (int k = 0; k < 6; k++)
+      for (uint32_t x = threadIdx.x; x < words[k]; x += blockDim.x) to[k][x] = from[k][x];
+  }
+  __syncthreads();
+
+  uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  bool have = i < a.cnt, fresh = have, live = false;       // have: a record is the lane's; fresh: not begun; live: being walked
+  uint64_t at = 0;                                         // the segment's first byte
+  uint32_t ph = 0, rlen = 0, j = 0, nn = 0, last = 0;      // ph: 0 del, 1 ins, 2 mrg, 3 sub
+  rec_reader rd;
+  rd.seg = a.buf; rd.ring = S.ring[threadIdx.x]; rd.T = 0; rd.have = 0; rd.asked[0] = 0; rd.asked[1] = 0;
+  rd.got[0][0] = u32x4{ 0u, 0u, 0u, 0u }; rd.got[0][1] = rd.got[0][0]; rd.got[1][0] = rd.got[0][0]; rd.got[1][1] = rd.got[0][0];
+
+  // (a lane that is done stays in the loop until its wave is: the pumps and the bursts are the wave's)
+  for (uint32_t turn = 0; ; turn++)
+    { const bool serve = (turn & (REC_SERVE - 1u)) == 0u;  // (records end and begin every REC_SERVE-th turn: memory round trips for the whole wave)
+      if (serve && have && !live && !fresh)                // the lane's record is walked: the next one
+        { const uint64_t nk = atomicAdd(queue, 1ull);
+          have = fresh = nk < a.cnt;
+          i = nk;
+        }
+      if (serve && fresh)
+        { fresh = false;
+          rlen = a.len[i]; at = a.start[i];
+          uint32_t *s = seg + 5u * i;
+          if (rlen == 0u) { s[0] = 0u; s[1] = 0u; s[2] = 0u; s[3] = 0u; s[4] = 0u; }     // QV.c:436-442: an empty stream has no words
+          else if (rlen > a.rlen_max) { s[0] = REC_HOST; atomicAdd(res + 1, 1ull); }
+          else if (at > a.n) atomicMin(res, (unsigned long long) i);
+          else
+            { live = true; ph = 0; j = 0; nn = 0; last = 0;
+              rec_open(rd, a, a.buf + at);
+            }
+        }
+      if (!__any(live || have)) break;
+
+      bool more = live, fail = false;
+      const uint16_t *tab = S.t[live ? ph : 0u];
+      #pragma unroll 1
+      for (int b = 0; b < REC_BURSTS; b += 2)
+        { rec_burst<0>(rd, a, tab, rlen, j, nn, last, more);
+          rec_burst<1>(rd, a, tab, rlen, j, nn, last, more);
+          if (!__any(more)) break;
+        }
+      // for the lanes the bursts left waiting, one step of another kind: a single code (a line's last few, a pair that does not fit
+      // the window), a code of more than 12 bits or an escape (the 16-bit tables in memory), a run's literal, a segment's end
+      if (live && !more && (j >= rlen || rec_words(rd) >= RING_STEP))
+        { const bool runs = (ph == 0u && a.delChar >= 0) || (ph == 3u && a.subChar >= 0);
+          if (j < rlen)
+            { uint32_t w = rec_window(rd) >> 16;
+              bool sym = true;
+              if (runs)                                    // the run code alone first (QV.c:604-691)
+                { const uint32_t e1 = S.r1[ph ? 1u : 0u][w >> (16 - WALK_WIN)];
+                  uint32_t c;
+                  if (e1) { last = e1 & 15u; c = e1 >> 8; rd.T += last; }
+                  else                                     // more than 12 bits, the code of 255 (a 16-bit literal follows), none
+                    { const uint32_t e = a.w16[(DX_DRUN + (ph ? 1u : 0u)) * 65536u + w];
+                      last = e >> 8; c = e & 0xffu;
+                      if (last == 0u) fail = true;
+                      rd.T += last;
+                      if (c == 255u) { c = rec_window(rd) >> 16; rd.T += 16u; last = 16u; }
+                    }
+                  if (c > rlen - j) fail = true;
+                  else j += c;
+                  sym = !fail && j < rlen;
+                  if (sym) w = rec_window(rd) >> 16;
+                }
+              if (sym)                                     // a symbol's code (QV.c:510-599)
+                { const uint32_t f = S.one[ph][w >> (16 - WALK_WIN)] & 15u;
+                  if (f) { last = f; rd.T += f; }
+                  else                                     // more than 12 bits, an escape (an 8-bit literal follows), none
+                    { const uint32_t e = a.w16[ph * 65536u + w];
+                      last = e >> 8;
+                      if (last == 0u) fail = true;
+                      rd.T += last;
+                      if (a.esc[ph] && (e & 0xffu) == 255u) { rd.T += 8u; last = 8u; }
+                    }
+                  j += 1u; nn += 1u;
+                }
+            }
+          if ((uint64_t) rd.T > 64ull * rlen + 64u) fail = true;
+          if (!fail && j >= rlen)                          // the segment's end: its bytes, and on to the next one
+            { const uint64_t bytes = 4ull * rec_pad_words(rd.T, last);
+              uint32_t *s = seg + 5u * i;
+              if (at + bytes > a.n) fail = true;
+              else
+                { s[ph ? ph + 1u : 0u] = (uint32_t) bytes;
+                  at += bytes;
+                  if (ph == 0u)                            // the tags, 2 bits for every symbol the deletion line spelt out (QV.c:810-819)
+                    { const uint32_t tb = ((runs ? nn : rlen) + 3u) >> 2;
+                      s[1] = tb;
+                      if (at + tb > a.n) fail = true;
+                      at += tb;
+                    }
+                  ph += 1u; j = 0u; nn = 0u; last = 0u;
+                  if (ph == 4u) live = false;
+                  else if (!fail) rec_open(rd, a, a.buf + at);
+                }
+            }
+          if (fail) { atomicMin(res, (unsigned long long) i); live = false; }
+        }
+    }
+}
+
+// the entries the kernel left to the host (seg[5i] == REC_HOST): each on a copy of the bytes it can reach
+static int records_on_host(dx_ctx *ctx, const uint8_t *d_buf, uint64_t nbytes, const uint64_t *d_start, const uint32_t *d_len, uint64_t n,
+                           const dx_qv_coding *cd, int flip, uint32_t *d_seg, uint64_t *bad)
+{ uint64_t *start = (uint64_t *) malloc(n * 8);
+  uint32_t *len = (uint32_t *) malloc(n * 4), *seg = (uint32_t *) malloc(n * 20);
+  uint8_t  *copy = NULL;
+  int rc = DX_OK;
+  if (!start || !len || !seg) rc = dx_fail(ctx, DX_E_NOMEM, "dx_qv_walk_records_device: out of host memory");
+  if (rc == DX_OK) rc = dx_d2h(ctx, start, d_start, n * 8);
+  if (rc == DX_OK) rc = dx_d2h(ctx, len, d_len, n * 4);
+  if (rc == DX_OK) rc = dx_d2h(ctx, seg, d_seg, n * 20);
+  for (uint64_t i = 0; i < n && rc == DX_OK; i++)
+    if (seg[5 * i] == REC_HOST)
+      { const uint64_t zero = 0, most = 40ull * len[i] + 64u;                     // (<= 64 bits a symbol and line, and the tags)
+        const uint64_t m = start[i] > nbytes ? 0 : (nbytes - start[i] < most ? nbytes - start[i] : most);
+        uint64_t b = UINT64_MAX;
+        free(copy);
+        copy = (uint8_t *) malloc(m + 16);
+        if (copy == NULL) { rc = dx_fail(ctx, DX_E_NOMEM, "dx_qv_walk_records_device: out of host memory"); break; }
+        if (m) rc = dx_d2h(ctx, copy, d_buf + start[i], m);
+        if (rc != DX_OK) break;
+        if (start[i] > nbytes || dx_qv_walk_records(copy, m, &zero, len + i, 1, cd, flip, seg + 5 * i, &b) != DX_OK)
+          { if (i < *bad) *bad = i; }                      // (a record that is cut off at `most` bytes would not have ended inside them either)
+        else
+          rc = dx_h2d(ctx, d_seg + 5 * i, seg + 5 * i, 20);
+      }
+  free(start); free(len); free(seg); free(copy);
+  return rc;
+}
+
+extern "C" int dx_entry_fail(dx_ctx *ctx, uint64_t id, uint64_t at, uint64_t nbytes)
+{ return dx_fail(ctx, DX_E_FORMAT, "entry %llu, at byte %llu, does not end inside the stream's %llu bytes",
+                 (unsigned long long) id, (unsigned long long) at, (unsigned long long) nbytes);
+}
+
+extern "C" int dx_qv_walk_records_device(dx_ctx *ctx, const uint8_t *d_buf, uint64_t nbytes, const uint64_t *d_start,
+                                         const uint32_t *d_len, uint64_t n, const dx_qv_coding *cd, int flip,
+                                         uint32_t *d_seg, uint64_t *bad_entry)
+{ if (ctx == NULL) return DX_E_ARG;
+  if (bad_entry) *bad_entry = UINT64_MAX;
+  if (cd == NULL) return dx_fail(ctx, DX_E_ARG, "dx_qv_walk_records_device: no coding");
+  if (n == 0) return DX_OK;
+  if (!d_start || !d_len || !d_seg || (!d_buf && nbytes))
+    return dx_fail(ctx, DX_E_ARG, "dx_qv_walk_records_device: NULL device pointer");
+  DX_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = dx_after_pending(ctx);
+  if (rc != DX_OK) return rc;
+
+  rec_args a;
+  memset(&a, 0, sizeof(a));
+  a.buf = d_buf; a.n = nbytes; a.start = d_start; a.len = d_len; a.cnt = n;
+  a.delChar = cd->delChar; a.subChar = cd->subChar; a.flip = flip != 0;
+  a.rlen_max = REC_RLEN_MAX;
+  { const long long v = dx_test_num("records_rlen_max", 0); if (v >= 1 && v < REC_RLEN_MAX) a.rlen_max = (uint32_t) v; }     // (tests: the host's share)
+  a.tail_at = nbytes >= 64 ? (nbytes - 64) & ~(uint64_t) 15 : 0;
+
+  uint8_t *blob = (uint8_t *) malloc(WALK_BLOB_BYTES), *d_blob = NULL, *d_tail = NULL;
+  unsigned long long *d_res = NULL, back[2] = { ~0ull, 0ull };
+#define REC_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (void) hipGetLastError(); rc = dx_fail(ctx, DX_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); goto done; } } while (0)
+  if (blob == NULL) { rc = dx_fail(ctx, DX_E_NOMEM, "dx_qv_walk_records_device: out of host memory"); goto done; }
+  rc = dx_walk_luts_build(cd, blob, a.esc);
+  if (rc != DX_OK) { rc = dx_fail(ctx, rc, "dx_qv_walk_records_device: the look-up tables could not be built"); goto done; }
+  REC_HIP(hipMalloc(&d_blob, WALK_BLOB_BYTES));
+  REC_HIP(hipMalloc(&d_tail, 256));
+  REC_HIP(hipMalloc(&d_res, 64));
+  REC_HIP(hipMemcpyAsync(d_blob, blob, WALK_BLOB_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  REC_HIP(hipMemsetAsync(d_tail, 0, 256, ctx->stream));
+  if (nbytes > a.tail_at) REC_HIP(hipMemcpyAsync(d_tail, d_buf + a.tail_at, nbytes - a.tail_at, hipMemcpyDeviceToDevice, ctx->stream));
+  a.tail = d_tail;
+  a.w16 = (const uint16_t *) (d_blob + WALK_W16_OFF); a.mw = (const uint16_t *) (d_blob + WALK_MW_OFF);
+  a.rw  = (const uint16_t *) (d_blob + WALK_RW_OFF);  a.r1 = (const uint16_t *) (d_blob + WALK_R1_OFF);
+  a.one = (const uint16_t *) (d_blob + WALK_ONE_OFF);
+  { // as many lanes as the device holds at once (a workgroup a CU), every CU busy while there are records for it; the records
+    // beyond the lanes launched wait in the queue
+    const uint64_t most = (uint64_t) ctx->num_cu * REC_BLOCK, lanes = n < most ? n : most;
+    const uint64_t waves = (lanes + 63u) / 64u, per_cu = (waves + ctx->num_cu - 1) / ctx->num_cu;
+    const uint32_t bs = per_cu >= REC_BLOCK / 64u ? REC_BLOCK : (uint32_t) (per_cu * 64u);
+    const uint32_t blocks = (uint32_t) ((lanes + bs - 1) / bs);
+    back[0] = ~0ull; back[1] = 0ull;
+    const unsigned long long init[3] = { ~0ull, 0ull, (unsigned long long) blocks * bs };
+    REC_HIP(hipMemcpyAsync(d_res, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_walk_records, dim3(blocks), dim3(bs), 0, ctx->stream, a, d_seg, d_res, d_res + 2);
+    REC_HIP(hipGetLastError());
+  }
+  REC_HIP(hipMemcpyAsync(back, d_res, 16, hipMemcpyDeviceToHost, ctx->stream));
+  REC_HIP(hipStreamSynchronize(ctx->stream));
+  { uint64_t bad = back[0];
+    if (back[1] != 0) rc = records_on_host(ctx, d_buf, nbytes, d_start, d_len, n, cd, flip, d_seg, &bad);
+    if (rc == DX_OK && bad != UINT64_MAX)
+      { uint64_t at = 0;
+        if (bad_entry) *bad_entry = bad;
+        rc = dx_d2h(ctx, &at, d_start + bad, 8);           // (the words name the record's start: it is on the device)
+        if (rc == DX_OK) rc = dx_entry_fail(ctx, bad, at, nbytes);
+      }
+  }
+done:
+  (void) hipFree(d_blob); (void) hipFree(d_tail); (void) hipFree(d_res);
+  free(blob);
+  return rc;
+#undef REC_HIP
+}

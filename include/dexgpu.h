@@ -572,6 +572,40 @@ int         dx_entries_add(dx_entries *e, int rlen, const char *del, const char 
 int         dx_entries_compress(dx_ctx *ctx, const dx_entries *e, int lossy, dx_qv_coding *coding,
                                 uint8_t **records, size_t *nbytes, uint64_t **coff);
 
+/* The read side: Load_QVentry (DB.c:2575-2621) seeks to reads[i].coff and calls Uncompress_Next_QVentry(..., rlen)
+ * (QV.c:1428-1481) for any i, in any order.  A .qvs record has no framing bytes and the format stores no segment sizes, but with
+ * every record's start and length known the records are independent: one record is one unit of work.
+ *
+ * dx_qv_walk_records (host, no GPU) / dx_qv_walk_records_device: record i's deletion segment starts at buf + start[i] and every
+ * line of it has rlen[i] symbols; seg[5i ..] receives the byte sizes of its del, tag, ins, mrg and sub segments (code lengths
+ * only are decoded; each segment ends by the pad rule, QV.c:436-442).  Starts may come in any order, may repeat and need not
+ * tile the buffer; rlen 0 gives five zeros.  DX_E_FORMAT with *bad_entry = the first such i (UINT64_MAX otherwise; may be NULL)
+ * when a segment does not end inside [0, nbytes).  flip: the code words were written byte-swapped (DX_DECODE_FLIP).
+ * The device form (csrc/records/dx_qv_records.hip) walks a record a lane and never reads outside [0, nbytes); d_start (as
+ * d_rec_off), d_seg and d_len are what dx_qv_decode takes with d_hdr_off = NULL.  Entries of more than 4 M symbols are walked by
+ * the host function on a copy of their bytes.                                                                            */
+int dx_qv_walk_records(const uint8_t *buf, size_t nbytes, const uint64_t *start, const uint32_t *rlen, uint64_t n,
+                       const dx_qv_coding *cd, int flip, uint32_t *seg /* n x 5 */, uint64_t *bad_entry);
+int dx_qv_walk_records_device(dx_ctx *ctx, const uint8_t *d_buf, uint64_t nbytes, const uint64_t *d_start,
+                              const uint32_t *d_len, uint64_t n, const dx_qv_coding *cd, int flip,
+                              uint32_t *d_seg, uint64_t *bad_entry);
+
+/* Load_QVentry for a selection of entries at once: entry ids[j] (ids == NULL: entries 0 .. n_ids - 1) starts at records +
+ * coff[ids[j]] and has rlen[ids[j]] symbols a line; its five lines, each followed by '\n' (dx_qv_decode's layout), stand at
+ * *text + toff[j], toff[n_ids] = *text_bytes (both malloc'd: dx_file_free).  ids may come in any order and may repeat.
+ * ascii as Load_QVentry's (DB.c:2602-2618): 1 the tag line in lower case, 2 in upper case, 0 as numbers 0..3 (Number_Read).
+ * coding / flip: what dx_qv_read_coding gave for the track.  ONE coding per call: a .qvs made of several files has one coding
+ * per file (DB.c:2485-2508), and the caller groups its reads by coding.
+ * Only the selected records' bytes travel: when they make up less than half of the stream they are uploaded packed side by
+ * side, else the whole stream goes up once (a stream the device has no room for goes up packed, slice by slice, whatever
+ * is selected).  A selection whose text exceeds DEXGPU_TEXT_BUDGET bytes, or what is free on the device, is decoded in slices
+ * of whole entries.  n_ids == 0: DX_OK and an empty text.  DX_E_FORMAT: an entry does not lie inside the stream
+ * (dx_last_error names it).                                                                                              */
+int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
+                          const uint8_t *records, size_t nbytes, const uint64_t *coff, const uint32_t *rlen,
+                          const uint64_t *ids, uint64_t n_ids,
+                          int ascii, uint8_t **text, size_t *text_bytes, uint64_t **toff /* n_ids + 1 */);
+
 /* ------------------------------------------------------------------------------------------
  *  seeded synthetic corpora on the device (benchmark/test plumbing; mirrors dextractor_amd/synth.py)
  * ------------------------------------------------------------------------------------------ */
