@@ -16,7 +16,7 @@ ERR_NAMES = {-1: "DX_E_ARG", -2: "DX_E_HIP", -3: "DX_E_FORMAT", -4: "DX_E_DEGENE
              -5: "DX_E_UNSUPPORTED", -6: "DX_E_NOMEM", -7: "DX_E_MISMATCH", -8: "DX_E_SPACE", -9: "DX_E_IO"}
 
 DX_ALPHA_BASES, DX_ALPHA_ARROW = 0, 1
-DX_LETTERS_LOWER, DX_LETTERS_UPPER, DX_LETTERS_ARROW = 0, 1, 2
+DX_LETTERS_LOWER, DX_LETTERS_UPPER, DX_LETTERS_ARROW, DX_LETTERS_NUMBERS = 0, 1, 2, 3
 DX_DEL, DX_INS, DX_MRG, DX_SUB, DX_DRUN, DX_SRUN = range(6)
 KERNELS = ["k_pack2_encode", "k_pack2_decode", "k_qv_prescan", "k_qv_hist", "k_qv_sizes", "k_scan",
            "k_qv_encode", "k_qv_decode", "k_synth", "k_index", "k_qv_compact", "k_qv_encode_text",
@@ -180,6 +180,9 @@ SIGNATURES = {
                                             C.POINTER(C.c_uint64)]),
     "dx_entries_uncompress": (C.c_int, [_P, C.POINTER(QVCoding), C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int,
                                         C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P)]),
+    "dx_reads_unpack": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
+    "dx_reads_uncompress": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P, _P, _P, C.c_uint64,
+                                      C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "dx_synth_quiva": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.c_int,
                                  C.c_char_p, _P]),
 }

@@ -306,6 +306,71 @@ class Context:
         finally:
             self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
 
+    def reads_unpack(self, letters, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
+        """dx_reads_unpack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
+        whole reads from symbol 0) as d_len[j] bytes of `letters` and one delimiter behind them at d_out + d_out_off[j].  Raises
+        DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie inside the in_bytes."""
+        bad = C.c_uint64()
+        rc = self.lib.dx_reads_unpack(self.h, int(letters), d_in.ptr, int(in_bytes), d_boff.ptr, d_beg.ptr if d_beg else None,
+                                      d_len.ptr, int(n), d_out.ptr, d_out_off.ptr, C.byref(bad))
+        if rc != 0:
+            e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
+            e.bad_unit = bad.value if bad.value != 2**64 - 1 else None
+            raise e
+
+    @staticmethod
+    def _reads_selection(boff, rlen, ids, beg, end):
+        """the argument checks of reads_uncompress, before any device call -> (boff, rlen, ids or None, beg or None, end or None, n)"""
+        boff = np.ascontiguousarray(boff, dtype=np.uint64)
+        rlen = np.ascontiguousarray(rlen, dtype=np.uint32)
+        if len(boff) < len(rlen):
+            raise IndexError("fewer offsets than lengths")
+        if ids is None:
+            n, of = len(rlen), rlen
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            if len(ids) and int(ids.max()) >= len(rlen):
+                raise IndexError("an id beyond the reads of boff / rlen")
+            n, of = len(ids), rlen[ids.astype(np.int64)]
+        if (beg is None) != (end is None):
+            raise ValueError("beg and end are given together")
+        if beg is not None:
+            if np.any(np.asarray(beg) < 0) or np.any(np.asarray(end) < 0):
+                raise ValueError("a negative beg or end")
+            beg = np.ascontiguousarray(beg, dtype=np.uint32)
+            end = np.ascontiguousarray(end, dtype=np.uint32)
+            if len(beg) != n or len(end) != n:
+                raise ValueError("beg / end: one value a selected read")
+            if np.any(beg > end):
+                raise ValueError("a subread with beg > end")
+            if np.any(end > of):
+                raise ValueError("a subread that ends behind its read (end > rlen)")
+        return boff, rlen, ids, beg, end, n
+
+    def reads_uncompress(self, payload, boff, rlen, ids=None, beg=None, end=None, letters=L.DX_LETTERS_NUMBERS):
+        """dx_reads_uncompress (Load_Read / Load_Subread / Load_Arrow, DB.c:1232-1381, 1508-1548, for a selection at once): read
+        ids[j] (None: every read of rlen, in order) starts at payload[boff[ids[j]]] and has rlen[ids[j]] symbols; all of it, or
+        its symbols [beg[j], end[j]) -> (text: bytes, toff: uint64 [len(ids) + 1]) in Load_All_Reads' layout: unit j is
+        text[toff[j]: toff[j + 1] - 1], a delimiter (4 for numbers, 0 for letters) in front of it and behind it."""
+        boff, rlen, ids, beg, end, n_ids = self._reads_selection(boff, rlen, ids, beg, end)
+        if not (L.DX_LETTERS_LOWER <= int(letters) <= L.DX_LETTERS_NUMBERS):
+            raise ValueError("unknown letter set")
+        if isinstance(payload, np.ndarray):
+            payload = np.ascontiguousarray(payload, dtype=np.uint8)
+            pp, nb = payload.ctypes.data_as(C.c_void_p), payload.size
+        else:
+            pp, nb = payload, len(payload)
+        out, n, toff = C.c_void_p(), C.c_size_t(), C.c_void_p()
+        self._chk(self.lib.dx_reads_uncompress(self.h, int(letters), pp, nb, boff.ctypes.data, rlen.ctypes.data,
+                                               ids.ctypes.data if ids is not None else None,
+                                               beg.ctypes.data if beg is not None else None,
+                                               end.ctypes.data if end is not None else None, n_ids,
+                                               C.byref(out), C.byref(n), C.byref(toff)))
+        try:
+            return C.string_at(out.value, n.value), np.ctypeslib.as_array(C.cast(toff, C.POINTER(C.c_uint64)), (n_ids + 1,)).copy()
+        finally:
+            self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
+
     def index_quiva_device(self, d_text, nbytes):
         """GPU text front end -> (off uint64, len uint32, hdr4 int32 [n,4], prefix_len); raises
         DexGPUError(DX_E_FORMAT) with .line / .idx_code on a malformed image."""

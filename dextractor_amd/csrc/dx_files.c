@@ -2400,6 +2400,27 @@ static uint64_t spans_pack(rspan *sp, uint64_t m, const uint8_t *records, uint8_
   return base + (hi - lo);
 }
 
+/* Does a selection's stream go up whole?  When its merged spans cover half of it or more -- and the device has room for it beside a
+   slice of text: else the packed way whatever is selected, since a slice's spans are what has to fit.  (Tests: packed_key /
+   whole_key in DEXGPU_TEST decide.) */
+static int sel_goes_whole(dx_ctx *ctx, uint64_t covered, size_t nbytes, const char *packed_key, const char *whole_key)
+{ int whole = 2 * covered >= nbytes && !dx_test_on(packed_key);
+  if (whole)
+    { uint64_t fr = 0, all_b = 0;
+      if (dx_mem_info(ctx, &fr, &all_b) == DX_OK && fr != 0 && (double) nbytes + (double) ((size_t) 4 << 20) > 0.9 * (double) fr) whole = 0;
+    }
+  if (dx_test_on(whole_key)) whole = 1;
+  return whole;
+}
+
+/* a slice of whole units of a selection from j0 on, to[] their places in the text: at most cap bytes of it (0: all at once), one unit at least */
+static uint64_t sel_slice_end(const uint64_t *to, uint64_t j0, uint64_t n_ids, size_t cap)
+{ const uint64_t m_most = (uint64_t) 1 << 30;
+  uint64_t j1;
+  for (j1 = j0 + 1; j1 < n_ids && j1 - j0 < m_most && (cap == 0 || to[j1 + 1] - to[j0] <= cap); j1++) ;
+  return j1;
+}
+
 int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
                           const uint8_t *records, size_t nbytes, const uint64_t *coff, const uint32_t *rlen,
                           const uint64_t *ids, uint64_t n_ids,
@@ -2442,12 +2463,7 @@ int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
 
   spans_of(sp, 0, n_ids, ids, coff, len, bits, nbytes);
   covered = spans_pack(sp, n_ids, records, NULL, NULL);
-  whole   = 2 * covered >= nbytes && !dx_test_on("entries_packed");        /* (tests: the packed way whatever is selected) */
-  if (whole)                                              /* ... which the device must have room for, beside a slice of text */
-    { uint64_t fr = 0, all_b = 0;
-      if (dx_mem_info(ctx, &fr, &all_b) == DX_OK && fr != 0 && (double) nbytes + (double) ((size_t) 4 << 20) > 0.9 * (double) fr) whole = 0;
-    }
-  if (dx_test_on("entries_whole")) whole = 1;
+  whole   = sel_goes_whole(ctx, covered, nbytes, "entries_packed", "entries_whole");
   cap = out_cap(ctx, whole ? nbytes : (size_t) covered, (size_t) to[n_ids], n_ids);
   TRY(dx_qv_set_coding(ctx, coding, 0));
   if (whole) TRY(dupload(&all, records, nbytes, &d_whole));
@@ -2457,11 +2473,10 @@ int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
     }
 
   for (j0 = 0; j0 < n_ids; j0 = j1)                       /* slices of whole entries: at most cap bytes of text each (0: all at once) */
-    { const uint64_t m_most = (uint64_t) 1 << 30;
-      void    *d_in = d_whole, *d_start, *d_len, *d_seg, *d_ooff, *d_out;
+    { void    *d_in = d_whole, *d_start, *d_len, *d_seg, *d_ooff, *d_out;
       uint64_t m, in_bytes = nbytes, bad = UINT64_MAX;
-      for (j1 = j0 + 1; j1 < n_ids && j1 - j0 < m_most && (cap == 0 || to[j1 + 1] - to[j0] <= cap); j1++) ;
-      m = j1 - j0;
+      j1 = sel_slice_end(to, j0, n_ids, cap);
+      m  = j1 - j0;
       if (whole)
         for (j = 0; j < m; j++) rel[j] = coff[ids ? ids[j0 + j] : j0 + j];
       else                                                /* this slice's spans, packed */
@@ -2514,5 +2529,115 @@ done:
   dfree_all(&pool);
   dfree_all(&all);
   free(sp); free(rel); free(len); free(seg); free(stage); free(res); free(to);
+  return rc;
+}
+
+/* ==========================================================================================
+ *  The .bps / .arw read side: Load_Read (DB.c:1232-1298), Load_Subread (DB.c:1308-1381), Load_Arrow
+ *  (DB.c:1508-1548) for a selection at once, in Load_All_Reads' layout (DB.c:1406-1433) -- dx_reads_unpack
+ *  on the selected units.  What travels is decided as for a .qvs track above, but a unit's span of the
+ *  payload is exact: bytes [boff + beg / 4, boff + (end - 1) / 4 + 1), cut at the payload's end.  A
+ *  span that is cut ends the packed layout as it ends the payload, so the unit reaches past the end of
+ *  what the device has either way, and the kernel's own check finds it.
+ * ========================================================================================== */
+int dx_reads_uncompress(dx_ctx *ctx, int letters, const uint8_t *payload, size_t nbytes,
+                        const uint64_t *boff, const uint32_t *rlen,
+                        const uint64_t *ids, const uint32_t *beg, const uint32_t *end, uint64_t n_ids,
+                        uint8_t **text, size_t *text_bytes, uint64_t **toff)
+{ dpool     all = { {0}, 0, ctx }, pool = { {0}, 0, ctx };
+  rspan    *sp = NULL, *un = NULL;                        /* un[j]: unit j's span; sp: a slice's, as spans_pack sorts them */
+  uint64_t *to = NULL, *rel = NULL, *at = NULL, j, j0, j1, covered;   /* at[j]: where unit j's first byte is, cut or not */
+  uint32_t *len = NULL, *ph = NULL;
+  uint8_t  *res = NULL, *stage = NULL;
+  void     *d_whole = NULL;
+  size_t    cap;
+  int       rc = DX_OK, whole;
+  const uint8_t delim = letters == DX_LETTERS_NUMBERS ? 4 : 0;    /* DB.c:362 / DB.c:367-389 */
+
+  if (ctx == NULL || text == NULL || text_bytes == NULL || toff == NULL || letters < DX_LETTERS_LOWER || letters > DX_LETTERS_NUMBERS)
+    return DX_E_ARG;
+  if ((beg == NULL) != (end == NULL)) return DX_E_ARG;
+  if (n_ids > 0 && (boff == NULL || rlen == NULL || (payload == NULL && nbytes > 0))) return DX_E_ARG;
+  *text = NULL; *text_bytes = 0; *toff = NULL;
+  to  = malloc((n_ids + 1) * sizeof(*to));
+  sp  = malloc((n_ids + 1) * sizeof(*sp));
+  un  = malloc((n_ids + 1) * sizeof(*un));
+  rel = malloc((n_ids + 1) * sizeof(*rel));
+  at  = malloc((n_ids + 1) * sizeof(*at));
+  len = malloc((n_ids + 1) * sizeof(*len));
+  ph  = malloc((n_ids + 1) * sizeof(*ph));
+  if (!to || !sp || !un || !rel || !at || !len || !ph) { rc = DX_E_NOMEM; goto done; }
+
+  /* the text's layout, and every unit's span of the payload */
+  to[0] = 1;
+  for (j = 0; j < n_ids; j++)
+    { const uint64_t id = ids ? ids[j] : j, L = rlen[id];
+      const uint64_t b = beg ? beg[j] : 0, e = end ? end[j] : L;
+      uint64_t lo, hi;
+      if (b > e || e > L || e - b > 0x7fffffffu) { rc = DX_E_ARG; goto done; }
+      if (boff[id] > nbytes)
+        { rc = dx_entry_fail(ctx, id, boff[id], nbytes); goto done; }
+      lo = boff[id] + b / 4;
+      hi = e > b ? boff[id] + (e - 1) / 4 + 1 : lo;
+      un[j].lo = lo < nbytes ? lo : nbytes;
+      un[j].hi = hi < nbytes ? hi : nbytes;
+      un[j].j  = j;
+      at[j]  = lo;
+      len[j] = (uint32_t) (e - b);
+      ph[j]  = (uint32_t) (b & 3);
+      to[j + 1] = to[j] + (e - b) + 1;
+    }
+  res = malloc((size_t) to[n_ids] + 16);
+  if (res == NULL) { rc = DX_E_NOMEM; goto done; }
+  res[0] = delim;
+  if (n_ids == 0) goto deliver;
+
+  memcpy(sp, un, (size_t) n_ids * sizeof(*sp));
+  covered = spans_pack(sp, n_ids, payload, NULL, NULL);
+  whole   = sel_goes_whole(ctx, covered, nbytes, "reads_packed", "reads_whole");
+  cap     = out_cap(ctx, whole ? nbytes : (size_t) covered, (size_t) to[n_ids], n_ids);
+  if (whole) TRY(dupload(&all, payload, nbytes, &d_whole));
+  else                                                    /* (no slice's spans are more than the selection's) */
+    { stage = malloc((size_t) covered + 16);
+      if (stage == NULL) { rc = DX_E_NOMEM; goto done; }
+    }
+
+  for (j0 = 0; j0 < n_ids; j0 = j1)                       /* slices of whole units: at most cap bytes of text each (0: all at once) */
+    { void    *d_in = d_whole, *d_boff, *d_beg, *d_len, *d_ooff, *d_out;
+      uint64_t m, in_bytes = nbytes, bad = UINT64_MAX;
+      j1 = sel_slice_end(to, j0, n_ids, cap);
+      m  = j1 - j0;
+      if (whole)
+        memcpy(rel, at + j0, (size_t) m * 8);
+      else                                                /* this slice's spans, packed */
+        { for (j = 0; j < m; j++) { sp[j] = un[j0 + j]; sp[j].j = j; }
+          in_bytes = spans_pack(sp, m, payload, stage, rel);
+          TRY(dupload(&pool, stage, (size_t) in_bytes, &d_in));
+        }
+      TRY(dupload(&pool, rel, m * 8, &d_boff));
+      TRY(dupload(&pool, ph + j0, m * 4, &d_beg));
+      TRY(dupload(&pool, len + j0, m * 4, &d_len));
+      for (j = 0; j < m; j++) rel[j] = to[j0 + j] - to[j0];   /* the units' places in the slice's text */
+      TRY(dupload(&pool, rel, m * 8, &d_ooff));
+      TRY(dalloc(&pool, (size_t) (to[j1] - to[j0]), &d_out));
+      rc = dx_reads_unpack(ctx, letters, d_in, in_bytes, d_boff, d_beg, d_len, m, d_out, d_ooff, &bad);
+      if (rc == DX_E_FORMAT && bad != UINT64_MAX)         /* the caller's read, not its place in the slice */
+        { const uint64_t id = ids ? ids[j0 + bad] : j0 + bad;
+          rc = dx_entry_fail(ctx, id, boff[id], nbytes);
+        }
+      if (rc != DX_OK) goto done;
+      TRY(dx_d2h(ctx, res + to[j0], d_out, (size_t) (to[j1] - to[j0])));
+      dfree_all(&pool);
+    }
+
+deliver:
+  *text = res; *text_bytes = (size_t) to[n_ids]; *toff = to;
+  res = NULL; to = NULL;
+  rc = DX_OK;
+
+done:
+  dfree_all(&pool);
+  dfree_all(&all);
+  free(sp); free(un); free(rel); free(at); free(len); free(ph); free(stage); free(res); free(to);
   return rc;
 }

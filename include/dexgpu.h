@@ -607,6 +607,47 @@ int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
                           int ascii, uint8_t **text, size_t *text_bytes, uint64_t **toff /* n_ids + 1 */);
 
 /* ------------------------------------------------------------------------------------------
+ *  .bps / .arw read side: Load_Read, Load_Subread, Load_All_Reads, Load_Arrow as a batch
+ * ------------------------------------------------------------------------------------------ */
+/* A .bps / .arw payload is dx_pack2_encode's output with d_hdr = NULL: Compress_Read's bytes (DB.c:319-338) of every read, one
+ * behind the other, found through DAZZ_READ.boff and .rlen.  Load_Read (DB.c:1232-1298) reads COMPRESSED_LEN(rlen) bytes at
+ * boff, Load_Subread (DB.c:1308-1381) bytes [beg / 4, (end - 1) / 4 + 1) of them -- the string it returns begins beg % 4
+ * symbols into what it uncompressed (DB.c:1351-1367) --, Load_Arrow (DB.c:1508-1548) does the same on the .arw track; all
+ * leave a delimiter on both sides of the string, Load_All_Reads (DB.c:1389-1441) one between any two reads.
+ *
+ * dx_reads_unpack (device in, device out; csrc/reads/dx_reads.hip): unit j is symbols [d_beg[j], d_beg[j] + d_len[j]) of the
+ * packed read that starts at d_in + d_boff[j] -- any byte offset, any phase; symbol i of a read is bits 7 - 2 (i & 3),
+ * 6 - 2 (i & 3) of its byte i >> 2; d_beg == NULL: all 0.  It writes d_len[j] bytes at d_out + d_out_off[j] (any alignment)
+ * and ONE delimiter byte behind them, nothing else: 4 for DX_LETTERS_NUMBERS (Uncompress_Read, DB.c:362), '\0' for the
+ * letter sets (Lower_Read & co., DB.c:367-389); d_len[j] == 0 writes the delimiter only.  Units may overlap or repeat in the
+ * input; the outputs are the caller's to keep disjoint.  Nothing outside [0, in_bytes) is read.  DX_E_FORMAT with *bad_unit =
+ * the smallest such j (UINT64_MAX otherwise; may be NULL) when a unit's last packed byte d_boff[j] + ((d_beg[j] + d_len[j] - 1)
+ * >> 2) is not below in_bytes (d_len[j] > 0), when d_boff[j] > in_bytes, or when d_len[j] > 2^31 - 1 (DAZZ_READ.rlen is an int);
+ * nothing is promised about d_out then.  The check is the kernel's own: one read-back of the verdict a call.            */
+int dx_reads_unpack(dx_ctx *ctx, int letters, const uint8_t *d_in, uint64_t in_bytes,
+                    const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len,
+                    uint64_t n, uint8_t *d_out, const uint64_t *d_out_off, uint64_t *bad_unit /* may be NULL */);
+
+/* Load_Read / Load_Subread / Load_Arrow for a selection at once (host in, host out): unit j is read ids[j] (ids == NULL: reads
+ * 0 .. n_ids - 1), which starts at payload + boff[ids[j]] and has rlen[ids[j]] symbols -- all of it when beg == NULL, else its
+ * symbols [beg[j], end[j]) (beg and end are given together; beg[j] <= end[j] <= rlen[ids[j]], else DX_E_ARG).  ids may come in
+ * any order and may repeat.  The layout is Load_All_Reads' (DB.c:1406-1433): (*text)[0] is a delimiter, toff[0] = 1,
+ * toff[j + 1] = toff[j] + len_j + 1, *text_bytes = toff[n_ids]; unit j is (*text)[toff[j] .. toff[j] + len_j), with a
+ * delimiter in front of it and behind it -- Load_Read's "the byte before read will be set to a delimiter".  The one difference
+ * from Load_All_Reads: its first byte is 4 whatever ascii is (DB.c:1406); here it is the letter set's delimiter, as Load_Read
+ * leaves it.  text and toff are malloc'd (dx_file_free).
+ * What travels, as for dx_entries_uncompress: a unit's span of the payload is exact, [boff + beg / 4, boff + (end - 1) / 4 + 1);
+ * the spans are merged, and when they cover less than half of the payload they go up packed side by side, else the payload
+ * goes up once (one the device has no room for goes up packed, slice by slice, whatever is selected).  A selection whose
+ * text exceeds DEXGPU_TEXT_BUDGET bytes, or what is free on the device, is decoded in slices of whole units.  n_ids == 0:
+ * DX_OK, and the text is one delimiter byte.  DX_E_FORMAT: a read does not lie inside [0, nbytes) (dx_last_error names the
+ * caller's read id).                                                                                                    */
+int dx_reads_uncompress(dx_ctx *ctx, int letters, const uint8_t *payload, size_t nbytes,
+                        const uint64_t *boff, const uint32_t *rlen,
+                        const uint64_t *ids, const uint32_t *beg, const uint32_t *end, uint64_t n_ids,
+                        uint8_t **text, size_t *text_bytes, uint64_t **toff /* n_ids + 1 */);
+
+/* ------------------------------------------------------------------------------------------
  *  seeded synthetic corpora on the device (benchmark/test plumbing; mirrors dextractor_amd/synth.py)
  * ------------------------------------------------------------------------------------------ */
 /* Writes entries [entry0, entry0+n) of the .quiva corpus `seed`: for each entry the header line
