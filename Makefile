@@ -12,8 +12,8 @@ EXTRA   ?=
 HIPFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall -Wno-unused-function $(EXTRA)
 CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 
-# verify/, records/, reads/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
-HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads
+# verify/, records/, reads/, digest/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
+HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads digest/dx_crc
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
 C_OBJ    = $(BUILD)/dx_host.o $(BUILD)/dx_walk_host.o $(BUILD)/dx_files.o $(BUILD)/dx_compat.o
 TOOLS    = dexta undexta dexar undexar dexqv undexqv

@@ -70,6 +70,9 @@ class VerifyReport(C.Structure):                 # dx_verify_report
                 ("records_src", C.c_uint64), ("records_img", C.c_uint64), ("record", C.c_uint64), ("line", C.c_uint64),
                 ("column", C.c_uint64), ("src_byte", C.c_uint64), ("img_byte", C.c_uint64)]
 
+class Digest(C.Structure):                       # dx_digest
+    _fields_ = [("crc32", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("records", C.c_uint64)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
@@ -170,6 +173,11 @@ SIGNATURES = {
     "dx_verify_ranges": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint64)]),
     "dx_file_verify": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_int, C.POINTER(VerifyReport)]),
+    "dx_crc32_ranges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "dx_crc32_fold": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dx_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
+    "dx_file_digest": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(Digest), C.POINTER(_P)]),
+    "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),
     "dx_entries_add": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),

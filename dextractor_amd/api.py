@@ -483,6 +483,41 @@ class Context:
             out["error"] = (self.lib.dx_last_error(self.h) or b"").decode()
         return out
 
+    # ---- digest ------------------------------------------------------------------------------------
+    def crc32_ranges(self, d_buf, buf_bytes, d_off, d_len, n, d_crc):
+        """dx_crc32_ranges: d_crc[j] = zlib's CRC-32 of d_buf[d_off[j] .. d_off[j] + d_len[j]) (offsets and lengths: uint64 on the
+        device).  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie inside the buf_bytes."""
+        bad = C.c_uint64()
+        rc = self.lib.dx_crc32_ranges(self.h, d_buf.ptr if d_buf else None, int(buf_bytes), d_off.ptr if d_off else None,
+                                      d_len.ptr if d_len else None, int(n), d_crc.ptr if d_crc else None, C.byref(bad))
+        if rc != 0:
+            e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
+            e.bad_unit = bad.value if bad.value != 2**64 - 1 else None
+            raise e
+
+    def crc32_fold(self, d_crc, d_len, n):
+        """dx_crc32_fold: (CRC-32, length) of the units' concatenation in index order, from their CRCs (uint32) and lengths (uint64)"""
+        crc, nbytes = C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.dx_crc32_fold(self.h, d_crc.ptr if d_crc else None, d_len.ptr if d_len else None, int(n),
+                                         C.byref(crc), C.byref(nbytes)))
+        return crc.value, nbytes.value
+
+    def digest(self, kind, img: bytes, upper=False, width=80, per_record=False) -> dict:
+        """dx_file_digest: the CRC-32 (zlib's) and size of the text undexta / undexar / undexqv writes for img with these options,
+        decoded and hashed on the device.  kind: "fasta", "arrow" or "quiva".  {"crc32", "bytes", "records"}, and with per_record
+        "rec_crc": every record's own CRC-32 (its header line included) as a uint32 array."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        dg, rec = L.Digest(), C.c_void_p()
+        self._chk(self.lib.dx_file_digest(self.h, k, img, len(img), int(bool(upper)), int(width), C.byref(dg),
+                                          C.byref(rec) if per_record else None))
+        out = {"crc32": dg.crc32, "bytes": dg.bytes, "records": dg.records}
+        if per_record:
+            try:
+                out["rec_crc"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), (dg.records + 1,))[:dg.records].copy()
+            finally:
+                self.lib.dx_file_free(rec)
+        return out
+
     def qv_subindex(self, on=True):
         self._chk(self.lib.dx_qv_subindex(self.h, int(bool(on))))
 
@@ -630,6 +665,21 @@ def pack2_sharded(contexts, text: bytes, arrow=False) -> bytes:
 
 
 # ---- host-only helpers (no GPU needed) ---------------------------------------------------------
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """dx_crc32_combine (host): zlib's crc32_combine -- crc32(A + B) from crc32(A), crc32(B) and len(B)"""
+    return L.load().dx_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b))
+
+
+def text_options(kind, text: bytes):
+    """dx_file_text_options (host): (upper, width) that give `text` back, as dx_file_verify reads them off it"""
+    k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+    upper, width = C.c_int(), C.c_uint32()
+    rc = L.load().dx_file_text_options(k, text, len(text), C.byref(upper), C.byref(width))
+    if rc != 0:
+        raise L.DexGPUError(rc, "the text does not index")
+    return bool(upper.value), width.value
+
 
 def qv_build(hist, tot, params, lossy=False) -> L.QVCoding:
     """Create_QVcoding (QV.c:1029-1169) on the host."""

@@ -61,6 +61,7 @@ static const tool_t TOOLS[6] =
         "      -U: use uppercase letters (default is lower case).\n", NULL, NULL } } };
 
 static const char *Prog;
+static int         Digest = 0;   /* DEXGPU_DIGEST: 1: a line on stdout for every file done; 2 ("only"): the line, and no output file */
 
 /* ---- whole-file I/O ---------------------------------------------------------------------- */
 
@@ -651,6 +652,35 @@ static int verified_on_disk(dx_ctx *ctx, int tool, const char *src, const char *
   return ok;
 }
 
+/* DEXGPU_DIGEST: the CRC-32 (zlib's) and the size of the text behind a file's image -- of what the undex* tool makes of it with its -U
+   and -w, never assembled: dx_file_digest decodes and hashes on the GPU.  undexta, undexar, undexqv: the image is the input in memory;
+   dexta, dexar, dexqv: the image just written, as it is on disk, with the options read off the source as DEXGPU_VERIFY reads them
+   (dx_file_text_options) -- what undex* gives back, which DEXGPU_VERIFY=1 says is the source. */
+static int is_undex(int tool) { return tool == TOOL_UNDEXTA || tool == TOOL_UNDEXAR || tool == TOOL_UNDEXQV; }
+
+static int digest_of(const options *o, job *f, dx_digest *dg)
+{ const int kind = o->tool == TOOL_DEXTA || o->tool == TOOL_UNDEXTA ? DX_KIND_FASTA
+                 : (o->tool == TOOL_DEXAR || o->tool == TOOL_UNDEXAR ? DX_KIND_ARROW : DX_KIND_QUIVA);
+  int      upper = o->upper, rc = DX_OK;
+  uint32_t width = (uint32_t) o->width;
+  if (f->ctx == NULL) f->ctx = context();
+  if (is_undex(o->tool))
+    return f->in == NULL ? DX_E_NOMEM : dx_file_digest(f->ctx, kind, f->in, f->n, upper, width, dg, NULL);
+  { FILE    *fs = fopen(f->src, "r"), *fd = fopen(f->dst, "r");
+    uint8_t *text = NULL, *img = NULL;
+    size_t   n = 0, m = 0;
+    int      tmapped = 0, imapped = 0;
+    if (fs == NULL || fd == NULL || (text = slurp(fs, &n, &tmapped)) == NULL || (img = slurp(fd, &m, &imapped)) == NULL) rc = DX_E_IO;
+    if (rc == DX_OK) rc = dx_file_text_options(kind, text, n, &upper, &width);
+    if (text != NULL) unslurp(text, n, tmapped);
+    if (rc == DX_OK) rc = dx_file_digest(f->ctx, kind, img, m, upper, width ? width : 1, dg, NULL);
+    if (img != NULL) unslurp(img, m, imapped);
+    if (fs != NULL) fclose(fs);
+    if (fd != NULL) fclose(fd);
+  }
+  return rc;
+}
+
 /* the files behind a name (dexta.c:87-94), or the standard streams */
 static void begin(const options *o, const char *name, job *f)
 { const tool_t *t = &TOOLS[o->tool];
@@ -669,12 +699,12 @@ static void begin(const options *o, const char *name, job *f)
         { fprintf(stderr, "%s: Cannot open %s for 'r'\n", Prog, f->src);   /* Fopen, DB.c:103-110 */
           leave(1);
         }
-      if ((f->output = fopen(f->dst, "w+")) == NULL)         /* (readable too: a large output is written through a shared mapping, which wants that) */
+      if (Digest != 2 && (f->output = fopen(f->dst, "w+")) == NULL)     /* (readable too: a large output is written through a shared mapping, which wants that) */
         { fprintf(stderr, "%s: Cannot open %s for 'w'\n", Prog, f->dst);
           leave(1);
         }
     }
-  f->out_fd = fileno(f->output);
+  f->out_fd = f->output != NULL ? fileno(f->output) : -1;       /* (DEXGPU_DIGEST=only: there is no output) */
   if (o->verbose)
     { fprintf(stderr, "Processing '%s' ...\n", f->root);
       fflush(stderr);
@@ -683,16 +713,34 @@ static void begin(const options *o, const char *name, job *f)
 
 /* The one end of a file's run, whichever route it took and whatever that answered. */
 static void end(const options *o, job *f, int rc)
-{ if (rc == DX_OK && f->seek && lseek(f->out_fd, (off_t) f->out_len, SEEK_SET) < 0) rc = DX_E_IO;
+{ dx_digest dg;
+  memset(&dg, 0, sizeof(dg));
+  if (rc == DX_OK && f->seek && lseek(f->out_fd, (off_t) f->out_len, SEEK_SET) < 0) rc = DX_E_IO;
+  if (rc == DX_OK && Digest && is_undex(o->tool))          /* (the image is the input, while it is still in memory) */
+    { rc = digest_of(o, f, &dg);
+      tmark("digested");
+    }
   if (rc == DX_OK)
     { if (f->in != NULL) unslurp(f->in, f->n, f->mapped);
       tmark("output written");
       if (!o->pipe) fclose(f->input);
-      if (o->pipe ? fflush(f->output) != 0 : fclose(f->output) != 0)   /* a deferred write error (ENOSPC, quota, NFS) surfaces here: */
-        rc = DX_E_IO;                                                  /* the source must survive it */
+      if (f->output != NULL && (o->pipe ? fflush(f->output) != 0 : fclose(f->output) != 0))   /* a deferred write error (ENOSPC, quota, NFS) */
+        rc = DX_E_IO;                                                                         /* surfaces here: the source must survive it */
     }
   if (rc != DX_OK)
     leave(report_failure(o->tool, f, rc));
+  if (Digest && !is_undex(o->tool))                        /* (the image is the file just closed) */
+    { if ((rc = digest_of(o, f, &dg)) != DX_OK)
+        { fprintf(stderr, "%s: %s could not be digested (%s); %s is kept\n", Prog, f->dst,
+                  rc == DX_E_IO ? "cannot be read" : dx_last_error(f->ctx), f->src);
+          leave(1);
+        }
+      tmark("digested");
+    }
+  if (Digest)
+    { printf("%08x %llu %s\n", dg.crc32, (unsigned long long) dg.bytes, is_undex(o->tool) ? f->dst : f->src);
+      fflush(stdout);
+    }
   if (!o->pipe)
     { const char *verify = getenv("DEXGPU_VERIFY");
       if ((o->tool == TOOL_DEXTA || o->tool == TOOL_DEXAR || o->tool == TOOL_DEXQV) && verify != NULL && atoi(verify) != 0)
@@ -700,7 +748,7 @@ static void end(const options *o, job *f, int rc)
             leave(3);                                    /* (the reference's tools leave with 1 and 2; the files that follow are not touched) */
           tmark("verified");
         }
-      if (!o->keep) unlink(f->src);
+      if (!o->keep && Digest != 2) unlink(f->src);           /* (DEXGPU_DIGEST=only made nothing that could stand in for it) */
     }
   free(f->root); free(f->pwd); free(f->src); free(f->dst);
   if (o->verbose)
@@ -778,6 +826,15 @@ int dex_tool_main(int tool, int argc, char *argv[])
   Prog = TOOLS[tool].name;
   argc = parse_arguments(tool, argc, argv, &o);
 
+  { const char *d = getenv("DEXGPU_DIGEST");              /* (with -i stdout carries the data: no line there) */
+    Digest = d == NULL || *d == '\0' || o.pipe ? 0 : (strcmp(d, "only") == 0 ? 2 : atoi(d) != 0);
+    if (Digest == 2 && !is_undex(tool))
+      { fprintf(stderr, "%s: DEXGPU_DIGEST=only digests an image and writes nothing: that is for un%s; %s is there to write one\n",
+                Prog, Prog, Prog);
+        exit(1);
+      }
+  }
+
   tmark("start");
 #ifdef F_SETPIPE_SZ
   if (o.pipe) (void) fcntl(0, F_SETPIPE_SZ, 1 << 20);      /* (a pipe's 64 KB are 2 GB/s at best; no harm where stdin is none or the size is refused) */
@@ -789,6 +846,7 @@ int dex_tool_main(int tool, int argc, char *argv[])
       int    rc = NOT_MINE;
       size_t r;
       begin(&o, argv[i], &f);
+      if (Digest == 2) rc = read_input(&o, &f) == NOT_MINE ? DX_OK : DX_E_IO;     /* (no route: nothing is converted) */
       for (r = 0; r < sizeof(ROUTES) / sizeof(ROUTES[0]) && (rc == NOT_MINE || rc == DX_E_AGAIN); r++)
         { f.seek = 0;                                      /* (what a route that passed the file on has set) */
           rc = ROUTES[r](&o, &f);

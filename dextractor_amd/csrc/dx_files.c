@@ -1741,13 +1741,62 @@ static void verify_place(const verify_job *v, uint64_t r, int body, uint64_t pos
   rep->record = r; rep->line = line; rep->column = col; rep->src_byte = at + pos;
 }
 
+/* The options that give an indexed text back (dexgpu.h: dx_file_verify, dx_file_text_options): the case of its letters, its line width
+   (quiva: 0).  sx: the index of a .fasta / .arrow, qx: of a .quiva. */
+static void text_options(int kind, const uint8_t *text, const seq_index *sx, const quiva_index *qx, int32_t *upper, uint32_t *width)
+{ uint64_t i;
+  *upper = 0; *width = 0;
+  if (kind == DX_KIND_QUIVA)
+    { for (i = 0; i < qx->cnt; i++)                       /* undexqv -U: the deletion tags' case (undexqv.c:198-204) */
+        if (qx->len[i] > 0)
+          { const uint8_t c = text[qx->off[i] + qx->len[i] + 1];
+            *upper = c >= 'A' && c <= 'Z';
+            break;
+          }
+    }
+  else
+    { uint32_t longest = 0;
+      for (i = 0; i < sx->cnt && kind == DX_KIND_FASTA; i++)
+        if (sx->nsym[i] > 0)
+          { const uint8_t *q = text + sx->off[i];
+            while (*q == '\n') q++;
+            *upper = *q >= 'A' && *q <= 'Z';
+            break;
+          }
+      for (i = 0; i < sx->cnt && *width == 0; i++)         /* -w: the first line that another line of its record follows */
+        { const uint8_t *q = text + sx->off[i], *e = sx->tlen[i] ? memchr(q, '\n', sx->tlen[i]) : NULL;
+          if (e != NULL && (size_t) (e - q) + 1 < sx->tlen[i] && e > q) *width = (uint32_t) (e - q);
+          if (sx->nsym[i] > longest) longest = sx->nsym[i];
+        }
+      if (*width == 0) *width = longest ? longest : 1;
+    }
+}
+
+int dx_file_text_options(int kind, const uint8_t *text, size_t n, int *upper, uint32_t *width)
+{ seq_index   sx;
+  quiva_index qx = { 0, NULL, NULL, NULL, 0 };
+  uint64_t    el = 0;
+  int32_t     up = 0;
+  int         rc, ec = 0;
+  if (upper == NULL || width == NULL || (text == NULL && n)) return DX_E_ARG;
+  if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW && kind != DX_KIND_QUIVA) return DX_E_ARG;
+  memset(&sx, 0, sizeof(sx));
+  rc = kind == DX_KIND_QUIVA ? quiva_index_host(&qx, text, n, &el, &ec) : seq_index_host(&sx, kind == DX_KIND_ARROW, text, n, &el, &ec);
+  if (rc == DX_OK)
+    { text_options(kind, text, &sx, &qx, &up, width);
+      *upper = up;
+    }
+  seq_index_free(&sx); quiva_index_free(&qx);
+  return rc;
+}
+
 int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const uint8_t *img, size_t m, int lossy, dx_verify_report *rep)
 { seq_index        sx;
   quiva_index      qx = { 0, NULL, NULL, NULL, 0 };
   u2_index         ux;
   dx_undexqv_plan *plan = NULL;
   verify_job       v;
-  uint64_t        *ooff = NULL, el = 0, both, i, hfirst;
+  uint64_t        *ooff = NULL, el = 0, both, hfirst;
   const uint64_t  *hat = NULL;
   const char      *hd = NULL;
   size_t           total = 0, cap;
@@ -1763,31 +1812,12 @@ int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const u
   if (kind == DX_KIND_QUIVA)
     { TRY(quiva_index_host(&qx, text, n, &el, &ec));
       v.cnt = qx.cnt; v.off = qx.off; v.blen = qx.len;
-      for (i = 0; i < qx.cnt; i++)                        /* undexqv -U: the deletion tags' case (undexqv.c:198-204) */
-        if (qx.len[i] > 0)
-          { const uint8_t c = text[qx.off[i] + qx.len[i] + 1];
-            rep->upper = c >= 'A' && c <= 'Z';
-            break;
-          }
     }
   else
-    { uint32_t longest = 0;
-      TRY(seq_index_host(&sx, kind == DX_KIND_ARROW, text, n, &el, &ec));
+    { TRY(seq_index_host(&sx, kind == DX_KIND_ARROW, text, n, &el, &ec));
       v.cnt = sx.cnt; v.off = sx.off; v.blen = sx.tlen;
-      for (i = 0; i < sx.cnt && kind == DX_KIND_FASTA; i++)
-        if (sx.nsym[i] > 0)
-          { const uint8_t *q = text + sx.off[i];
-            while (*q == '\n') q++;
-            rep->upper = *q >= 'A' && *q <= 'Z';
-            break;
-          }
-      for (i = 0; i < sx.cnt && rep->width == 0; i++)      /* -w: the first line that another line of its record follows */
-        { const uint8_t *q = text + sx.off[i], *e = sx.tlen[i] ? memchr(q, '\n', sx.tlen[i]) : NULL;
-          if (e != NULL && (size_t) (e - q) + 1 < sx.tlen[i] && e > q) rep->width = (uint32_t) (e - q);
-          if (sx.nsym[i] > longest) longest = sx.nsym[i];
-        }
-      if (rep->width == 0) rep->width = longest ? longest : 1;
     }
+  text_options(kind, text, &sx, &qx, &rep->upper, &rep->width);
   rep->records_src = v.cnt;
 
   /* the image: its records, the header lines the decoder prints, the text's layout */
@@ -1875,6 +1905,122 @@ done:
   dx_file_undexqv_plan_free(plan);
   seq_index_free(&sx); quiva_index_free(&qx); u2_index_free(&ux);
   free(ooff);
+  return rc;
+}
+
+/* ==========================================================================================
+ *  digest (dx_file_digest): the CRC-32 of the text an image decodes to, for the day the text is gone.  The image is walked and
+ *  decoded as the drivers above do it, slice by slice; a slice of decoded bodies stays where it is made and is hashed there
+ *  (dx_crc32_ranges), and so are the header lines, which the host prints and uploads once.  Per slice the device joins a record's
+ *  two (crc, length) pairs and folds the records' (dx_crc32_fold); the host joins the slices.  Nothing of the text comes back.
+ * ========================================================================================== */
+typedef struct
+  { dx_ctx          *ctx;
+    const hdr_patch *h;                            /* the decoded text's layout */
+    void            *d_hd;    size_t hd_bytes;     /* device: the header lines, one after the other */
+    void            *d_arr;   size_t arr_cap;      /* ... a slice's unit arrays */
+    uint32_t         crc;     uint64_t bytes;      /* of the slices so far */
+    uint32_t        *rec;                          /* every record's CRC, when wanted */
+  } digest_job;
+
+/* a slice of decoded text, records [i0, i1): per record two units, its header line (in d_hd) and its body (in d_out) */
+static int digest_slice(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes)
+{ digest_job *g = arg;
+  const hdr_patch *h = g->h;
+  const uint64_t m = i1 - i0;
+  uint64_t *off, *len, k, sbytes = 0;
+  uint32_t  scrc = 0;
+  int       rc;
+  if (m * 52 + 64 > g->arr_cap)
+    { if (g->d_arr) (void) dx_free(g->ctx, g->d_arr);
+      g->d_arr = NULL; g->arr_cap = 0;
+      if ((rc = dx_malloc(g->ctx, (size_t) m * 52 + 64, &g->d_arr)) != DX_OK) return rc;
+      g->arr_cap = (size_t) m * 52 + 64;
+    }
+  off = malloc((size_t) m * 32 + 64);                      /* off, len: 2 m each, a record's header line, then its body */
+  if (off == NULL) return DX_E_NOMEM;
+  len = off + 2 * m;
+  for (k = 0; k < m; k++)
+    { const uint64_t i = i0 + k;
+      off[2*k]     = h->hat[i];
+      len[2*k]     = h->hat[i + 1] - h->hat[i];
+      off[2*k + 1] = h->ooff[i] - t0;
+      len[2*k + 1] = text_at(h, i + 1) - h->ooff[i];
+    }
+  rc = dx_h2d(g->ctx, g->d_arr, off, (size_t) m * 32);
+  free(off);
+  if (rc != DX_OK) return rc;
+  { uint64_t *d_off = g->d_arr, *d_len = d_off + 2 * m, *d_rlen = d_len + 2 * m;
+    uint32_t *d_crc = (uint32_t *) (d_rlen + m), *d_rcrc = d_crc + 2 * m;
+    if ((rc = dx_crc32_ranges_strided(g->ctx, g->d_hd, g->hd_bytes, d_off, d_len, m, 2, d_crc, NULL)) != DX_OK) return rc;
+    if ((rc = dx_crc32_ranges_strided(g->ctx, d_out, bytes, d_off + 1, d_len + 1, m, 2, d_crc + 1, NULL)) != DX_OK) return rc;
+    if ((rc = dx_crc32_pairs(g->ctx, d_crc, d_len, m, d_rcrc, d_rlen)) != DX_OK) return rc;
+    if ((rc = dx_crc32_fold(g->ctx, d_rcrc, d_rlen, m, &scrc, &sbytes)) != DX_OK) return rc;
+    if (g->rec != NULL && (rc = dx_d2h(g->ctx, g->rec + i0, d_rcrc, (size_t) m * 4)) != DX_OK) return rc;
+  }
+  g->crc    = dx_crc32_combine(g->crc, scrc, sbytes);
+  g->bytes += sbytes;
+  return DX_OK;
+}
+
+int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int upper, uint32_t width, dx_digest *out, uint32_t **rec_crc)
+{ u2_index         ux;
+  dx_undexqv_plan *plan = NULL;
+  digest_job       g;
+  hdr_patch        h;
+  uint64_t        *ooff = NULL, cnt = 0;
+  size_t           total = 0;
+  int              rc;
+
+  if (ctx == NULL || img == NULL || out == NULL) return DX_E_ARG;
+  if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW && kind != DX_KIND_QUIVA) return DX_E_ARG;
+  if (kind != DX_KIND_QUIVA && width == 0) return DX_E_ARG;
+  if (rec_crc) *rec_crc = NULL;
+  memset(&ux, 0, sizeof(ux)); memset(&g, 0, sizeof(g)); memset(&h, 0, sizeof(h));
+  g.ctx = ctx; g.h = &h;
+
+  /* the image: its records, the header lines the decoder prints, the text's layout */
+  if (kind == DX_KIND_QUIVA)
+    { TRY(dx_file_undexqv_plan_on(ctx, img, m, &plan, &total));
+      cnt = plan->x.n;
+      h.n = cnt; h.ooff = plan->ooff; h.hat = plan->hat; h.hd = plan->hd.p; h.total = total;
+      g.hd_bytes = plan->hd.len;
+    }
+  else
+    { TRY(u2_walk(kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : DX_LETTERS_LOWER, img, m, NULL, &ux));
+      cnt = ux.cnt;
+      if ((ooff = malloc((cnt + 1) * sizeof(*ooff))) == NULL) { rc = DX_E_NOMEM; goto done; }
+      total = u2_layout(&ux, width, ooff);
+      h.n = cnt; h.ooff = ooff; h.hat = ux.hat; h.hd = ux.hd.p; h.total = total;
+      g.hd_bytes = ux.hd.len;
+    }
+  if (rec_crc != NULL && (g.rec = malloc((cnt + 1) * sizeof(*g.rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
+
+  if (cnt > 0)
+    { TRY(dx_malloc(ctx, g.hd_bytes + 64, &g.d_hd));
+      TRY(dx_h2d(ctx, g.d_hd, h.hd, g.hd_bytes));
+      if (kind == DX_KIND_QUIVA)
+        { int whole_in;
+          const size_t cap = undexqv_cap(ctx, plan, &whole_in);
+          TRY(undexqv_sliced(ctx, plan, upper, digest_slice, &g, cap ? cap : total + 1, whole_in));
+        }
+      else
+        { const int    mode = kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : (upper ? DX_LETTERS_UPPER : DX_LETTERS_LOWER);
+          const size_t cap  = out_cap(ctx, m, total, cnt);
+          TRY(unpack2_slices(ctx, mode, img, m, width, &ux, &h, cap ? cap : total + 1, digest_slice, &g));
+        }
+      if (g.bytes != total) { rc = DX_E_MISMATCH; goto done; }     /* (the slices are the whole text) */
+    }
+  out->crc32 = g.crc; out->reserved = 0; out->bytes = g.bytes; out->records = cnt;
+  if (rec_crc) { *rec_crc = g.rec; g.rec = NULL; }
+  rc = DX_OK;
+
+done:
+  if (g.d_hd) (void) dx_free(ctx, g.d_hd);
+  if (g.d_arr) (void) dx_free(ctx, g.d_arr);
+  dx_file_undexqv_plan_free(plan);
+  u2_index_free(&ux);
+  free(ooff); free(g.rec);
   return rc;
 }
 

@@ -25,4 +25,12 @@ int dx_qv_read_head(const uint8_t *img, size_t n, dx_qv_index *x, size_t *first)
    written by the device files' dx_fail); dx_entries_uncompress names the caller's entry with it, not its place in a slice. */
 int dx_entry_fail(dx_ctx *ctx, uint64_t id, uint64_t at, uint64_t nbytes);
 
+/* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
+   arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their
+   (crc, length) pairs are wanted side by side in record order.  dx_crc32_pairs: units 2 k and 2 k + 1 joined into unit k of the
+   output arrays (a record's header line and its body -> the record), m of them, on the device; nothing comes back. */
+int dx_crc32_ranges_strided(dx_ctx *ctx, const uint8_t *d_buf, uint64_t buf_bytes, const uint64_t *d_off, const uint64_t *d_len,
+                            uint64_t n, uint64_t stride, uint32_t *d_crc, uint64_t *bad_unit);
+int dx_crc32_pairs(dx_ctx *ctx, const uint32_t *d_crc, const uint64_t *d_len, uint64_t m, uint32_t *d_out_crc, uint64_t *d_out_len);
+
 #endif

@@ -555,6 +555,39 @@ int  dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const 
                     dx_verify_report *rep);
 
 /* ------------------------------------------------------------------------------------------
+ *  digest: the CRC-32 of what an image decodes to, once the text is gone  (none of the three formats carries a checksum)
+ * ------------------------------------------------------------------------------------------ */
+/* CRC-32 (zlib: polynomial 0xEDB88320 reflected, initial value and final xor 0xFFFFFFFF) of n byte ranges of a device buffer:
+ * d_crc[j] = crc32(d_buf[d_off[j] .. d_off[j] + d_len[j])), any offset, any length from 0 (crc 0) up, ranges may overlap or repeat.
+ * Nothing outside [0, buf_bytes) is read; DX_E_FORMAT with *bad_unit = the smallest j whose range does not lie inside it
+ * (UINT64_MAX otherwise; may be NULL), checked by the kernel, one read-back a call (the convention of dx_reads_unpack).
+ * n < 2^31.  Short units go a lane each, long ones a wave each, those of 1 MiB and more over many waves (csrc/digest/dx_crc.hip). */
+int dx_crc32_ranges(dx_ctx *ctx, const uint8_t *d_buf, uint64_t buf_bytes, const uint64_t *d_off, const uint64_t *d_len,
+                    uint64_t n, uint32_t *d_crc, uint64_t *bad_unit);
+
+/* The CRC-32 of the units' concatenation in index order, from their CRCs and lengths alone (device arrays), and its length:
+ * n == 0 gives 0 and 0.  One read-back.                                                                                    */
+int dx_crc32_fold(dx_ctx *ctx, const uint32_t *d_crc, const uint64_t *d_len, uint64_t n, uint32_t *crc, uint64_t *bytes);
+
+/* host: zlib's crc32_combine -- crc(A || B) from crc(A), crc(B) and B's length */
+uint32_t dx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+typedef struct { uint32_t crc32, reserved; uint64_t bytes, records; } dx_digest;
+/* The CRC-32 and the size of the text undexta [-U] [-w<width>] / undexar [-w<width>] / undexqv [-U] writes for img (kind
+ * DX_KIND_FASTA / _ARROW / _QUIVA; arrow ignores upper, quiva ignores width): header lines included, byte for byte the output of
+ * dx_file_unpack2 / dx_file_undexqv -- which is never assembled or downloaded.  rec_crc != NULL: also *rec_crc[i] = the CRC-32
+ * of record i's text, its header line included (malloc'd, dx_file_free), to find WHICH records of two files differ.
+ * Errors are those of dx_file_unpack2 / dx_file_undexqv for the same image; *out is then untouched.
+ * The image is walked and decoded by the drivers' own code, slice by slice when the text does not fit the device (or
+ * DEXGPU_TEXT_BUDGET); the header lines, printed on the host, are hashed on the device like the bodies.               */
+int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int upper, uint32_t width,
+                   dx_digest *out, uint32_t **rec_crc);
+
+/* The options that give a text back, read off it as dx_file_verify reads them (see there): *upper, *width (quiva: 0).  A text that
+ * does not index is the error it is for dx_file_pack2 / dx_file_dexqv.  Host only.                                      */
+int dx_file_text_options(int kind, const uint8_t *text, size_t n, int *upper, uint32_t *width);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
