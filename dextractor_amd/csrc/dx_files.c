@@ -53,6 +53,18 @@ static int dupload(dpool *pool, const void *src, size_t bytes, void **out)
   return rc;
 }
 
+/* a device array of the caller's (*p, *cap bytes of it; none yet: NULL, 0) that is to hold `need` bytes: made anew when it is too small,
+   and what it held is gone then */
+static int dgrow(dx_ctx *ctx, void **p, size_t *cap, size_t need)
+{ int rc;
+  if (need <= *cap) return DX_OK;
+  if (*p) (void) dx_free(ctx, *p);
+  *p = NULL; *cap = 0;
+  if ((rc = dx_malloc(ctx, need, p)) != DX_OK) { *p = NULL; return rc; }
+  *cap = need;
+  return DX_OK;
+}
+
 /* The encoder of the file drivers is dx_qv_encode_onepass (no size pass; the same bytes).  DEXGPU_TEST=twopass
  * selects dx_qv_sizes + dx_qv_encode instead (the two-pass API, kept as a cross-check). */
 static int two_pass(void)
@@ -549,6 +561,9 @@ done:
 /* ==========================================================================================
  *  undexta / undexar
  * ========================================================================================== */
+/* One path: the image is walked on the host (u2_walk), the text laid out (u2_layout), and unpack2_slices decodes it slice by slice
+   of whole reads -- the whole text is the case of one slice.  What becomes of a slice is its hook's business (slice_fn): out to the
+   caller (slice_deliver), compared (verify_slice), hashed (digest_slice). */
 typedef struct { const uint8_t *p; size_t n, at; int bad; } rsrc;
 
 static void rd(rsrc *r, void *dst, size_t k)
@@ -602,9 +617,10 @@ static int patch_and_pass(void *arg, uint8_t *data, size_t len, size_t at0)
 static size_t text_at(const hdr_patch *h, uint64_t i)
 { return i < h->n ? (size_t) h->ooff[i] - (size_t) (h->hat[i + 1] - h->hat[i]) : h->total; }
 
-/* a slice of whole entries from i0 on: as many as make at most `cap` bytes of text, and one at least */
+/* a slice of whole entries from i0 on: as many as make at most `cap` bytes of text, and one at least; cap 0: all that are left */
 static uint64_t text_slice_end(const hdr_patch *h, uint64_t i0, size_t cap)
 { uint64_t i1 = i0 + 1;
+  if (cap == 0) return h->n;
   while (i1 < h->n && text_at(h, i1 + 1) - text_at(h, i0) <= cap) i1++;
   return i1;
 }
@@ -781,8 +797,9 @@ static size_t u2_layout(const u2_index *x, uint32_t width, uint64_t *ooff)
   return total;
 }
 
-/* A walked image's text made in slices of whole reads, at most `cap` bytes of text each, the image resident (a quarter of the text);
-   every slice goes to `deliver` before the next one is made (the reference writes read after read, undexta.c:175-271). */
+/* A walked image's text made in slices of whole reads, at most `cap` bytes of text each (0: the whole text, one slice), the image resident
+   (a quarter of the text); every slice goes to `deliver` before the next one is made (the reference writes read after read,
+   undexta.c:175-271).  The only decode of a .dexta / .dexar image in this file. */
 static int unpack2_slices(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width, const u2_index *x, const hdr_patch *h,
                           size_t cap, slice_fn deliver, void *arg)
 { dpool     pool = { {0}, 0, ctx };
@@ -821,13 +838,11 @@ static int unpack2_slices(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, u
 /* out != NULL: the text in memory, else through the sink */
 static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width,
                         uint8_t **out, dx_sink_fn sink, void *user, size_t *out_len, u2_state *st)
-{ dpool     pool = { {0}, 0, ctx };
-  u2_index  x;
-  uint64_t  cnt, i, *ooff = NULL;
+{ u2_index  x;
+  uint64_t  cnt, *ooff = NULL;
   int       rc;
   uint8_t  *res = NULL;
   size_t    total = 0;
-  void     *d_in, *d_ioff, *d_nsym, *d_out, *d_ooff;
 
   if (ctx == NULL || (out == NULL && sink == NULL) || out_len == NULL || img == NULL) return DX_E_ARG;
   if (width == 0) return DX_E_ARG;
@@ -846,32 +861,12 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
       if (!res) { rc = DX_E_NOMEM; goto done; }
     }
 
-  { /* A text that does not fit the device beside the image (or DEXGPU_TEXT_BUDGET): slices of whole reads, every slice's text
-       out before the next one's is made. */
-    const size_t cap = out_cap(ctx, n, total, cnt);
-    if (cnt > 0 && cap)
-      { hdr_patch h = { cnt, ooff, x.hat, x.hd.p, sink, user, 0, total };
-        slice_out so = { ctx, &h, res };
-        TRY(unpack2_slices(ctx, mode, img, n, width, &x, &h, cap, slice_deliver, &so));
-        cnt = 0;                                          /* (done: nothing left for the one-shot path below) */
-      }
-  }
-  if (cnt > 0)
-    { TRY(dupload(&pool, img, n, &d_in));
-      TRY(dupload(&pool, x.ioff, cnt * 8, &d_ioff));
-      TRY(dupload(&pool, x.nsym, cnt * 4, &d_nsym));
-      TRY(dupload(&pool, ooff, cnt * 8, &d_ooff));
-      TRY(dalloc(&pool, total, &d_out));
-      TRY(dx_pack2_decode(ctx, mode, d_in, d_ioff, d_nsym, cnt, width, d_out, d_ooff));
-      if (out)
-        { TRY(dx_d2h(ctx, res, d_out, total));
-          for (i = 0; i < cnt; i++)
-            memcpy(res + ooff[i] - (x.hat[i+1] - x.hat[i]), x.hd.p + x.hat[i], (size_t) (x.hat[i+1] - x.hat[i]));
-        }
-      else
-        { hdr_patch h = { cnt, ooff, x.hat, x.hd.p, sink, user, 0, total };
-          TRY(dx_d2h_stream(ctx, d_out, total, patch_and_pass, &h));
-        }
+  if (cnt > 0)                                            /* (an image without records: nothing for the device) */
+    { /* All of the text at once, or, when it does not fit the device beside the image (or DEXGPU_TEXT_BUDGET says so), in slices
+         of whole reads, every slice's text out before the next one's is made. */
+      hdr_patch h = { cnt, ooff, x.hat, x.hd.p, sink, user, 0, total };
+      slice_out so = { ctx, &h, res };
+      TRY(unpack2_slices(ctx, mode, img, n, width, &x, &h, out_cap(ctx, n, total, cnt), slice_deliver, &so));
     }
   if (out) { *out = res; res = NULL; }
   *out_len = total;
@@ -879,7 +874,6 @@ static int unpack2_core(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uin
   rc = DX_OK;
 
 done:
-  dfree_all(&pool);
   u2_index_free(&x);
   free(ooff); free(res);
   return rc;
@@ -1297,7 +1291,9 @@ int dx_file_dexqv_to(dx_ctx *ctx, const uint8_t *text, size_t n, int lossy, dx_s
 /* ==========================================================================================
  *  undexqv
  * ========================================================================================== */
-/* undexqv in two steps (dexgpu.h): the plan is host work only, the run is the GPU's */
+/* undexqv in two steps (dexgpu.h): the plan is host work only, the run is the GPU's.  The run has one path, undexqv_sliced: slices of
+   whole entries, and the whole text is the case of one slice.  dx_file_undexqv_run, dx_file_verify and dx_file_digest all decode
+   through it, so a check of an image takes the decoder kernels the tool's own run takes. */
 struct dx_undexqv_plan
   { const uint8_t *img;
     size_t         n, total;
@@ -1494,11 +1490,14 @@ done:
 static int decode_flags(const dx_undexqv_plan *p, int upper)
 { return (upper ? DX_DECODE_UPPER : 0) | (p->x.flip ? DX_DECODE_FLIP : 0); }
 
-/* ---- a text larger than the device (or than DEXGPU_TEXT_BUDGET): slices of whole entries ------------------------------
- * The reference writes entry after entry (undexqv.c:182-207).  Here: per slice of at most `cap` bytes of text, the slice's
- * records -- the whole image stays on the device when it is there already (a plan made there) or fits beside a slice's text,
- * else the slice's bytes are uploaded -- are decoded into one buffer that goes to `deliver` before the next slice comes in.
- * Same text; such a file is bound by the host link.                                                               */
+/* ---- the decode of a plan's records: slices of whole entries ------------------------------------------------------------
+ * The reference writes entry after entry (undexqv.c:182-207).  Here: per slice of at most `cap` bytes of text (0: the whole
+ * text, one slice; else a text larger than the device, or than DEXGPU_TEXT_BUDGET), the slice's records -- the whole image
+ * stays on the device when it is there already (a plan made there) or fits beside a slice's text, else the slice's bytes are
+ * uploaded -- are decoded into one buffer that goes to `deliver` before the next slice comes in.  Same text; a file in several
+ * slices is bound by the host link.
+ * The host walk's group index (DEXGPU_TEST=walk_index: a wavefront per line, dx_qv_use_index) is for the whole image in one
+ * slice; with several slices it stays out.                                                                          */
 static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_fn deliver, void *arg, size_t cap, int whole_in_)
 { const int whole_in = whole_in_ || PLAN_HAS_IMAGE(p);    /* (an image that is there is there whole) */
   dpool     pool = { {0}, 0, ctx };
@@ -1520,6 +1519,13 @@ static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slic
   TRY(undexqv_stage(ctx, p, &pool, imax, most, &s, &indexed));
   TRY(dalloc(&pool, (most + 1) * 8, &d_ooff));
   TRY(dalloc(&pool, tmax, &d_out));
+  if (p->x.gidx != NULL && !p->x.flip && whole_in && text_slice_end(&h, 0, cap) == n)
+    { void *d_gidx, *d_goff;
+      TRY(dupload(&pool, p->x.gidx, (size_t) p->x.gidx_words * 4, &d_gidx));
+      TRY(dupload(&pool, p->x.gidx_off, (n + 1) * 8, &d_goff));
+      TRY(dx_qv_use_index(ctx, s.d_in, s.d_seg, n, d_gidx, d_goff, p->x.gidx_none));
+      indexed = 1;
+    }
   for (i0 = 0; i0 < n; i0 = i1)
     { const size_t t0 = text_at(&h, i0);
       const uint64_t *rec = s.d_rec;
@@ -1534,12 +1540,15 @@ static int undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slic
           TRY(dx_h2d(ctx, s.d_in, p->img + b0, (size_t) (p->x.rec_off[i1] - b0)));
           TRY(dx_h2d(ctx, s.d_rec, rel + most + 1, (i1 - i0 + 1) * 8));
         }
+      fmark("undexqv: buffers ready");
       TRY(dx_qv_decode(ctx, s.d_in, rec, (const uint64_t *) s.d_hoff + i0, (const uint32_t *) s.d_seg + 5 * i0, (const uint32_t *) s.d_len + i0, i1 - i0,
                        decode_flags(p, upper), d_out, d_ooff));
+      fmark("undexqv: decoded");
       TRY(deliver(arg, d_out, i0, i1, t0, text_at(&h, i1) - t0));
+      fmark("undexqv: text passed on");
     }
 done:
-  if (indexed) (void) dx_qv_use_index(ctx, NULL, NULL, 0, NULL, NULL, 0);
+  if (indexed) (void) dx_qv_use_index(ctx, NULL, NULL, 0, NULL, NULL, 0);     /* (either index: the host walk's lives in the pool freed below) */
   dfree_all(&pool);
   free(rel);
   return rc == SLICE_STOP ? DX_OK : rc;
@@ -1565,41 +1574,18 @@ static size_t undexqv_cap(dx_ctx *ctx, const dx_undexqv_plan *p, int *whole_in)
 }
 
 int dx_file_undexqv_run(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, dx_sink_fn sink, void *user)
-{ dpool     pool = { {0}, 0, ctx };
-  undexqv_staged s;
-  void     *d_out, *d_ooff;
-  hdr_patch h;
-  size_t    cap;
-  int       rc = DX_OK, indexed = 0, whole_in;
+{ size_t cap;
+  int    whole_in;
 
   if (ctx == NULL || p == NULL || sink == NULL) return DX_E_ARG;
-  h.n = p->x.n; h.ooff = p->ooff; h.hat = p->hat; h.hd = p->hd.p; h.sink = sink; h.user = user; h.base = 0; h.total = p->total;
   if (p->ctx != NULL && p->ctx != ctx) return DX_E_ARG;   /* (a plan made on a device runs there) */
   if (p->x.n == 0) return DX_OK;
   cap = undexqv_cap(ctx, p, &whole_in);
-  if (cap)
-    { slice_out so = { ctx, &h, NULL };
-      return undexqv_sliced(ctx, p, upper, slice_deliver, &so, cap, dx_test_on("slice_input") && !PLAN_HAS_IMAGE(p) ? 0 : whole_in);   /* (DEXGPU_TEST=slice_input) */
-    }
-  TRY(undexqv_stage(ctx, p, &pool, 0, 0, &s, &indexed));  /* (image and index: up, or on the device already) */
-  TRY(dupload(&pool, p->ooff, p->x.n * 8, &d_ooff));
-  TRY(dalloc(&pool, p->total, &d_out));
-  if (p->x.gidx != NULL && !p->x.flip)                   /* the host walk's group index: a wavefront per line (dx_qv_use_index) */
-    { void *d_gidx, *d_goff;
-      TRY(dupload(&pool, p->x.gidx, (size_t) p->x.gidx_words * 4, &d_gidx));
-      TRY(dupload(&pool, p->x.gidx_off, (p->x.n + 1) * 8, &d_goff));
-      TRY(dx_qv_use_index(ctx, s.d_in, s.d_seg, p->x.n, d_gidx, d_goff, p->x.gidx_none));
-      indexed = 1;
-    }
-  fmark("undexqv: buffers ready");
-  TRY(dx_qv_decode(ctx, s.d_in, s.d_rec, s.d_hoff, s.d_seg, s.d_len, p->x.n, decode_flags(p, upper), d_out, d_ooff));
-  fmark("undexqv: decoded");
-  TRY(dx_d2h_stream(ctx, d_out, p->total, patch_and_pass, &h));
-  fmark("undexqv: text passed on");
-done:
-  if (indexed) (void) dx_qv_use_index(ctx, NULL, NULL, 0, NULL, NULL, 0);     /* (the index lives in the pool freed below) */
-  dfree_all(&pool);
-  return rc;
+  if (cap && dx_test_on("slice_input") && !PLAN_HAS_IMAGE(p)) whole_in = 0;      /* (DEXGPU_TEST=slice_input) */
+  { hdr_patch h = { p->x.n, p->ooff, p->hat, p->hd.p, sink, user, 0, p->total };
+    slice_out so = { ctx, &h, NULL };
+    return undexqv_sliced(ctx, p, upper, slice_deliver, &so, cap, whole_in);
+  }
 }
 
 typedef struct { uint8_t *res; } mem_sink;
@@ -1625,6 +1611,59 @@ int dx_file_undexqv(dx_ctx *ctx, const uint8_t *img, size_t n, int upper, uint8_
   else             free(m.res);
   dx_file_undexqv_plan_free(p);
   return rc;
+}
+
+/* ==========================================================================================
+ *  An image of any of the three kinds and the text it decodes to, for who wants the text's slices where they are made
+ *  (dx_file_verify, dx_file_digest): the image's records walked, the header lines the decoder prints, the text's layout.
+ * ========================================================================================== */
+typedef struct
+  { int              kind, mode, upper;            /* DX_KIND_*; the 2-bit kinds' DX_LETTERS_*; quiva: undexqv -U */
+    uint32_t         width;                        /* the 2-bit kinds' line width */
+    const uint8_t   *img;
+    size_t           n;
+    u2_index         ux;                           /* the 2-bit kinds' records */
+    dx_undexqv_plan *plan;                         /* quiva's */
+    uint64_t        *ooff;                         /* h.n + 1 (the last: h.total); owned for the 2-bit kinds, the plan's for quiva */
+    hdr_patch        h;                            /* the layout as the slice loops and their hooks read it (no sink): h.n records, h.total
+                                                      bytes of text, the header lines h.hd one after the other, hd_len bytes of them */
+    size_t           hd_len;
+  } image_text;
+
+static void image_close(image_text *im)
+{ dx_file_undexqv_plan_free(im->plan);
+  u2_index_free(&im->ux);
+  if (im->kind != DX_KIND_QUIVA) free(im->ooff);
+  memset(im, 0, sizeof(*im));
+}
+
+/* an error leaves what there is to image_close */
+static int image_open(dx_ctx *ctx, int kind, int upper, uint32_t width, const uint8_t *img, size_t n, image_text *im)
+{ hdr_patch *h = &im->h;
+  int rc;
+  memset(im, 0, sizeof(*im));
+  im->kind = kind; im->upper = upper; im->width = width; im->img = img; im->n = n;
+  if (kind == DX_KIND_QUIVA)
+    { if ((rc = dx_file_undexqv_plan_on(ctx, img, n, &im->plan, &h->total)) != DX_OK) return rc;
+      h->n = im->plan->x.n; im->ooff = im->plan->ooff; h->hat = im->plan->hat; h->hd = im->plan->hd.p; im->hd_len = im->plan->hd.len;
+    }
+  else
+    { im->mode = kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : (upper ? DX_LETTERS_UPPER : DX_LETTERS_LOWER);
+      if ((rc = u2_walk(im->mode, img, n, NULL, &im->ux)) != DX_OK) return rc;
+      h->n = im->ux.cnt;
+      if ((im->ooff = malloc((h->n + 1) * sizeof(*im->ooff))) == NULL) return DX_E_NOMEM;
+      h->total = u2_layout(&im->ux, width, im->ooff);
+      im->ooff[h->n] = h->total;
+      h->hat = im->ux.hat; h->hd = im->ux.hd.p; im->hd_len = im->ux.hd.len;
+    }
+  h->ooff = im->ooff;
+  return DX_OK;
+}
+
+/* the text in slices of at most `cap` bytes (0: in one), each to `fn`; whole_in: quiva's image goes up whole (undexqv_sliced) */
+static int image_slices(dx_ctx *ctx, const image_text *im, size_t cap, int whole_in, slice_fn fn, void *arg)
+{ if (im->kind == DX_KIND_QUIVA) return undexqv_sliced(ctx, im->plan, im->upper, fn, arg, cap, whole_in);
+  return unpack2_slices(ctx, im->mode, im->img, im->n, im->width, &im->ux, &im->h, cap, fn, arg);
 }
 
 /* ==========================================================================================
@@ -1672,18 +1711,8 @@ static int verify_slice(void *arg, const void *d_out, uint64_t i0, uint64_t i1, 
   (void) bytes;
   if (m == 0) return SLICE_STOP;
   s0 = v->off[i0]; s1 = v->off[e1 - 1] + vj_body_bytes(v, e1 - 1);
-  if (s1 - s0 + 64 > v->src_cap)
-    { if (v->d_src) (void) dx_free(v->ctx, v->d_src);
-      v->d_src = NULL; v->src_cap = 0;
-      if ((rc = dx_malloc(v->ctx, (size_t) (s1 - s0) + 64, &v->d_src)) != DX_OK) goto bad;
-      v->src_cap = (size_t) (s1 - s0) + 64;
-    }
-  if (m * 28 + 64 > v->arr_cap)
-    { if (v->d_arr) (void) dx_free(v->ctx, v->d_arr);
-      v->d_arr = NULL; v->arr_cap = 0;
-      if ((rc = dx_malloc(v->ctx, (size_t) m * 28 + 64, &v->d_arr)) != DX_OK) goto bad;
-      v->arr_cap = (size_t) m * 28 + 64;
-    }
+  if ((rc = dgrow(v->ctx, &v->d_src, &v->src_cap, (size_t) (s1 - s0) + 64)) != DX_OK) goto bad;
+  if ((rc = dgrow(v->ctx, &v->d_arr, &v->arr_cap, (size_t) m * 28 + 64)) != DX_OK) goto bad;
   h = malloc((size_t) m * 28 + 64);                        /* a_off, b_off (8 each), a_len, b_len, the lines' symbols (4 each) */
   if (h == NULL) { rc = DX_E_NOMEM; goto bad; }
   a_off = (uint64_t *) h; b_off = a_off + m; a_len = (uint32_t *) (b_off + m); b_len = a_len + m; q_len = b_len + m;
@@ -1793,19 +1822,17 @@ int dx_file_text_options(int kind, const uint8_t *text, size_t n, int *upper, ui
 int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const uint8_t *img, size_t m, int lossy, dx_verify_report *rep)
 { seq_index        sx;
   quiva_index      qx = { 0, NULL, NULL, NULL, 0 };
-  u2_index         ux;
-  dx_undexqv_plan *plan = NULL;
+  image_text       im;
   verify_job       v;
-  uint64_t        *ooff = NULL, el = 0, both, hfirst;
-  const uint64_t  *hat = NULL;
-  const char      *hd = NULL;
-  size_t           total = 0, cap;
-  int              rc, ec = 0, mode = DX_LETTERS_LOWER;
+  uint64_t         el = 0, both, hfirst;
+  const uint64_t  *hat;
+  const char      *hd;
+  int              rc, ec = 0;
 
   if (ctx == NULL || rep == NULL || (text == NULL && n) || (img == NULL && m)) return DX_E_ARG;
   if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW && kind != DX_KIND_QUIVA) return DX_E_ARG;
   memset(rep, 0, sizeof(*rep));
-  memset(&sx, 0, sizeof(sx)); memset(&ux, 0, sizeof(ux)); memset(&v, 0, sizeof(v));
+  memset(&sx, 0, sizeof(sx)); memset(&im, 0, sizeof(im)); memset(&v, 0, sizeof(v));
   v.ctx = ctx; v.rep = rep; v.kind = kind; v.lossy = lossy; v.text = text; v.n = n; v.hit = UINT64_MAX;
 
   /* the text: its records, and the options that would give it back */
@@ -1820,27 +1847,14 @@ int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const u
   text_options(kind, text, &sx, &qx, &rep->upper, &rep->width);
   rep->records_src = v.cnt;
 
-  /* the image: its records, the header lines the decoder prints, the text's layout */
-  if (kind == DX_KIND_QUIVA)
-    { rc = m ? dx_file_undexqv_plan_on(ctx, img, m, &plan, &total) : DX_E_FORMAT;
-      if (rc == DX_OK) { rep->records_img = plan->x.n; ooff = NULL; v.ooff = plan->ooff; hat = plan->hat; hd = plan->hd.p; }
-    }
-  else
-    { mode = kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : (rep->upper ? DX_LETTERS_UPPER : DX_LETTERS_LOWER);
-      rc = m ? u2_walk(mode, img, m, NULL, &ux) : DX_E_FORMAT;
-      if (rc == DX_OK && (ooff = malloc((ux.cnt + 1) * sizeof(*ooff))) == NULL) rc = DX_E_NOMEM;
-      if (rc == DX_OK)
-        { total = u2_layout(&ux, rep->width, ooff);
-          ooff[ux.cnt] = total;
-          rep->records_img = ux.cnt; v.ooff = ooff; hat = ux.hat; hd = ux.hd.p;
-        }
-    }
+  /* the image, decoded with those options */
+  rc = m ? image_open(ctx, kind, rep->upper, rep->width, img, m, &im) : DX_E_FORMAT;
   if (rc == DX_E_FORMAT || rc == DX_E_UNSUPPORTED || rc == DX_E_DEGENERATE)
     { rep->where = DX_VERIFY_IMAGE;                        /* (no image of anything) */
       rc = DX_OK; goto done;
     }
   if (rc != DX_OK) goto done;
-  v.hat = hat;
+  rep->records_img = im.h.n; v.ooff = im.h.ooff; v.hat = hat = im.h.hat; hd = im.h.hd;
 
   /* header lines, here: the first record whose line is not the decoder's (O(records)) */
   both = v.cnt < rep->records_img ? v.cnt : rep->records_img;
@@ -1851,14 +1865,9 @@ int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const u
 
   /* bodies, there: of the records in front of that one */
   v.upto = hfirst;
-  cap = verify_cap(ctx, kind == DX_KIND_QUIVA && PLAN_HAS_IMAGE(plan) ? 0 : m, total, both);
   if (v.upto > 0)
-    { if (kind == DX_KIND_QUIVA)
-        rc = undexqv_sliced(ctx, plan, rep->upper, verify_slice, &v, cap ? cap : total + 1, 1);
-      else
-        { const hdr_patch h = { ux.cnt, ooff, ux.hat, ux.hd.p, NULL, NULL, 0, total };
-          rc = unpack2_slices(ctx, mode, img, m, rep->width, &ux, &h, cap ? cap : total + 1, verify_slice, &v);
-        }
+    { const size_t cap = verify_cap(ctx, kind == DX_KIND_QUIVA && PLAN_HAS_IMAGE(im.plan) ? 0 : m, im.h.total, both);
+      rc = image_slices(ctx, &im, cap, 1, verify_slice, &v);
       if (rc != DX_OK && !v.failed && (rc == DX_E_FORMAT || rc == DX_E_MISMATCH || rc == DX_E_UNSUPPORTED))
         { rep->where = DX_VERIFY_IMAGE;                    /* the decoder turned the records down */
           rc = DX_OK; goto done;
@@ -1890,21 +1899,20 @@ int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const u
     { if (kind != DX_KIND_QUIVA)
         { uint64_t sym = 0, k;
           for (k = v.off[rep->record]; rep->where == DX_VERIFY_BODY && k < rep->src_byte; k++) sym += text[k] != '\n';
-          rep->img_byte = ux.ioff[rep->record] + sym / 4;
+          rep->img_byte = im.ux.ioff[rep->record] + sym / 4;
         }
-      else if (PLAN_HAS_INDEX(plan))
-        TRY(dx_d2h(ctx, &rep->img_byte, plan->dix.d_rec_off + rep->record, 8));
+      else if (PLAN_HAS_INDEX(im.plan))
+        TRY(dx_d2h(ctx, &rep->img_byte, im.plan->dix.d_rec_off + rep->record, 8));
       else
-        rep->img_byte = plan->x.rec_off[rep->record];
+        rep->img_byte = im.plan->x.rec_off[rep->record];
     }
   rc = DX_OK;
 
 done:
   if (v.d_src) (void) dx_free(ctx, v.d_src);
   if (v.d_arr) (void) dx_free(ctx, v.d_arr);
-  dx_file_undexqv_plan_free(plan);
-  seq_index_free(&sx); quiva_index_free(&qx); u2_index_free(&ux);
-  free(ooff);
+  image_close(&im);
+  seq_index_free(&sx); quiva_index_free(&qx);
   return rc;
 }
 
@@ -1931,12 +1939,7 @@ static int digest_slice(void *arg, const void *d_out, uint64_t i0, uint64_t i1, 
   uint64_t *off, *len, k, sbytes = 0;
   uint32_t  scrc = 0;
   int       rc;
-  if (m * 52 + 64 > g->arr_cap)
-    { if (g->d_arr) (void) dx_free(g->ctx, g->d_arr);
-      g->d_arr = NULL; g->arr_cap = 0;
-      if ((rc = dx_malloc(g->ctx, (size_t) m * 52 + 64, &g->d_arr)) != DX_OK) return rc;
-      g->arr_cap = (size_t) m * 52 + 64;
-    }
+  if ((rc = dgrow(g->ctx, &g->d_arr, &g->arr_cap, (size_t) m * 52 + 64)) != DX_OK) return rc;
   off = malloc((size_t) m * 32 + 64);                      /* off, len: 2 m each, a record's header line, then its body */
   if (off == NULL) return DX_E_NOMEM;
   len = off + 2 * m;
@@ -1964,52 +1967,29 @@ static int digest_slice(void *arg, const void *d_out, uint64_t i0, uint64_t i1, 
 }
 
 int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int upper, uint32_t width, dx_digest *out, uint32_t **rec_crc)
-{ u2_index         ux;
-  dx_undexqv_plan *plan = NULL;
-  digest_job       g;
-  hdr_patch        h;
-  uint64_t        *ooff = NULL, cnt = 0;
-  size_t           total = 0;
-  int              rc;
+{ image_text im;
+  digest_job g;
+  uint64_t   cnt;
+  int        rc;
 
   if (ctx == NULL || img == NULL || out == NULL) return DX_E_ARG;
   if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW && kind != DX_KIND_QUIVA) return DX_E_ARG;
   if (kind != DX_KIND_QUIVA && width == 0) return DX_E_ARG;
   if (rec_crc) *rec_crc = NULL;
-  memset(&ux, 0, sizeof(ux)); memset(&g, 0, sizeof(g)); memset(&h, 0, sizeof(h));
-  g.ctx = ctx; g.h = &h;
+  memset(&g, 0, sizeof(g));
+  g.ctx = ctx; g.h = &im.h;
 
-  /* the image: its records, the header lines the decoder prints, the text's layout */
-  if (kind == DX_KIND_QUIVA)
-    { TRY(dx_file_undexqv_plan_on(ctx, img, m, &plan, &total));
-      cnt = plan->x.n;
-      h.n = cnt; h.ooff = plan->ooff; h.hat = plan->hat; h.hd = plan->hd.p; h.total = total;
-      g.hd_bytes = plan->hd.len;
-    }
-  else
-    { TRY(u2_walk(kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : DX_LETTERS_LOWER, img, m, NULL, &ux));
-      cnt = ux.cnt;
-      if ((ooff = malloc((cnt + 1) * sizeof(*ooff))) == NULL) { rc = DX_E_NOMEM; goto done; }
-      total = u2_layout(&ux, width, ooff);
-      h.n = cnt; h.ooff = ooff; h.hat = ux.hat; h.hd = ux.hd.p; h.total = total;
-      g.hd_bytes = ux.hd.len;
-    }
+  TRY(image_open(ctx, kind, upper, width, img, m, &im));
+  cnt = im.h.n; g.hd_bytes = im.hd_len;
   if (rec_crc != NULL && (g.rec = malloc((cnt + 1) * sizeof(*g.rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
 
   if (cnt > 0)
-    { TRY(dx_malloc(ctx, g.hd_bytes + 64, &g.d_hd));
-      TRY(dx_h2d(ctx, g.d_hd, h.hd, g.hd_bytes));
-      if (kind == DX_KIND_QUIVA)
-        { int whole_in;
-          const size_t cap = undexqv_cap(ctx, plan, &whole_in);
-          TRY(undexqv_sliced(ctx, plan, upper, digest_slice, &g, cap ? cap : total + 1, whole_in));
-        }
-      else
-        { const int    mode = kind == DX_KIND_ARROW ? DX_LETTERS_ARROW : (upper ? DX_LETTERS_UPPER : DX_LETTERS_LOWER);
-          const size_t cap  = out_cap(ctx, m, total, cnt);
-          TRY(unpack2_slices(ctx, mode, img, m, width, &ux, &h, cap ? cap : total + 1, digest_slice, &g));
-        }
-      if (g.bytes != total) { rc = DX_E_MISMATCH; goto done; }     /* (the slices are the whole text) */
+    { int whole_in = 1;
+      const size_t cap = kind == DX_KIND_QUIVA ? undexqv_cap(ctx, im.plan, &whole_in) : out_cap(ctx, m, im.h.total, cnt);
+      TRY(dx_malloc(ctx, g.hd_bytes + 64, &g.d_hd));
+      TRY(dx_h2d(ctx, g.d_hd, im.h.hd, g.hd_bytes));
+      TRY(image_slices(ctx, &im, cap, whole_in, digest_slice, &g));
+      if (g.bytes != im.h.total) { rc = DX_E_MISMATCH; goto done; }     /* (the slices are the whole text) */
     }
   out->crc32 = g.crc; out->reserved = 0; out->bytes = g.bytes; out->records = cnt;
   if (rec_crc) { *rec_crc = g.rec; g.rec = NULL; }
@@ -2018,9 +1998,8 @@ int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int uppe
 done:
   if (g.d_hd) (void) dx_free(ctx, g.d_hd);
   if (g.d_arr) (void) dx_free(ctx, g.d_arr);
-  dx_file_undexqv_plan_free(plan);
-  u2_index_free(&ux);
-  free(ooff); free(g.rec);
+  image_close(&im);
+  free(g.rec);
   return rc;
 }
 

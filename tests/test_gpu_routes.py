@@ -242,3 +242,87 @@ def test_two_bit_drivers_in_slices(monkeypatch, tmp_path):
         r = subprocess.run([os.path.join(bindir, "undexta"), "-k", str(tmp_path / "reads.dexta")], env=env, capture_output=True, timeout=300)
         assert r.returncode == 0, r.stderr[-500:]
         assert (tmp_path / "reads.fasta").read_bytes() == O.undexta(O.dexta(text))
+
+
+# ---- the seam between one slice and several (the decode-side file drivers have one path: the whole text is one slice) ----
+# DEXGPU_TEXT_BUDGET has a floor of 65536 bytes and decides "whole" when it is not below the text's size, so the smallest texts that
+# reach every branch are a little over 128 KiB: two records of 70 KB of text each with an empty one between them.
+def _seam_two_bit(kind):
+    c = synth.make_seqfile(kind, 3, seed=11, lens=np.array([70000, 0, 70000], np.uint32))
+    img = O.dexta(c.text) if kind == "fasta" else O.dexar(c.text)
+    mode = L.DX_LETTERS_LOWER if kind == "fasta" else L.DX_LETTERS_ARROW
+    for width in (80, 70000):
+        want = O.undexta(img, False, width) if kind == "fasta" else O.undexar(img, width)
+        yield (want, (lambda ctx, w=width: ctx.undexta(img, width=w) if kind == "fasta" else ctx.undexar(img, width=w)),
+               (lambda ctx, sink, w=width: ctx.unpack2_stream(img, sink, mode, w)))
+
+
+def _seam_quiva():
+    c = synth.make_quiva(3, seed=12, lens=np.array([14000, 0, 14000], np.uint32))
+    img = O.dexqv(c.text)
+    return c.text, img, O.undexqv(img, upper=True)
+
+
+def _seam_cases(shape):
+    if shape != "undexqv":
+        return list(_seam_two_bit("fasta" if shape == "undexta" else "arrow"))
+    _, img, want = _seam_quiva()
+    return [(want, lambda ctx: ctx.undexqv(img, upper=True), lambda ctx, sink: ctx.undexqv_stream(img, sink, upper=True))]
+
+
+@pytest.mark.parametrize("shape", ["undexta", "undexar", "undexqv"])
+def test_one_slice_and_several_give_the_same_text(shape, monkeypatch):
+    """Three records of 70 KB, 0 and 70 KB of text (reads of 70000, 0, 70000 symbols at widths 80 and 70000; entries of 14000, 0,
+    14000 symbols), in memory and through a sink, under no budget, a budget of the text's size (set, and decides whole), of one byte
+    less (all but the last record, then the last) and of 65536 (a large record is more than the cap and a slice of its own, the "one at
+    least" rule).  Always the oracle's bytes, and the sink sees every byte of the text exactly once."""
+    with api.Context(0) as ctx:
+        for want, in_memory, through in _seam_cases(shape):
+            assert len(want) > 2 * 65536
+            for budget in (None, len(want), len(want) - 1, 65536):
+                if budget is None:
+                    monkeypatch.delenv("DEXGPU_TEXT_BUDGET", raising=False)
+                else:
+                    monkeypatch.setenv("DEXGPU_TEXT_BUDGET", str(budget))
+                assert in_memory(ctx) == want, (shape, budget)
+                got, seen = bytearray(len(want)), np.zeros(len(want), np.uint8)
+                def sink(data, at):
+                    got[at: at + len(data)] = data
+                    seen[at: at + len(data)] += 1
+                assert through(ctx, sink) == len(want), (shape, budget)
+                assert bytes(got) == want and (seen == 1).all(), (shape, budget)
+
+
+def test_several_slices_leave_the_host_walks_group_index_out(monkeypatch):
+    """DEXGPU_TEST=walk_index with a text in several slices: the same text, and the wave-per-line decoders did not run (the host
+    walk's group index is for the whole image in one slice)."""
+    _, img, want = _seam_quiva()
+    set_flag(monkeypatch, "walk_index", "1")
+    monkeypatch.setenv("DEXGPU_TEXT_BUDGET", "65536")
+    with api.Context(0) as ctx:
+        ctx.profile(True)
+        assert ctx.undexqv(img, upper=True) == want
+        used = ctx.kernel_times()
+        ctx.profile(False)
+    assert "k_qv_decode_sub" not in used and "k_qv_decode_runs" not in used, used.keys()
+
+
+def test_verify_and_digest_decode_by_the_route_of_the_tools_run(monkeypatch):
+    """DEXGPU_TEST=walk_index and no budget: dx_file_verify and dx_file_digest of an image with a run character decode it with
+    the host walk's group index, as dx_file_undexqv does (k_qv_decode_runs ran), and say what they say without the flag."""
+    import zlib
+    text, img, want = _seam_quiva()
+    assert text == want and api.qv_walk(img, index=True)["delChar"] >= 0
+    monkeypatch.delenv("DEXGPU_TEXT_BUDGET", raising=False)
+    with api.Context(0) as ctx:
+        plain_d, plain_v = ctx.digest("quiva", img, upper=True), ctx.verify("quiva", text, img)
+        assert plain_d["crc32"] == zlib.crc32(want) and plain_d["bytes"] == len(want) and plain_v["ok"]
+        set_flag(monkeypatch, "walk_index", "1")
+        for call, plain in ((lambda: ctx.digest("quiva", img, upper=True), plain_d), (lambda: ctx.verify("quiva", text, img), plain_v),
+                            (lambda: ctx.undexqv(img, upper=True), want)):
+            ctx.profile(True)
+            got = call()
+            used = ctx.kernel_times()
+            ctx.profile(False)
+            assert got == plain
+            assert "k_qv_decode_runs" in used, used.keys()

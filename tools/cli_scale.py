@@ -1,7 +1,8 @@
-"""The six tools end to end on LARGE files, tmpfs to tmpfs (GPU box): tools/cli_scale.py [GB of .quiva, default 20] [--ref]
+"""The six tools end to end on LARGE files, tmpfs to tmpfs (GPU box): tools/cli_scale.py [GB of .quiva, default 20] [--ref] [--budget-quarter]
   dexqv / undexqv on an S GB .quiva (S / 50 KB entries of 10 kb, the bench's generator), dexta / undexta on the .fasta of the same
   reads; per run the wall time, the tool's own DEXGPU_TIMING marks (stages), and the effective rate; every round trip compared with
-  its input (cmp); --ref: the reference's undexqv / undexta (oracle/_ref, one core) read the GPU tools' files back too.
+  its input (cmp); --ref: the reference's undexqv / undexta (oracle/_ref, one core) read the GPU tools' files back too;
+  --budget-quarter: every timed run with DEXGPU_TEXT_BUDGET at a quarter of its text's size, so that the drivers work in slices.
 One JSON object on stdout (bench.py picks it up as cpu_baseline.cli_end_to_end_large when it is in profiles/)."""
 import atexit, json, os, re, shutil, signal, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,6 +13,7 @@ from dextractor_amd import api, synth
 
 GB = float(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else 20.0
 REF = "--ref" in sys.argv
+QUARTER = "--budget-quarter" in sys.argv
 # a directory of this run's own (two runs on one box must not share files), removed however the run ends: the files are tens
 # of GB of RAM-backed tmpfs.  --dir D: the caller made D and removes it itself as well (bench.py does, after a timeout's kill)
 D = sys.argv[sys.argv.index("--dir") + 1] if "--dir" in sys.argv else tempfile.mkdtemp(prefix="cliscale.", dir="/dev/shm")
@@ -98,13 +100,16 @@ qbytes = make_files()
 fbytes = os.path.getsize(os.path.join(D, "s.fasta"))
 res["file"] = {"quiva_bytes": qbytes, "fasta_bytes": fbytes, "entries": n, "mean_len": mean, "made_in_s": round(time.perf_counter() - t0, 1),
                "where": "tmpfs (/dev/shm) to tmpfs"}
+if QUARTER:
+    res["file"]["text_budget"] = "a quarter of each text"
 log("files made:", res["file"])
 for kind, pack, unpack, ext, px, uflags in (("quiva", "dexqv", "undexqv", ".quiva", ".dexqv", ["-U"]), ("fasta", "dexta", "undexta", ".fasta", ".dexta", ["-U", "-w80"])):
     size = qbytes if kind == "quiva" else fbytes
+    env = {"DEXGPU_TEXT_BUDGET": str(size // 4)} if QUARTER else None
     os.replace(os.path.join(D, "s" + ext), os.path.join(D, "s0" + ext))
     os.link(os.path.join(D, "s0" + ext), os.path.join(D, "s" + ext))
     for rep in range(2):
-        dt, marks = run(os.path.join(BIN, pack), ["-k", "s"])
+        dt, marks = run(os.path.join(BIN, pack), ["-k", "s"], env)
         res["runs"].setdefault(pack, []).append({"s": round(dt, 3), "GBps": round(size / dt / 1e9, 2), "marks_ms": marks})
         log(pack, dt)
     if kind == "fasta":
@@ -134,7 +139,7 @@ for kind, pack, unpack, ext, px, uflags in (("quiva", "dexqv", "undexqv", ".quiv
     os.unlink(os.path.join(D, "s" + ext))
     psize = os.path.getsize(os.path.join(D, "s" + px))
     for rep in range(2):
-        dt, marks = run(os.path.join(BIN, unpack), ["-k"] + uflags + ["s"])
+        dt, marks = run(os.path.join(BIN, unpack), ["-k"] + uflags + ["s"], env)
         # the text against the input: byte for byte (.fasta); the .quiva generator pads its header fields where undexqv prints %d
         # (undexqv.c:182), so there the text is packed once more and THAT file compared with the first (same tables, same records)
         if kind == "fasta":
