@@ -15,7 +15,8 @@ CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 # verify/, records/, reads/, digest/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
 HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads digest/dx_crc
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
-C_OBJ    = $(BUILD)/dx_host.o $(BUILD)/dx_walk_host.o $(BUILD)/dx_files.o $(BUILD)/dx_compat.o
+C_SRC    = dx_host dx_walk_host dx_files dx_file_pack2 dx_file_qv dx_file_check dx_select dx_compat
+C_OBJ    = $(C_SRC:%=$(BUILD)/%.o)
 TOOLS    = dexta undexta dexar undexar dexqv undexqv
 
 all: lib cli
@@ -30,7 +31,7 @@ $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/dx_internal.hpp $(CSRC)/dx_device.hpp $(CSRC
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.res; rc=$$?; \
 	  grep -v "kernel-resource-usage\|^ *[0-9]* | \|^ *| *^" $(BUILD)/$*.res >&2; exit $$rc
 
-$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_host.h $(CSRC)/dx_env.h include/dexgpu.h include/dexcompat.h
+$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_host.h $(CSRC)/dx_files.h $(CSRC)/dx_env.h include/dexgpu.h include/dexcompat.h
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
@@ -54,4 +55,9 @@ oracle:
 clean:
 	rm -rf $(BUILD) $(LIB) dextractor_amd/bin
 
-.PHONY: all lib cli oracle clean
+# what the library is linked from, for tools/mkvariant.sh: the device files' names, then the host objects
+print-objs:
+	@echo $(HIP_SRC)
+	@echo $(C_OBJ)
+
+.PHONY: all lib cli oracle clean print-objs

@@ -1,0 +1,176 @@
+/*
+ * dx_files.h -- what the file drivers share among themselves; no part of the C-ABI.
+ *
+ *     dx_files.c       what every driver uses, and the decoded text on its way out (header lines laid over it, slices of it)
+ *     dx_file_pack2.c  dexta / dexar (whole, streamed, sharded), undexta / undexar
+ *     dx_file_qv.c     dexqv (whole, sliced, sharded), undexqv plan / run
+ *     dx_file_check.c  an image of any kind and its text where it is made: dx_file_verify, dx_file_digest
+ *     dx_select.c      the .qvs entry API, the .bps / .arw read loader
+ *
+ * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
+ */
+#ifndef DX_FILES_H
+#define DX_FILES_H
+#include <stddef.h>
+#include <stdint.h>
+#include "dexgpu.h"
+
+#define DXF_HIDDEN __attribute__((visibility("hidden")))
+
+#define TRY(x) do { rc = (x); if (rc != DX_OK) goto done; } while (0)
+
+#define DX_GPU_INDEX_MIN (1u << 20)      /* .quiva images from 1 MiB on are indexed on the GPU */
+
+/* ---- device arrays that are freed together -------------------------------------------------------------------------- */
+typedef struct { void *p[24]; int n; dx_ctx *ctx; } dpool;
+
+static inline int dalloc(dpool *pool, size_t bytes, void **out)
+{ int rc;
+  if (pool->n >= (int) (sizeof(pool->p) / sizeof(pool->p[0])) - 2) return DX_E_NOMEM;   /* pool slots exhausted */
+  rc = dx_malloc(pool->ctx, bytes + 64, out);
+  if (rc == DX_OK) pool->p[pool->n++] = *out;
+  return rc;
+}
+
+static inline int dupload(dpool *pool, const void *src, size_t bytes, void **out)
+{ int rc = dalloc(pool, bytes, out);
+  if (rc == DX_OK && bytes) rc = dx_h2d(pool->ctx, *out, src, bytes);
+  return rc;
+}
+
+/* a device array of the caller's (*p, *cap bytes of it; none yet: NULL, 0) that is to hold `need` bytes: made anew when it is too small,
+   and what it held is gone then */
+static inline int dgrow(dx_ctx *ctx, void **p, size_t *cap, size_t need)
+{ int rc;
+  if (need <= *cap) return DX_OK;
+  if (*p) (void) dx_free(ctx, *p);
+  *p = NULL; *cap = 0;
+  if ((rc = dx_malloc(ctx, need, p)) != DX_OK) { *p = NULL; return rc; }
+  *cap = need;
+  return DX_OK;
+}
+
+static inline void dfree_all(dpool *pool)
+{ int i;
+  for (i = 0; i < pool->n; i++)
+    dx_free(pool->ctx, pool->p[i]);
+  pool->n = 0;
+}
+
+/* ---- dx_files.c ------------------------------------------------------------------------------------------------------ */
+/* DEXGPU_TEXT_BUDGET (bytes): how much of `whole` bytes the device is to take at once.  1: the variable is set and has decided -- *cap is
+   its figure (`floor` at least), or 0 for all at once (no figure, or one the whole stays under); 0: it is not set, what is free decides */
+DXF_HIDDEN int dxf_budget_env(size_t whole, size_t floor, size_t *cap);
+
+/* a sink that sees its chunks `shift` bytes further on (the record stream follows the file's head; a piece follows the pieces before it) */
+typedef struct { dx_sink_fn sink; void *user; size_t shift; } shifted_sink;
+static inline int pass_shifted(void *arg, uint8_t *data, size_t len, size_t at)
+{ shifted_sink *h = arg;
+  return h->sink(h->user, data, len, at + h->shift);
+}
+
+/* text that grows (the header lines a decoder prints): room for `more` bytes behind the len that are there */
+typedef struct { char *p; size_t len, cap; } tbuf;
+DXF_HIDDEN int dxf_tb_room(tbuf *b, size_t more);
+
+/* A chunk of decoded text on its way out (dx_d2h_stream): the header lines that fall into it are laid over it.
+   Entry i's text starts at ooff[i]; its header line, hd[hat[i] .. hat[i+1]), ends there.                 */
+typedef struct
+  { uint64_t n; const uint64_t *ooff, *hat; const char *hd;
+    dx_sink_fn sink; void *user;
+    size_t base;                  /* where in the text the streamed buffer starts (a slice of the entries; else 0) */
+    size_t total;                 /* the whole text's bytes */
+  } hdr_patch;
+
+/* where entry i's header line starts in the text (i == n: where the text ends) */
+static inline size_t text_at(const hdr_patch *h, uint64_t i)
+{ return i < h->n ? (size_t) h->ooff[i] - (size_t) (h->hat[i + 1] - h->hat[i]) : h->total; }
+
+/* a slice of whole entries from i0 on: as many as make at most `cap` bytes of text, and one at least; cap 0: all that are left */
+DXF_HIDDEN uint64_t dxf_text_slice_end(const hdr_patch *h, uint64_t i0, size_t cap);
+
+/* how much of an output of `total` bytes the device makes at once beside an input of n bytes (and 48 bytes of index a unit): 0 = all
+   of it; DEXGPU_TEXT_BUDGET (bytes) when set, else what is free decides */
+DXF_HIDDEN size_t dxf_out_cap(dx_ctx *ctx, size_t n, size_t total, uint64_t units);
+
+/* What becomes of a slice of decoded text -- entries [i0, i1), `bytes` of them at d_out, the first at t0 in the whole text: DX_OK
+   (the next slice), SLICE_STOP (no more slices are wanted: not an error), or an error */
+typedef int (*slice_fn)(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes);
+#define SLICE_STOP 1
+
+/* ... out to the caller: into the text in memory (res), or through the sink of h; header lines in place either way */
+typedef struct { dx_ctx *ctx; hdr_patch *h; uint8_t *res; } slice_out;
+DXF_HIDDEN int dxf_slice_deliver(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes);
+
+/* ---- dx_file_pack2.c ------------------------------------------------------------------------------------------------- */
+/* The index of a .fasta / .arrow text and the layout of its image.  Per read: where its lines begin in the text and how long they are
+   (off, tlen: host index only), its symbols (nsym), the header's fields (hdr4, cnr4); then the framed header bytes (blob, hoff[cnt + 1])
+   and the record's place in the image (ooff[cnt + 1]; ooff[cnt] == total). */
+typedef struct
+  { uint64_t  cnt, *off, *hoff, *ooff;
+    uint32_t *tlen, *nsym;
+    int32_t  *hdr4;
+    uint16_t *cnr4;
+    uint8_t  *blob;
+    size_t    plen, total;
+  } seq_index;
+
+DXF_HIDDEN int  dxf_seq_index_host(seq_index *ix, int arrow, const uint8_t *text, size_t n, uint64_t *errline, int *errcode);
+DXF_HIDDEN void dxf_seq_index_free(seq_index *ix);
+
+/* an image that arrives in pieces (dx_file_unpack2_stream): what the file's head said, the well the last record stood at, and
+   how far into this piece the whole records reached (a piece may end inside a record: `more` says that more is coming) */
+typedef struct { int started, flip, newv, well, more; int32_t plen; char *name; size_t consumed; } u2_state;
+
+/* The records of a .dexta / .dexar image, walked (undexta.c:138-271, undexar.c:136-229): per read where its packed bases stand in the
+   image (ioff) and how many there are (nsym), and its header line as the tool prints it (hd, from hat[i] on; hat[cnt]: their end);
+   `at`: how far the whole records reached, `well`: the last one's well. */
+typedef struct { uint64_t cnt, *ioff, *hat; uint32_t *nsym; tbuf hd; size_t at; int well; } u2_index;
+
+/* mode: DX_LETTERS_LOWER / _UPPER (dexta images) or _ARROW (dexar images); st: the image arrives in pieces (else NULL) */
+DXF_HIDDEN int    dxf_u2_walk(int mode, const uint8_t *img, size_t n, u2_state *st, u2_index *x);
+DXF_HIDDEN void   dxf_u2_index_free(u2_index *x);
+/* the text's layout for a line width: header line, wrapped letters, read after read; ooff[i]: where read i's letters begin */
+DXF_HIDDEN size_t dxf_u2_layout(const u2_index *x, uint32_t width, uint64_t *ooff);
+/* a walked image's text in slices of whole reads, at most `cap` bytes of text each (0: the whole text, one slice), each to `deliver` */
+DXF_HIDDEN int    dxf_unpack2_slices(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width, const u2_index *x, const hdr_patch *h,
+                                     size_t cap, slice_fn deliver, void *arg);
+
+/* ---- dx_file_qv.c ---------------------------------------------------------------------------------------------------- */
+/* The host's index of a .quiva text (dx_index_quiva): per entry where its five lines begin, how long they are, the header's four fields */
+typedef struct { uint64_t cnt, *off; uint32_t *len; int32_t *hdr4; size_t plen; } quiva_index;
+
+DXF_HIDDEN int  dxf_quiva_index_host(quiva_index *qx, const uint8_t *text, size_t n, uint64_t *errline, int *errcode);
+DXF_HIDDEN void dxf_quiva_index_free(quiva_index *qx);
+
+DXF_HIDDEN dx_qv_batch dxf_qv_batch(const void *d_text, const void *d_off, const void *d_len, uint64_t m, uint64_t span, int line_pad);
+
+/* A batch of entries as the encoder wants it: the text (b), the framing bytes of the headers and their offsets (none of either for the bare
+   record stream of the entry API), and the per-entry record offsets and segment sizes the encoder fills */
+typedef struct { dx_qv_batch b; void *d_hdr, *d_hoff, *d_rec, *d_seg; uint64_t hbytes; } qv_staged;
+
+/* m entries whose text is on the device staged in `pool` (hdr4 == NULL: no framing bytes); Compress_Next_QVentry for a staged batch */
+DXF_HIDDEN int dxf_qv_stage(dpool *pool, const int32_t *hdr4, uint64_t m, int32_t *lwell, const void *d_text, const void *d_off, const void *d_len,
+                            uint64_t span, int line_pad, qv_staged *s);
+DXF_HIDDEN int dxf_qv_encode_batch(dx_ctx *ctx, const qv_staged *s, const uint64_t (*hist)[256], const dx_qv_coding *cd, int lossy,
+                                   void **d_out, size_t *out_cap, uint64_t *total);
+
+struct dx_undexqv_plan
+  { const uint8_t *img;
+    size_t         n, total;
+    dx_qv_index    x;
+    tbuf           hd;            /* the header lines, one after the other */
+    uint64_t      *ooff, *hat;    /* per entry: where its five data lines start in the text; where its header line starts in hd */
+    /* a plan made on the device (dx_file_undexqv_plan_on): the image is there already, and so is the index */
+    dx_ctx        *ctx;
+    void          *d_in;          /* the image, when it is on ctx's device already */
+    dx_qv_dindex   dix;           /* the index, when it was made there (d_rec_off != NULL) */
+  };
+#define PLAN_HAS_IMAGE(p) ((p)->ctx != NULL && (p)->d_in != NULL)
+#define PLAN_HAS_INDEX(p) ((p)->ctx != NULL && (p)->dix.d_rec_off != NULL)
+
+/* a plan's text in slices of whole entries, at most `cap` bytes of text each (0: in one), each to `deliver`; and the cap the device asks for */
+DXF_HIDDEN int    dxf_undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_fn deliver, void *arg, size_t cap, int whole_in_);
+DXF_HIDDEN size_t dxf_undexqv_cap(dx_ctx *ctx, const dx_undexqv_plan *p, int *whole_in);
+
+#endif

@@ -1,5 +1,5 @@
 /*
- * dx_host.h -- what the library's host C files (dx_host.c, dx_walk_host.c, dx_files.c) share among themselves; no part of the C-ABI.
+ * dx_host.h -- what the library's host C files (dx_host.c, dx_walk_host.c, the file drivers of dx_files.h) share among themselves; no part of the C-ABI.
  */
 #ifndef DX_HOST_H
 #define DX_HOST_H

@@ -67,7 +67,7 @@ def merge_params(per_rank, rank_tots=None, sub_hists=None, lo_of_rank=None, lens
     (small files, many ranks) the caller passes every rank's symbol total (`rank_tots`), the ranks'
     substitution histograms of their entries up to the cut (`sub_hists`: zeros beyond it) and the
     slices' first entries / lengths, and the cut is located here -- what dx_file_dexqv_sharded
-    does with its prefix batch (csrc/dx_files.c)."""
+    does with its prefix batch (csrc/dx_file_qv.c)."""
     dC, dF = merge_del([(p[0], p[1]) for p in per_rank])
     if rank_tots is None:
         return dC, dF, int(per_rank[0][2]), int(per_rank[0][3])

@@ -257,14 +257,24 @@ def test_byte_swapped_stream(ctx, name):
 
 # ---- 8. truncated stream -----------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("packed", [False, True], ids=["cut_by_size", "packed"])
-def test_truncated_stream_is_an_error_of_the_library(ctx, packed, monkeypatch):
+# budget: the selection in slices (test_slices_give_the_same_bytes' figure), every entry in order, so that the cut one lies in the last
+# slice and its place there is not its place in the selection.  The sliced cases force their transport (entries_whole /
+# entries_packed), as that test does; cut_by_size sets no flag and lets the cut stream's size decide.
+@pytest.mark.parametrize("packed, budget", [(False, 0), (True, 0), (False, 400000), (True, 400000)],
+                         ids=["cut_by_size", "packed", "sliced_whole_stream", "sliced_packed"])
+def test_truncated_stream_is_an_error_of_the_library(ctx, packed, budget, monkeypatch):
     stream, coff, rlen, coding = bare("synth130")
     n = len(rlen)
     cut = stream[: int(coff[n - 1]) + int(coff[n] - coff[n - 1]) // 2]
-    if packed:
+    selections = (None, np.array([3, n - 1, 7]), np.arange(n)[::-1])
+    if budget:
+        assert 5 * (int(rlen[: n - 1].sum()) + n - 1) > budget      # the last entry begins behind the first slice
+        monkeypatch.setenv("DEXGPU_TEXT_BUDGET", str(budget))
+        set_flag(monkeypatch, "entries_packed" if packed else "entries_whole")
+        selections = (np.arange(n),)
+    elif packed:
         set_flag(monkeypatch, "entries_packed")
-    for ids in (None, np.array([3, n - 1, 7]), np.arange(n)[::-1]):
+    for ids in selections:
         with pytest.raises(L.DexGPUError) as e:
             ctx.entries_uncompress(coding, cut, coff, rlen, ids=ids)
         assert e.value.code == -3 and f"entry {n - 1}," in str(e.value), str(e.value)

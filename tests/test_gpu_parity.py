@@ -1026,7 +1026,7 @@ def _dev(k):
 
 def test_file_dexqv_sharded_cut_beyond_shard0(ctx):
     """~250 k symbols over 4 contexts: the 100000-symbol threshold of QV.c:1006 lies beyond shard 0, whose
-    prefix batch must then supply subChar (csrc/dx_files.c)."""
+    prefix batch must then supply subChar (csrc/dx_file_qv.c)."""
     c = synth.make_quiva(28, seed=17, mean=9000)
     cs = [api.Context(_dev(k)) for k in range(4)]
     try:
@@ -1096,7 +1096,7 @@ def test_file_dexqv_sharded_by_byte_ranges(ctx, monkeypatch, nctx):
 
 def test_sharded_file_drivers_over_every_physical_device():
     """dx_file_dexqv_sharded / dx_file_pack2_sharded with ONE context on EVERY device hipGetDeviceCount reports: the
-    hipSetDevice-per-thread path of csrc/dx_files.c on real multi-GPU hardware (BASELINE configs[4]'s layout: contiguous
+    hipSetDevice-per-thread path of csrc/dx_file_qv.c and csrc/dx_file_pack2.c on real multi-GPU hardware (BASELINE configs[4]'s layout: contiguous
     entry ranges per GPU, host-side histogram sum, outputs concatenated), against the oracle.  Skips on a one-GPU box --
     there the same drivers run over several contexts of device 0 (the tests around this one)."""
     ndev = L.load().dx_device_count()

@@ -241,12 +241,20 @@ def test_slices_give_the_same_bytes(ctx, transport, monkeypatch):
 
 # ---- 6. refusals ----------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("transport", TRANSPORTS)
-def test_a_payload_cut_short_names_the_callers_read(ctx, transport, monkeypatch):
+# budget: the selection in slices (test_slices_give_the_same_bytes' figure), every read in order, so that the cut one lies in the last
+# slice and its place there is not its place in the selection
+@pytest.mark.parametrize("transport, budget", [(t, 0) for t in TRANSPORTS] + [(t, 200000) for t in TRANSPORTS],
+                         ids=TRANSPORTS + [f"sliced_{t}" for t in TRANSPORTS])
+def test_a_payload_cut_short_names_the_callers_read(ctx, transport, budget, monkeypatch):
     syms, payload, boff, rlen = payload200()
     n, cut = 200, payload[:-1]
     set_flag(monkeypatch, transport)
-    for ids in (None, np.array([3, n - 1, 7]), np.arange(n)[::-1]):
+    selections = (None, np.array([3, n - 1, 7]), np.arange(n)[::-1])
+    if budget:
+        assert int(rlen[: n - 1].sum()) + n - 1 > budget           # the last read begins behind the first slice
+        monkeypatch.setenv("DEXGPU_TEXT_BUDGET", str(budget))
+        selections = (np.arange(n),)
+    for ids in selections:
         with pytest.raises(L.DexGPUError) as e:
             ctx.reads_uncompress(cut, boff, rlen, ids=ids)
         assert e.value.code == -3 and f"entry {n - 1}," in str(e.value), str(e.value)
