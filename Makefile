@@ -12,8 +12,8 @@ EXTRA   ?=
 HIPFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall -Wno-unused-function $(EXTRA)
 CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 
-# verify/, records/, reads/, digest/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
-HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads digest/dx_crc
+# verify/, records/, reads/, digest/, census/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes $(CSRC)/*.hip only)
+HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads digest/dx_crc census/dx_census
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
 C_SRC    = dx_host dx_walk_host dx_files dx_file_pack2 dx_file_qv dx_file_check dx_select dx_compat
 C_OBJ    = $(C_SRC:%=$(BUILD)/%.o)

@@ -73,6 +73,10 @@ class VerifyReport(C.Structure):                 # dx_verify_report
 class Digest(C.Structure):                       # dx_digest
     _fields_ = [("crc32", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("records", C.c_uint64)]
 
+class Census(C.Structure):                       # dx_census
+    _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("min_len", C.c_uint32), ("max_len", C.c_uint32),
+                ("n50", C.c_uint32), ("reserved", C.c_uint32), ("code", C.c_uint64 * 4), ("hist", (C.c_uint64 * 256) * 5)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
@@ -177,6 +181,10 @@ SIGNATURES = {
     "dx_crc32_fold": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "dx_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "dx_file_digest": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(Digest), C.POINTER(_P)]),
+    "dx_code_counts": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_uint64)]),
+    "dx_byte_hist_ranges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_int, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
+    "dx_census_lengths": (C.c_int, [_P, C.c_uint64, C.POINTER(Census)]),
+    "dx_file_census": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(Census), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

@@ -518,6 +518,60 @@ class Context:
                 self.lib.dx_file_free(rec)
         return out
 
+    # ---- census ------------------------------------------------------------------------------------
+    def _bad_unit(self, rc, bad):
+        e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
+        e.bad_unit = bad.value if bad.value != 2**64 - 1 else None
+        return e
+
+    def code_counts(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_counts=None):
+        """dx_code_counts: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None: whole
+        reads from symbol 0); d_counts (uint32, n x 4, or None) gets every unit's symbols code by code, the four totals over the
+        call's units come back as a uint64 array.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does
+        not lie inside the in_bytes."""
+        tot, bad = (C.c_uint64 * 4)(), C.c_uint64()
+        rc = self.lib.dx_code_counts(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
+                                     d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n),
+                                     d_counts.ptr if d_counts else None, C.byref(tot), C.byref(bad))
+        if rc != 0:
+            raise self._bad_unit(rc, bad)
+        return np.array(list(tot), dtype=np.uint64)
+
+    def byte_hist_ranges(self, d_buf, buf_bytes, d_off, d_len, d_kind, nkinds, n, d_sum=None):
+        """dx_byte_hist_ranges: range j = d_buf[d_off[j] .. d_off[j] + d_len[j]) (uint64 on the device) adds its bytes' values to table
+        d_kind[j] (uint8; None: all 0) of nkinds (1 to 8); d_sum (uint64, n, or None) gets every range's byte sum.  The tables come
+        back as a uint64 array (nkinds, 256).  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) for a range outside
+        the buf_bytes or a kind that is not below nkinds."""
+        nk = int(nkinds)
+        hist, bad = np.zeros((max(nk, 1), 256), dtype=np.uint64), C.c_uint64()
+        rc = self.lib.dx_byte_hist_ranges(self.h, d_buf.ptr if d_buf else None, int(buf_bytes), d_off.ptr if d_off else None,
+                                          d_len.ptr if d_len else None, d_kind.ptr if d_kind else None, nk, int(n),
+                                          d_sum.ptr if d_sum else None, hist.ctypes.data, C.byref(bad))
+        if rc != 0:
+            raise self._bad_unit(rc, bad)
+        return hist
+
+    def census(self, kind, img: bytes, per_record=False) -> dict:
+        """dx_file_census: what the image holds, counted on the device (no text is made or downloaded).  kind: "fasta", "arrow" or
+        "quiva".  {"records", "symbols", "min_len", "max_len", "n50", "code" (uint64[4]), "hist" (uint64[5, 256])}, and with
+        per_record "rec_len" (uint32) and "rec_code" (uint32 [n, 4]; fasta, arrow) or "rec_sum" (uint64 [n, 5]; quiva)."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        cs, rl, rc_, rs = L.Census(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.dx_file_census(self.h, k, img, len(img), C.byref(cs), C.byref(rl) if per_record else None,
+                                          C.byref(rc_) if per_record else None, C.byref(rs) if per_record else None))
+        out = census_dict(cs)
+        if per_record:
+            n = cs.records
+            try:
+                out["rec_len"] = np.ctypeslib.as_array(C.cast(rl, C.POINTER(C.c_uint32)), (n + 1,))[:n].copy()
+                if rc_.value:
+                    out["rec_code"] = np.ctypeslib.as_array(C.cast(rc_, C.POINTER(C.c_uint32)), (4 * n + 4,))[:4 * n].reshape(n, 4).copy()
+                if rs.value:
+                    out["rec_sum"] = np.ctypeslib.as_array(C.cast(rs, C.POINTER(C.c_uint64)), (5 * n + 5,))[:5 * n].reshape(n, 5).copy()
+            finally:
+                self.lib.dx_file_free(rl); self.lib.dx_file_free(rc_); self.lib.dx_file_free(rs)
+        return out
+
     def qv_subindex(self, on=True):
         self._chk(self.lib.dx_qv_subindex(self.h, int(bool(on))))
 
@@ -665,6 +719,25 @@ def pack2_sharded(contexts, text: bytes, arrow=False) -> bytes:
 
 
 # ---- host-only helpers (no GPU needed) ---------------------------------------------------------
+
+def census_dict(cs) -> dict:
+    """a dx_census as a dict: the scalars, "code" (uint64[4]) and "hist" (uint64[5, 256])"""
+    out = {f: int(getattr(cs, f)) for f in ("records", "symbols", "min_len", "max_len", "n50")}
+    out["code"] = np.array(list(cs.code), dtype=np.uint64)
+    out["hist"] = np.array([list(row) for row in cs.hist], dtype=np.uint64)
+    return out
+
+
+def census_lengths(lengths) -> dict:
+    """dx_census_lengths (host): {"records", "symbols", "min_len", "max_len", "n50"} of read lengths (uint32).  N50: over the lengths
+    sorted downward, the length at which the running sum first reaches half of the total; 0 without symbols."""
+    a = np.ascontiguousarray(lengths, dtype=np.uint32)
+    cs = L.Census()
+    rc = L.load().dx_census_lengths(a.ctypes.data if a.size else None, int(a.size), C.byref(cs))
+    if rc != 0:
+        raise L.DexGPUError(rc, "dx_census_lengths")
+    return {f: int(getattr(cs, f)) for f in ("records", "symbols", "min_len", "max_len", "n50")}
+
 
 def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
     """dx_crc32_combine (host): zlib's crc32_combine -- crc32(A + B) from crc32(A), crc32(B) and len(B)"""

@@ -62,6 +62,8 @@ static const tool_t TOOLS[6] =
 
 static const char *Prog;
 static int         Digest = 0;   /* DEXGPU_DIGEST: 1: a line on stdout for every file done; 2 ("only"): the line, and no output file */
+static int         Census = 0;   /* DEXGPU_CENSUS: the same for the census line (it follows the digest's) */
+#define LINES_ONLY (Digest == 2 || Census == 2)
 
 /* ---- whole-file I/O ---------------------------------------------------------------------- */
 
@@ -681,6 +683,50 @@ static int digest_of(const options *o, job *f, dx_digest *dg)
   return rc;
 }
 
+/* DEXGPU_CENSUS: what the image holds (dx_file_census: counted on the GPU where it lies or is decoded to, no text made or downloaded), on
+   one line: records, symbols, the shortest and the longest read, N50, then the symbols code by code (fasta, arrow) or the mean byte value
+   of the deletion, insertion, merge and substitution QV lines (quiva).  The image is the one DEXGPU_DIGEST takes. */
+static int census_of(const options *o, job *f, dx_census *cs)
+{ const int kind = o->tool == TOOL_DEXTA || o->tool == TOOL_UNDEXTA ? DX_KIND_FASTA
+                 : (o->tool == TOOL_DEXAR || o->tool == TOOL_UNDEXAR ? DX_KIND_ARROW : DX_KIND_QUIVA);
+  int rc = DX_OK;
+  if (f->ctx == NULL) f->ctx = context();
+  if (is_undex(o->tool))
+    return f->in == NULL ? DX_E_NOMEM : dx_file_census(f->ctx, kind, f->in, f->n, cs, NULL, NULL, NULL);
+  { FILE    *fd = fopen(f->dst, "r");
+    uint8_t *img = NULL;
+    size_t   m = 0;
+    int      imapped = 0;
+    if (fd == NULL || (img = slurp(fd, &m, &imapped)) == NULL) rc = DX_E_IO;
+    if (rc == DX_OK) rc = dx_file_census(f->ctx, kind, img, m, cs, NULL, NULL, NULL);
+    if (img != NULL) unslurp(img, m, imapped);
+    if (fd != NULL) fclose(fd);
+  }
+  return rc;
+}
+
+static void census_line(const options *o, const dx_census *cs, const char *path)
+{ printf("records=%llu symbols=%llu min=%u max=%u n50=%u", (unsigned long long) cs->records, (unsigned long long) cs->symbols,
+         cs->min_len, cs->max_len, cs->n50);
+  if (o->tool == TOOL_DEXQV || o->tool == TOOL_UNDEXQV)
+    { static const char *name[4] = { "del", "ins", "mrg", "sub" };
+      static const int   line[4] = { 0, 2, 3, 4 };
+      int q, v;
+      for (q = 0; q < 4; q++)
+        { double sum = 0.0;
+          for (v = 0; v < 256; v++) sum += (double) v * (double) cs->hist[line[q]][v];
+          printf(" %s=%.3f", name[q], cs->symbols ? sum / (double) cs->symbols : 0.0);
+        }
+    }
+  else
+    { const char *name = o->tool == TOOL_DEXTA || o->tool == TOOL_UNDEXTA ? "acgt" : "1234";
+      int q;
+      for (q = 0; q < 4; q++) printf(" %c=%llu", name[q], (unsigned long long) cs->code[q]);
+    }
+  printf(" %s\n", path);
+  fflush(stdout);
+}
+
 /* the files behind a name (dexta.c:87-94), or the standard streams */
 static void begin(const options *o, const char *name, job *f)
 { const tool_t *t = &TOOLS[o->tool];
@@ -699,12 +745,12 @@ static void begin(const options *o, const char *name, job *f)
         { fprintf(stderr, "%s: Cannot open %s for 'r'\n", Prog, f->src);   /* Fopen, DB.c:103-110 */
           leave(1);
         }
-      if (Digest != 2 && (f->output = fopen(f->dst, "w+")) == NULL)     /* (readable too: a large output is written through a shared mapping, which wants that) */
+      if (!LINES_ONLY && (f->output = fopen(f->dst, "w+")) == NULL)     /* (readable too: a large output is written through a shared mapping, which wants that) */
         { fprintf(stderr, "%s: Cannot open %s for 'w'\n", Prog, f->dst);
           leave(1);
         }
     }
-  f->out_fd = f->output != NULL ? fileno(f->output) : -1;       /* (DEXGPU_DIGEST=only: there is no output) */
+  f->out_fd = f->output != NULL ? fileno(f->output) : -1;       /* (DEXGPU_DIGEST=only, DEXGPU_CENSUS=only: there is no output) */
   if (o->verbose)
     { fprintf(stderr, "Processing '%s' ...\n", f->root);
       fflush(stderr);
@@ -713,12 +759,18 @@ static void begin(const options *o, const char *name, job *f)
 
 /* The one end of a file's run, whichever route it took and whatever that answered. */
 static void end(const options *o, job *f, int rc)
-{ dx_digest dg;
+{ dx_digest  dg;
+  dx_census *cs = NULL;
   memset(&dg, 0, sizeof(dg));
+  if (Census && (cs = calloc(1, sizeof(*cs))) == NULL) rc = rc == DX_OK ? DX_E_NOMEM : rc;
   if (rc == DX_OK && f->seek && lseek(f->out_fd, (off_t) f->out_len, SEEK_SET) < 0) rc = DX_E_IO;
   if (rc == DX_OK && Digest && is_undex(o->tool))          /* (the image is the input, while it is still in memory) */
     { rc = digest_of(o, f, &dg);
       tmark("digested");
+    }
+  if (rc == DX_OK && Census && is_undex(o->tool))
+    { rc = census_of(o, f, cs);
+      tmark("counted");
     }
   if (rc == DX_OK)
     { if (f->in != NULL) unslurp(f->in, f->n, f->mapped);
@@ -737,9 +789,21 @@ static void end(const options *o, job *f, int rc)
         }
       tmark("digested");
     }
+  if (Census && !is_undex(o->tool))
+    { if ((rc = census_of(o, f, cs)) != DX_OK)
+        { fprintf(stderr, "%s: %s could not be counted (%s); %s is kept\n", Prog, f->dst,
+                  rc == DX_E_IO ? "cannot be read" : dx_last_error(f->ctx), f->src);
+          leave(1);
+        }
+      tmark("counted");
+    }
   if (Digest)
     { printf("%08x %llu %s\n", dg.crc32, (unsigned long long) dg.bytes, is_undex(o->tool) ? f->dst : f->src);
       fflush(stdout);
+    }
+  if (Census)
+    { census_line(o, cs, is_undex(o->tool) ? f->dst : f->src);
+      free(cs);
     }
   if (!o->pipe)
     { const char *verify = getenv("DEXGPU_VERIFY");
@@ -748,7 +812,7 @@ static void end(const options *o, job *f, int rc)
             leave(3);                                    /* (the reference's tools leave with 1 and 2; the files that follow are not touched) */
           tmark("verified");
         }
-      if (!o->keep && Digest != 2) unlink(f->src);           /* (DEXGPU_DIGEST=only made nothing that could stand in for it) */
+      if (!o->keep && !LINES_ONLY) unlink(f->src);           /* (DEXGPU_DIGEST=only, DEXGPU_CENSUS=only made nothing that could stand in for it) */
     }
   free(f->root); free(f->pwd); free(f->src); free(f->dst);
   if (o->verbose)
@@ -834,6 +898,14 @@ int dex_tool_main(int tool, int argc, char *argv[])
         exit(1);
       }
   }
+  { const char *d = getenv("DEXGPU_CENSUS");              /* (the same rules) */
+    Census = d == NULL || *d == '\0' || o.pipe ? 0 : (strcmp(d, "only") == 0 ? 2 : atoi(d) != 0);
+    if (Census == 2 && !is_undex(tool))
+      { fprintf(stderr, "%s: DEXGPU_CENSUS=only counts what an image holds and writes nothing: that is for un%s; %s is there to write one\n",
+                Prog, Prog, Prog);
+        exit(1);
+      }
+  }
 
   tmark("start");
 #ifdef F_SETPIPE_SZ
@@ -846,7 +918,7 @@ int dex_tool_main(int tool, int argc, char *argv[])
       int    rc = NOT_MINE;
       size_t r;
       begin(&o, argv[i], &f);
-      if (Digest == 2) rc = read_input(&o, &f) == NOT_MINE ? DX_OK : DX_E_IO;     /* (no route: nothing is converted) */
+      if (LINES_ONLY) rc = read_input(&o, &f) == NOT_MINE ? DX_OK : DX_E_IO;     /* (no route: nothing is converted) */
       for (r = 0; r < sizeof(ROUTES) / sizeof(ROUTES[0]) && (rc == NOT_MINE || rc == DX_E_AGAIN); r++)
         { f.seek = 0;                                      /* (what a route that passed the file on has set) */
           rc = ROUTES[r](&o, &f);

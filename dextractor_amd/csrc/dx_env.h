@@ -2,7 +2,7 @@
  * dx_env.h -- the library's switches.
  *
  * What a user of the tools may set stands in the environment under a name of its own (README.md): DEXGPU_DEVICE, DEXGPU_DEVICES,
- * DEXGPU_TIMING, DEXGPU_TEARDOWN, DEXGPU_TEXT_BUDGET, DEXGPU_SCRATCH_BUDGET, DEXGPU_WALK_THREADS, DEXGPU_VERIFY, DEXGPU_DIGEST.  Everything else -- a route
+ * DEXGPU_TIMING, DEXGPU_TEARDOWN, DEXGPU_TEXT_BUDGET, DEXGPU_SCRATCH_BUDGET, DEXGPU_WALK_THREADS, DEXGPU_VERIFY, DEXGPU_DIGEST, DEXGPU_CENSUS.  Everything else -- a route
  * forced for a test, a threshold lowered so that a small file takes the large files' path, a failure injected -- is a key of ONE
  * variable, DEXGPU_TEST: keys and key=value pairs separated by commas or blanks, e.g.
  *     DEXGPU_TEST="no_tokens,onepass_groups=3,device_walk_min=1"

@@ -1,6 +1,6 @@
 /*
  * dx_file_check.c -- an image of any of the three kinds and the text it decodes to, for who wants the text's slices where they are
- * made: the round-trip check (dx_file_verify) and the digest (dx_file_digest).
+ * made: the round-trip check (dx_file_verify), the digest (dx_file_digest) and the census (dx_file_census).
  */
 #include <stdlib.h>
 #include <string.h>
@@ -397,5 +397,194 @@ done:
   if (g.d_arr) (void) dx_free(ctx, g.d_arr);
   image_close(&im);
   free(g.rec);
+  return rc;
+}
+
+/* ==========================================================================================
+ *  census (dx_file_census): what an image holds -- records, symbols, the shortest and the longest read, N50, the composition of the
+ *  2-bit kinds, the distribution of a .quiva's five lines -- for the day the text is gone.  dex2DB.c:587-595 / 793-797 count
+ *  the same on one core as reads enter a database (DAZZ_DB.freq, totlen, maxlen: 896-913).  A .dexta / .dexar image is walked and
+ *  uploaded, and its packed reads are counted where they lie (dx_code_counts): no text is made.  A .dexqv image is planned and decoded
+ *  as the digest does it, and a slice hook counts every entry's five lines where they are made (dx_byte_hist_ranges).
+ * ========================================================================================== */
+/* Two counting passes, the first over the lengths' high halves (how many, and their sum), the second over the low halves of the
+   lengths in the bucket in which the running sum, from the longest down, reaches half of the total. */
+int dx_census_lengths(const uint32_t *len, uint64_t n, dx_census *out)
+{ uint64_t *sumh, *cntl, total = 0, run = 0, i;
+  uint32_t  lo = UINT32_MAX, hi = 0, n50 = 0;
+  int       h, l;
+  if (out == NULL || (len == NULL && n)) return DX_E_ARG;
+  if ((sumh = calloc(2 * 65536, sizeof(*sumh))) == NULL) return DX_E_NOMEM;
+  cntl = sumh + 65536;
+  for (i = 0; i < n; i++)
+    { const uint32_t v = len[i];
+      sumh[v >> 16] += v; total += v;
+      if (v < lo) lo = v;
+      if (v > hi) hi = v;
+    }
+  if (total > 0)
+    { for (h = 65535; h > 0 && run + sumh[h] < total - (run + sumh[h]); h--) run += sumh[h];      /* (2 running >= total, without the doubling) */
+      for (i = 0; i < n; i++)
+        if ((len[i] >> 16) == (uint32_t) h) cntl[len[i] & 0xffffu] += 1;
+      for (l = 65535; l >= 0; l--)                        /* the reads of one length together: the sum reaches half with one of them or with none */
+        { const uint64_t v = ((uint64_t) h << 16) | (uint64_t) l;
+          run += cntl[l] * v;
+          if (cntl[l] != 0 && run >= total - run) { n50 = (uint32_t) v; break; }
+        }
+    }
+  free(sumh);
+  out->records = n; out->symbols = total;
+  out->min_len = n ? lo : 0; out->max_len = hi; out->n50 = n50; out->reserved = 0;
+  return DX_OK;
+}
+
+/* how much of a 2-bit image of m bytes the device takes at once beside 48 bytes of arrays a record: 0 = all of it.  DEXGPU_TEXT_BUDGET
+   counts bytes of image here (there is no text) */
+static size_t census_cap(dx_ctx *ctx, size_t m, uint64_t units)
+{ uint64_t fr = 0, all = 0;
+  size_t   cap;
+  if (dxf_budget_env(m, 4096u, &cap)) return cap;
+  if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
+  if ((double) m + 48.0 * (double) units <= 0.9 * (double) fr) return 0;
+  { const double room = (0.9 * (double) fr) / 2.0;
+    return room > (double) ((size_t) 4 << 20) ? (size_t) room : (size_t) 4 << 20;
+  }
+}
+
+static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
+
+/* a slice of whole records from i0 on: as many as span at most `cap` bytes of image, and one at least; cap 0: all that are left */
+static uint64_t u2_slice_end(const u2_index *x, uint64_t i0, size_t cap)
+{ uint64_t i1 = i0 + 1;
+  if (cap == 0) return x->cnt;
+  while (i1 < x->cnt && u2_end(x, i1) - x->ioff[i0] <= cap) i1++;
+  return i1;
+}
+
+/* the packed reads of a walked image, slice by slice of whole records: code[4] and, when wanted, every record's four counts */
+static int census_pack2(dx_ctx *ctx, const uint8_t *img, const u2_index *x, size_t cap, uint64_t code[4], uint32_t *rec)
+{ const uint64_t cnt = x->cnt;
+  uint64_t *rel = NULL, i, i0, i1, most = 0, tot[4];
+  size_t    smax = 0, in_cap = 0, arr_cap = 0;
+  void     *d_in = NULL, *d_arr = NULL;
+  int       rc = DX_OK;
+  for (i0 = 0; i0 < cnt; i0 = i1)                         /* the largest slice: one allocation serves them all */
+    { i1 = u2_slice_end(x, i0, cap);
+      if (u2_end(x, i1 - 1) - x->ioff[i0] > smax) smax = (size_t) (u2_end(x, i1 - 1) - x->ioff[i0]);
+      if (i1 - i0 > most) most = i1 - i0;
+    }
+  if ((rel = malloc((most + 1) * sizeof(*rel))) == NULL) return DX_E_NOMEM;
+  TRY(dgrow(ctx, &d_in, &in_cap, smax + 64));
+  TRY(dgrow(ctx, &d_arr, &arr_cap, (size_t) most * 28 + 64));          /* offsets (8), symbols (4), counts (16) */
+  for (i0 = 0; i0 < cnt; i0 = i1)
+    { const uint64_t b0 = x->ioff[i0];
+      uint64_t *d_boff = d_arr;
+      uint32_t *d_cnt, *d_len;
+      i1 = u2_slice_end(x, i0, cap);
+      d_cnt = (uint32_t *) (d_boff + most); d_len = d_cnt + 4 * most;
+      for (i = i0; i < i1; i++) rel[i - i0] = x->ioff[i] - b0;
+      TRY(dx_h2d(ctx, d_in, img + b0, (size_t) (u2_end(x, i1 - 1) - b0)));
+      TRY(dx_h2d(ctx, d_boff, rel, (size_t) (i1 - i0) * 8));
+      TRY(dx_h2d(ctx, d_len, x->nsym + i0, (size_t) (i1 - i0) * 4));
+      TRY(dx_code_counts(ctx, d_in, u2_end(x, i1 - 1) - b0, d_boff, NULL, d_len, i1 - i0, rec ? d_cnt : NULL, tot, NULL));
+      if (rec != NULL) TRY(dx_d2h(ctx, rec + 4 * i0, d_cnt, (size_t) (i1 - i0) * 16));
+      for (i = 0; i < 4; i++) code[i] += tot[i];
+    }
+done:
+  if (d_in) (void) dx_free(ctx, d_in);
+  if (d_arr) (void) dx_free(ctx, d_arr);
+  free(rel);
+  return rc;
+}
+
+typedef struct
+  { dx_ctx          *ctx;
+    const hdr_patch *h;                            /* the decoded text's layout */
+    const uint32_t  *len;                          /* every entry's symbols a line */
+    void            *d_arr;   size_t arr_cap;      /* device: a slice's unit arrays */
+    uint64_t       (*hist)[256];                   /* five tables, of the slices so far */
+    uint64_t        *rec;                          /* every record's five sums, when wanted */
+  } census_job;
+
+/* a slice of decoded text, entries [i0, i1): per entry five ranges, its lines without their newlines, kinds 0 .. 4 */
+static int census_slice(void *arg, const void *d_out, uint64_t i0, uint64_t i1, size_t t0, size_t bytes)
+{ census_job *c = arg;
+  const uint64_t m = i1 - i0;
+  uint64_t *off, *ln, k, hs[5][256];
+  uint8_t  *kd;
+  int       rc, q;
+  if ((rc = dgrow(c->ctx, &c->d_arr, &c->arr_cap, (size_t) m * 125 + 64)) != DX_OK) return rc;       /* off, len, sum (40 each), kind (5) */
+  if ((off = malloc((size_t) m * 85 + 64)) == NULL) return DX_E_NOMEM;
+  ln = off + 5 * m; kd = (uint8_t *) (ln + 5 * m);
+  for (k = 0; k < m; k++)
+    for (q = 0; q < 5; q++)
+      { off[5*k + q] = c->h->ooff[i0 + k] - t0 + (uint64_t) q * ((uint64_t) c->len[i0 + k] + 1);
+        ln[5*k + q]  = c->len[i0 + k];
+        kd[5*k + q]  = (uint8_t) q;
+      }
+  { uint64_t *d_off = c->d_arr, *d_len = d_off + 5 * m, *d_sum = d_len + 5 * m;
+    uint8_t  *d_kind = (uint8_t *) (d_sum + 5 * m);
+    rc = dx_h2d(c->ctx, d_off, off, (size_t) m * 80);
+    if (rc == DX_OK) rc = dx_h2d(c->ctx, d_kind, kd, (size_t) m * 5);
+    free(off);
+    if (rc != DX_OK) return rc;
+    if ((rc = dx_byte_hist_ranges(c->ctx, d_out, bytes, d_off, d_len, d_kind, 5, 5 * m, c->rec ? d_sum : NULL, &hs[0][0], NULL)) != DX_OK) return rc;
+    if (c->rec != NULL && (rc = dx_d2h(c->ctx, c->rec + 5 * i0, d_sum, (size_t) m * 40)) != DX_OK) return rc;
+  }
+  for (q = 0; q < 5; q++)
+    for (k = 0; k < 256; k++) c->hist[q][k] += hs[q][k];
+  return DX_OK;
+}
+
+int dx_file_census(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, dx_census *out, uint32_t **rec_len, uint32_t **rec_code, uint64_t **rec_sum)
+{ image_text  im;
+  dx_census  *cs = NULL;
+  uint32_t   *rl = NULL, *rcode = NULL;
+  uint64_t   *rsum = NULL, cnt;
+  const uint32_t *lens;
+  int         rc;
+
+  if (ctx == NULL || img == NULL || out == NULL) return DX_E_ARG;
+  if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW && kind != DX_KIND_QUIVA) return DX_E_ARG;
+  if (rec_len) *rec_len = NULL;
+  if (rec_code) *rec_code = NULL;
+  if (rec_sum) *rec_sum = NULL;
+
+  TRY(image_open(ctx, kind, 0, 1, img, m, &im));          /* (the tag line in lower case; the line width lays out a text nobody makes) */
+  cnt  = im.h.n;
+  lens = kind == DX_KIND_QUIVA ? im.plan->x.len : im.ux.nsym;
+  if ((cs = calloc(1, sizeof(*cs))) == NULL) { rc = DX_E_NOMEM; goto done; }
+  TRY(dx_census_lengths(lens, cnt, cs));
+  if (rec_len != NULL)
+    { if ((rl = malloc((cnt + 1) * sizeof(*rl))) == NULL) { rc = DX_E_NOMEM; goto done; }
+      if (cnt) memcpy(rl, lens, cnt * sizeof(*rl));
+    }
+  if (kind != DX_KIND_QUIVA)
+    { if (rec_code != NULL && (rcode = malloc((cnt + 1) * 4 * sizeof(*rcode))) == NULL) { rc = DX_E_NOMEM; goto done; }
+      if (cnt > 0) TRY(census_pack2(ctx, img, &im.ux, census_cap(ctx, m, cnt), cs->code, rcode));
+    }
+  else
+    { census_job c;
+      memset(&c, 0, sizeof(c));
+      c.ctx = ctx; c.h = &im.h; c.len = lens; c.hist = cs->hist;
+      if (rec_sum != NULL && (rsum = malloc((cnt + 1) * 5 * sizeof(*rsum))) == NULL) { rc = DX_E_NOMEM; goto done; }
+      c.rec = rsum;
+      if (cnt > 0)
+        { int whole_in = 1;
+          const size_t cap = dxf_undexqv_cap(ctx, im.plan, &whole_in);
+          rc = image_slices(ctx, &im, cap, whole_in, census_slice, &c);
+        }
+      if (c.d_arr) (void) dx_free(ctx, c.d_arr);
+      if (rc != DX_OK) goto done;
+    }
+  *out = *cs;
+  if (rec_len)  { *rec_len = rl; rl = NULL; }
+  if (rec_code) { *rec_code = rcode; rcode = NULL; }
+  if (rec_sum)  { *rec_sum = rsum; rsum = NULL; }
+  rc = DX_OK;
+
+done:
+  image_close(&im);
+  free(cs); free(rl); free(rcode); free(rsum);
   return rc;
 }

@@ -4,7 +4,7 @@
  *     dx_files.c       what every driver uses, and the decoded text on its way out (header lines laid over it, slices of it)
  *     dx_file_pack2.c  dexta / dexar (whole, streamed, sharded), undexta / undexar
  *     dx_file_qv.c     dexqv (whole, sliced, sharded), undexqv plan / run
- *     dx_file_check.c  an image of any kind and its text where it is made: dx_file_verify, dx_file_digest
+ *     dx_file_check.c  an image of any kind and its text where it is made: dx_file_verify, dx_file_digest, dx_file_census
  *     dx_select.c      the .qvs entry API, the .bps / .arw read loader
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.

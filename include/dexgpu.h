@@ -588,6 +588,52 @@ int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int uppe
 int dx_file_text_options(int kind, const uint8_t *text, size_t n, int *upper, uint32_t *width);
 
 /* ------------------------------------------------------------------------------------------
+ *  census: what an archive holds, counted where it lies  (dex2DB.c:587-595, 793-797, 896-913 count this on one core)
+ * ------------------------------------------------------------------------------------------ */
+/* The composition of packed reads (csrc/census/dx_census.hip).  Unit j is what it is for dx_reads_unpack: symbols [d_beg[j], d_beg[j] +
+ * d_len[j]) of the packed read that starts at d_in + d_boff[j], any byte offset, any phase, d_beg == NULL: all 0.  d_counts[4 j + c]
+ * (may be NULL) = how many of the unit's symbols have code c, total[c] (host; may be NULL) = the sum over the call's units.  The pad
+ * bits of a read's last byte and the symbols in front of d_beg[j] are not counted; units may overlap or repeat; nothing is decoded,
+ * and nothing outside [0, in_bytes) is read.  Bad units are dx_reads_unpack's: DX_E_FORMAT with *bad_unit = the smallest such j
+ * (UINT64_MAX otherwise; may be NULL), checked by the kernel, one read-back a call (the totals come with it).  n < 2^31.
+ * On a .bps / .arw payload with DAZZ_READ.boff / .rlen the totals are DAZZ_DB.freq (times totlen), for any selection of reads.   */
+int dx_code_counts(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                   const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                   uint32_t *d_counts /* n x 4, may be NULL */, uint64_t total[4] /* host */, uint64_t *bad_unit /* may be NULL */);
+
+/* Byte-value histograms and byte sums of n ranges of a device buffer: range j = d_buf[d_off[j] .. d_off[j] + d_len[j]) adds its
+ * bytes' values to table d_kind[j] (d_kind == NULL: all 0) of the nkinds (1 to 8) tables of hist (host, nkinds x 256; may be
+ * NULL), and d_sum[j] (may be NULL) = the sum of its bytes.  Offsets of any alignment, lengths from 0 up, ranges may overlap or
+ * repeat (dx_crc32_ranges' conventions).  DX_E_FORMAT with *bad_unit = the smallest j whose range does not lie inside
+ * [0, buf_bytes) or whose kind is not below nkinds (UINT64_MAX otherwise; may be NULL); one read-back a call.  n < 2^31.       */
+int dx_byte_hist_ranges(dx_ctx *ctx, const uint8_t *d_buf, uint64_t buf_bytes, const uint64_t *d_off, const uint64_t *d_len,
+                        const uint8_t *d_kind /* NULL: all 0 */, int nkinds /* 1..8 */, uint64_t n,
+                        uint64_t *d_sum /* n, may be NULL */, uint64_t *hist /* host, nkinds x 256 */, uint64_t *bad_unit);
+
+typedef struct
+  { uint64_t records, symbols;
+    uint32_t min_len, max_len, n50, reserved;    /* all 0 for an image without records */
+    uint64_t code[4];                            /* fasta: a c g t; arrow: 1 2 3 4; quiva: zeros */
+    uint64_t hist[5][256];                       /* quiva: byte values of the del, tag, ins, mrg, sub lines as undexqv (no -U) writes them, newlines not counted; 2-bit kinds: zeros */
+  } dx_census;
+
+/* host only: records, symbols, min_len, max_len and n50 of n lengths (the other fields of *out are left as they are).  N50: over the
+ * lengths sorted downward, the length at which the running sum first reaches half of the total (2 * running >= symbols); 0 without
+ * symbols.  Two counting passes, no sort.                                                                                       */
+int dx_census_lengths(const uint32_t *len, uint64_t n, dx_census *out);
+
+/* The census of a .dexta / .dexar / .dexqv image (kind DX_KIND_*).  fasta / arrow: the image is walked as dx_file_unpack2 walks it,
+ * uploaded, and the packed reads counted where they lie (dx_code_counts): no text is made.  quiva: the image is planned and decoded
+ * as dx_file_digest does it, slice by slice, and every entry's five lines are counted where they are made (dx_byte_hist_ranges,
+ * kinds 0..4; the tag line in lower case): the text is never downloaded.  An image that does not fit the device (or exceeds
+ * DEXGPU_TEXT_BUDGET: bytes of image for the 2-bit kinds, bytes of text for quiva) goes in slices of whole records.
+ * The optional results are malloc'd (dx_file_free): *rec_len = every record's symbols; *rec_code (2-bit kinds; n x 4) = its symbols
+ * code by code; *rec_sum (quiva; n x 5) = the byte sums of its five lines.  One that does not apply to the kind comes back NULL.
+ * Errors are those of dx_file_unpack2 / dx_file_undexqv for the same image; *out is then untouched.                             */
+int dx_file_census(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, dx_census *out,
+                   uint32_t **rec_len, uint32_t **rec_code /* n x 4; 2-bit kinds */, uint64_t **rec_sum /* n x 5; quiva */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
