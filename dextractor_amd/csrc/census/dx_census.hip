@@ -45,12 +45,9 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in
 // the profiler's name table and are timed with events on the context's stream (tools/census_rate.py).
-#include "dx_internal.hpp"
-#include "dx_device.hpp"
+#include "units/dx_units.hpp"
 
 #define CC_BATCH    16u                    // units a ticket at least (k_ticket_units: more of short ones)
-#define CC_GROUP    16u                    // lanes that take a short unit together
-#define CC_LEN_MAX  0x7fffffffu            // symbols a unit (DAZZ_READ.rlen is an int), as for dx_reads_unpack
 #define CC_EVEN     0x55555555u
 #define CC_EVEN64   0x5555555555555555ull
 
@@ -58,20 +55,6 @@
 #define HS_WAVE_MIN 512u                   // ranges from here on take the whole wave
 #define HS_FLUSH    (1ull << 29)           // bytes a wave counts between two sweeps of the workgroup's counters
 #define HS_KINDS    8
-
-// the words of the scratch block both entry points use: ticket (2 x 32 bits), bad unit, 16 bytes of padded input, the answer
-#define CW_TICKET 0
-#define CW_BAD    1
-#define CW_PAD    2
-#define CW_OUT    4
-
-// ---------------------------------------------------------------------------------------------
-//  16 bytes at byte `a` of a buffer of `bytes` >= 16: its last 16 when they would reach past its end
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t cw_from(uint64_t a, uint64_t bytes) { return a + 16u > bytes ? bytes - 16u : a; }
-
-__device__ __forceinline__ u32x4 cw_ask(const uint8_t *in, uint64_t bytes, uint64_t a)
-{ return *(const u32x4_u *) (in + cw_from(a, bytes)); }
 
 // ---------------------------------------------------------------------------------------------
 //  k_code_counts
@@ -88,10 +71,10 @@ __device__ __forceinline__ void cc_word(cc_acc &c, uint32_t w, int lo, int hi)
   c.nh += __popc(h); c.nl += __popc(l); c.nb += __popc(h & l); c.nv += __popc(m);
 }
 
-// The chunk whose place is byte `a` of the buffer (v: what cw_ask gave for it): its symbols that are symbols [S0, S1) of the
+// The chunk whose place is byte `a` of the buffer (v: what last16_ask gave for it): its symbols that are symbols [S0, S1) of the
 // buffer (symbol 4 x + t: byte x, bits 7 - 2t, 6 - 2t).
 __device__ __forceinline__ void cc_chunk(cc_acc &c, const u32x4 &v, uint64_t bytes, uint64_t a, uint64_t S0, uint64_t S1)
-{ const uint64_t from = cw_from(a, bytes);
+{ const uint64_t from = last16_from(a, bytes);
   if (from == a && S0 <= 4u * a && 4u * a + 64u <= S1)
     { const uint64_t x = v.x | ((uint64_t) v.y << 32), y = v.z | ((uint64_t) v.w << 32);
       const uint64_t hx = (x >> 1) & CC_EVEN64, lx = x & CC_EVEN64, hy = (y >> 1) & CC_EVEN64, ly = y & CC_EVEN64;
@@ -106,15 +89,6 @@ __device__ __forceinline__ void cc_chunk(cc_acc &c, const u32x4 &v, uint64_t byt
   cc_word(c, __builtin_bswap32(v.y), lo - 16, hi - 16);
   cc_word(c, __builtin_bswap32(v.z), lo - 32, hi - 32);
   cc_word(c, __builtin_bswap32(v.w), lo - 48, hi - 48);
-}
-
-// the sum along a row of 16 lanes, in the row's last lane (the first four steps of wave_incl_scan)
-__device__ __forceinline__ uint32_t row_sum(uint32_t v)
-{ v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xf, 0xf, true);
-  return v;
 }
 
 __device__ __forceinline__ u32x4 cc_codes(uint32_t nh, uint32_t nl, uint32_t nb, uint32_t nv)
@@ -135,74 +109,57 @@ void k_code_counts(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t b
   if (threadIdx.x < 4u) s_tot[threadIdx.x] = 0ull;
   __syncthreads();
 
-  const uint32_t lane = (uint32_t) lane_id(), grp = lane / CC_GROUP, sub = lane % CC_GROUP;
+  const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP;
   uint64_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;                 // what this lane has stored, code by code
-  const uint32_t TB = ticket_units_of(ticket, CC_BATCH);
-  for (uint64_t r0 = next_unit(ticket, TB), nxt; r0 < n; r0 = nxt)
-  { nxt = next_unit(ticket, TB);                           // drawn early: hidden behind these units
-    const uint64_t r1 = r0 + TB < n ? r0 + TB : n;
-    for (uint64_t u0 = r0; u0 < r1; u0 += 64u)
+  units_rounds<true>(ticket, ticket_units_of(ticket, CC_BATCH), n, [&](uint64_t u0, uint64_t r1)
     { // unit u0 + lane is this lane's to read and to check
-      const uint64_t i = u0 + lane;
+      const uint64_t    i  = u0 + lane;
+      const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
       uint64_t S0 = 0, S1 = 0, a0 = 0;                     // its symbols in the buffer; its first chunk's place
       uint32_t nch = 0;                                    // its chunks
-      bool ok = false;
-      if (i < r1)
-        { const uint64_t at = boff[i];
-          const uint32_t b = beg != NULL ? beg[i] : 0u, L = len[i];
-          ok = at <= bound && L <= CC_LEN_MAX && (L == 0u || (((uint64_t) b + L - 1u) >> 2) < bound - at);
-          if (!ok) atomicMin(bad, (unsigned long long) i);
-          else if (L != 0u)
-            { S0 = 4u * at + b; S1 = S0 + L;
-              a0 = (S0 >> 2) & ~15ull;
-              nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-            }
+      if (pu.ok && pu.len != 0u)
+        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
+          a0 = (S0 >> 2) & ~15ull;
+          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
         }
-      const uint64_t briefs = __ballot(ok && nch > 1u && nch <= CC_GROUP);
-      uint64_t       longs  = __ballot(ok && nch > CC_GROUP);
 
       // no symbol, or one chunk: the lane's own
-      if (ok && nch <= 1u)
+      if (pu.ok && nch <= 1u)
         { cc_acc c = { 0u, 0u, 0u, 0u };
-          if (nch) cc_chunk(c, cw_ask(in, in_bytes, a0), in_bytes, a0, S0, S1);
+          if (nch) cc_chunk(c, last16_ask(in, in_bytes, a0), in_bytes, a0, S0, S1);
           const u32x4 r = cc_codes(c.nh, c.nl, c.nb, c.nv);
           if (counts != NULL) *(u32x4_u *) (counts + 4u * i) = r;
           t0 += r.x; t1 += r.y; t2 += r.z; t3 += r.w;
         }
 
-      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      for (uint32_t k = 0; k < 64u; k += 64u / CC_GROUP)
-        if ((briefs >> k) & ((1ull << (64u / CC_GROUP)) - 1u))
-          { const int from = (int) (k + grp);
-            const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from);
-            const uint32_t gn  = __shfl(nch, from);
-            const bool mine = ((briefs >> from) & 1ull) != 0ull;
-            cc_acc c = { 0u, 0u, 0u, 0u };
-            if (mine && sub < gn)
-              { const uint64_t a = ga0 + 16u * sub;
-                cc_chunk(c, cw_ask(in, in_bytes, a), in_bytes, a, gS0, gS1);
-              }
-            const uint32_t nh = row_sum(c.nh), nl = row_sum(c.nl), nb = row_sum(c.nb), nv = row_sum(c.nv);
-            if (mine && sub == CC_GROUP - 1u)
-              { const u32x4 r = cc_codes(nh, nl, nb, nv);
-                if (counts != NULL) *(u32x4_u *) (counts + 4u * (u0 + (uint64_t) from)) = r;
-                t0 += r.x; t1 += r.y; t2 += r.z; t3 += r.w;
-              }
-          }
+      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each, the group's counts summed along its row
+      units_by_fours(__ballot(pu.ok && nch > 1u && nch <= UNITS_GROUP), [&](int from, bool mine)
+        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from);
+          const uint32_t gn  = __shfl(nch, from);
+          cc_acc c = { 0u, 0u, 0u, 0u };
+          if (mine && sub < gn)
+            { const uint64_t a = ga0 + 16u * sub;
+              cc_chunk(c, last16_ask(in, in_bytes, a), in_bytes, a, gS0, gS1);
+            }
+          const uint32_t nh = row_sum(c.nh), nl = row_sum(c.nl), nb = row_sum(c.nb), nv = row_sum(c.nv);
+          if (mine && sub == UNITS_GROUP - 1u)
+            { const u32x4 r = cc_codes(nh, nl, nb, nv);
+              if (counts != NULL) *(u32x4_u *) (counts + 4u * (u0 + (uint64_t) from)) = r;
+              t0 += r.x; t1 += r.y; t2 += r.z; t3 += r.w;
+            }
+        });
 
       // the others: the whole wave, 1 KiB a step.  A step's bytes are asked for a step before they are counted (behind the
-      // unit cw_ask gives the buffer's last 16 bytes: asked for, never counted), in a register of their own: nothing but the
+      // unit last16_ask gives the buffer's last 16 bytes: asked for, never counted), in a register of their own: nothing but the
       // loads is under way, so the wait in front of the counting is for all but the youngest of them.
-      while (longs)
-        { const int from = __ffsll((unsigned long long) longs) - 1;
-          longs &= longs - 1u;
-          const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
+      units_each(__ballot(pu.ok && nch > UNITS_GROUP), [&](int from)
+        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
           const uint32_t wn  = uniform(__shfl(nch, from));
           cc_acc c = { 0u, 0u, 0u, 0u };
-          u32x4 cur = cw_ask(in, in_bytes, wa0 + 16u * lane);
+          u32x4 cur = last16_ask(in, in_bytes, wa0 + 16u * lane);
           for (uint32_t base = 0; base < wn; base += 64u)
             { const uint32_t j = base + lane;
-              const u32x4 ahead = cw_ask(in, in_bytes, wa0 + 16ull * (j + 64u));
+              const u32x4 ahead = last16_ask(in, in_bytes, wa0 + 16ull * (j + 64u));
               if (j < wn) cc_chunk(c, cur, in_bytes, wa0 + 16ull * j, wS0, wS1);
               cur = ahead;
             }
@@ -212,9 +169,8 @@ void k_code_counts(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t b
               if (counts != NULL) *(u32x4_u *) (counts + 4u * (u0 + (uint64_t) from)) = r;
               t0 += r.x; t1 += r.y; t2 += r.z; t3 += r.w;
             }
-        }
-    }
-  }
+        });
+    });
 
   if (t0) atomicAdd(&s_tot[0], (unsigned long long) t0);
   if (t1) atomicAdd(&s_tot[1], (unsigned long long) t1);
@@ -244,10 +200,10 @@ __device__ __forceinline__ uint32_t hs_part(uint32_t *tab, uint32_t w, int lo, i
   return w & (uint32_t) (((1ull << (8 * hi)) - 1u) & ~((1ull << (8 * lo)) - 1u));
 }
 
-// The chunk whose place is byte `a` of the buffer (v: what cw_ask gave for it): its bytes that are bytes [B0, B1) of the buffer are
+// The chunk whose place is byte `a` of the buffer (v: what last16_ask gave for it): its bytes that are bytes [B0, B1) of the buffer are
 // counted; their sum comes back.
 __device__ __forceinline__ uint32_t hs_chunk(uint32_t *tab, u32x4 v, uint64_t bytes, uint64_t a, uint64_t B0, uint64_t B1)
-{ const uint64_t from = cw_from(a, bytes);
+{ const uint64_t from = last16_from(a, bytes);
   if (!(from == a && B0 <= a && a + 16u <= B1))
     { const uint64_t b0 = B0 > a ? B0 : a, b1 = B1 < a + 16u ? B1 : a + 16u;
       if (b1 <= b0) return 0u;
@@ -290,61 +246,55 @@ void k_byte_hist(const uint8_t *__restrict__ buf, uint64_t buf_bytes, uint64_t b
   const uint32_t lane = (uint32_t) lane_id();
   uint32_t *copy = s_bins + (lane & (HS_COPIES - 1u));
   uint64_t  counted = 0;                                   // bytes this wave has counted since it last swept
-  for (uint64_t r0 = next_unit(ticket, per_ticket); r0 < n; r0 = next_unit(ticket, per_ticket))
-    { const uint64_t r1 = r0 + per_ticket < n ? r0 + per_ticket : n;
-      for (uint64_t u0 = r0; u0 < r1; u0 += 64u)
-        { const uint64_t i = u0 + lane;
-          uint64_t B0 = 0, L = 0;
-          uint32_t kd = 0;
-          int      how = 0;                  // 1: this lane's, 2: the wave's
-          if (i < r1)
-            { B0 = off[i]; L = len[i];
-              kd = kind != NULL ? kind[i] : 0u;
-              if (B0 <= bound && L <= bound - B0 && kd < nkinds) how = L < HS_WAVE_MIN ? 1 : 2;
-              else atomicMin(bad, (unsigned long long) i);
-            }
-          // the short ones: chunk after chunk from the boundary in front of the range on, the lanes side by side
-          { const uint64_t a0 = B0 & ~15ull;
-            const uint32_t nch = how == 1 && L ? (uint32_t) (((B0 + L - 1u - a0) >> 4) + 1u) : 0u;
-            uint32_t *tab = copy + 256u * HS_COPIES * kd;
-            uint32_t  s = 0;
-            for (uint32_t j = 0; j < nch; j++)
-              s += hs_chunk(tab, cw_ask(buf, buf_bytes, a0 + 16u * j), buf_bytes, a0 + 16u * j, B0, B0 + L);
-            if (how == 1 && sum != NULL) sum[i] = s;
-            counted += wave_sum(how == 1 ? (uint32_t) L : 0u);
-          }
-          // the others: the whole wave, 1 KiB a step, the next step's bytes asked for before this step's are counted
-          uint64_t longs = __ballot(how == 2);
-          while (longs)
-            { const int from = __ffsll((unsigned long long) longs) - 1;
-              longs &= longs - 1u;
-              const uint64_t wB0 = uniform64(__shfl(B0, from)), wL = uniform64(__shfl(L, from));
-              const uint32_t wk  = uniform(__shfl(kd, from));
-              const uint64_t wa0 = wB0 & ~15ull, wn = ((wB0 + wL - 1u - wa0) >> 4) + 1u;
-              uint32_t *tab = copy + 256u * HS_COPIES * wk;
-              uint64_t  s = 0;
-              u32x4 cur = cw_ask(buf, buf_bytes, wa0 + 16u * lane);
-              for (uint64_t base = 0; base < wn; base += 64u)
-                { const uint64_t j = base + lane;
-                  const u32x4 ahead = cw_ask(buf, buf_bytes, wa0 + 16u * (j + 64u));
-                  if (j < wn) s += hs_chunk(tab, cur, buf_bytes, wa0 + 16u * j, wB0, wB0 + wL);
-                  cur = ahead;
-                  counted += DX_STEP;
-                  if (counted >= flush_at)
-                    { hs_sweep(s_bins, nbins, hist, lane);
-                      counted = 0;
-                    }
-                }
-              #pragma unroll
-              for (int d = 32; d > 0; d >>= 1) s += __shfl_xor((unsigned long long) s, d);
-              if (lane == 0u && sum != NULL) sum[u0 + (uint64_t) from] = s;
-            }
-          if (counted >= flush_at)
-            { hs_sweep(s_bins, nbins, hist, lane);
-              counted = 0;
-            }
+  units_rounds<false>(ticket, per_ticket, n, [&](uint64_t u0, uint64_t r1)
+    { const uint64_t i = u0 + lane;
+      uint64_t B0 = 0, L = 0;
+      uint32_t kd = 0;
+      int      how = 0;                      // 1: this lane's, 2: the wave's
+      if (i < r1)
+        { B0 = off[i]; L = len[i];
+          kd = kind != NULL ? kind[i] : 0u;
+          if (range_ok(B0, L, bound) && kd < nkinds) how = L < HS_WAVE_MIN ? 1 : 2;
+          else atomicMin(bad, (unsigned long long) i);
         }
-    }
+      // the short ones: chunk after chunk from the boundary in front of the range on, the lanes side by side
+      { const uint64_t a0 = B0 & ~15ull;
+        const uint32_t nch = how == 1 && L ? (uint32_t) (((B0 + L - 1u - a0) >> 4) + 1u) : 0u;
+        uint32_t *tab = copy + 256u * HS_COPIES * kd;
+        uint32_t  s = 0;
+        for (uint32_t j = 0; j < nch; j++)
+          s += hs_chunk(tab, last16_ask(buf, buf_bytes, a0 + 16u * j), buf_bytes, a0 + 16u * j, B0, B0 + L);
+        if (how == 1 && sum != NULL) sum[i] = s;
+        counted += wave_sum(how == 1 ? (uint32_t) L : 0u);
+      }
+      // the others: the whole wave, 1 KiB a step, the next step's bytes asked for before this step's are counted
+      units_each(__ballot(how == 2), [&](int from)
+        { const uint64_t wB0 = uniform64(__shfl(B0, from)), wL = uniform64(__shfl(L, from));
+          const uint32_t wk  = uniform(__shfl(kd, from));
+          const uint64_t wa0 = wB0 & ~15ull, wn = ((wB0 + wL - 1u - wa0) >> 4) + 1u;
+          uint32_t *tab = copy + 256u * HS_COPIES * wk;
+          uint64_t  s = 0;
+          u32x4 cur = last16_ask(buf, buf_bytes, wa0 + 16u * lane);
+          for (uint64_t base = 0; base < wn; base += 64u)
+            { const uint64_t j = base + lane;
+              const u32x4 ahead = last16_ask(buf, buf_bytes, wa0 + 16u * (j + 64u));
+              if (j < wn) s += hs_chunk(tab, cur, buf_bytes, wa0 + 16u * j, wB0, wB0 + wL);
+              cur = ahead;
+              counted += DX_STEP;
+              if (counted >= flush_at)
+                { hs_sweep(s_bins, nbins, hist, lane);
+                  counted = 0;
+                }
+            }
+          #pragma unroll
+          for (int d = 32; d > 0; d >>= 1) s += __shfl_xor((unsigned long long) s, d);
+          if (lane == 0u && sum != NULL) sum[u0 + (uint64_t) from] = s;
+        });
+      if (counted >= flush_at)
+        { hs_sweep(s_bins, nbins, hist, lane);
+          counted = 0;
+        }
+    });
 
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < nbins; b += DX_BLOCK)
@@ -358,19 +308,6 @@ void k_byte_hist(const uint8_t *__restrict__ buf, uint64_t buf_bytes, uint64_t b
 // ---------------------------------------------------------------------------------------------
 //  the entry points
 // ---------------------------------------------------------------------------------------------
-// The scratch block zeroed, its bad-unit word all ones, and an input of fewer than 16 bytes copied into its 16 padded ones.
-static int cw_begin(dx_ctx *ctx, size_t out_words, uint64_t **d_w, const uint8_t **d_in, uint64_t *in_bytes)
-{ int rc = dx_scratch(ctx, (CW_OUT + out_words) * 8u, (void **) d_w);
-  if (rc != DX_OK) return rc;
-  DX_HIP(ctx, hipMemsetAsync(*d_w, 0, (CW_OUT + out_words) * 8u, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(*d_w + CW_BAD, 0xff, 8, ctx->stream));
-  if (*in_bytes < 16u)
-    { if (*in_bytes) DX_HIP(ctx, hipMemcpyAsync(*d_w + CW_PAD, *d_in, *in_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-      *d_in = (const uint8_t *) (*d_w + CW_PAD); *in_bytes = 16u;
-    }
-  return DX_OK;
-}
-
 extern "C" int dx_code_counts(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
                               const uint64_t *d_boff, const uint32_t *d_beg, const uint32_t *d_len, uint64_t n,
                               uint32_t *d_counts, uint64_t total[4], uint64_t *bad_unit)
@@ -378,34 +315,20 @@ extern "C" int dx_code_counts(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_byte
   if (bad_unit) *bad_unit = UINT64_MAX;
   if (total) total[0] = total[1] = total[2] = total[3] = 0;
   if (n == 0) return DX_OK;
-  if (n >= (1ull << 31))
-    return dx_fail(ctx, DX_E_ARG, "dx_code_counts: more than 2^31 - 1 units in one batch");
-  if (!d_boff || !d_len || (!d_in && in_bytes))
-    return dx_fail(ctx, DX_E_ARG, "dx_code_counts: NULL device pointer");
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_after_pending(ctx);
+  units_frame    f;
+  uint64_t       back[UF_OUT + 4];
+  const uint64_t bound = in_bytes;                         // (the kernel loads 16 bytes at a time: fewer are copied, zeros behind them)
+  int rc = units_begin(ctx, "dx_code_counts", n, d_boff && d_len && (d_in || !in_bytes), ctx->d_u64 + DXW_UNITS, 4, 16, &d_in, &in_bytes, &f);
   if (rc != DX_OK) return rc;
-
-  uint64_t *d_w, back[CW_OUT + 4];
-  const uint64_t bound = in_bytes;
-  if ((rc = cw_begin(ctx, 4, &d_w, &d_in, &in_bytes)) != DX_OK) return rc;
-  uint32_t *d_ticket = (uint32_t *) (d_w + CW_TICKET);
   // (units per ticket from the packed bytes' extent, about 40 kB a ticket: units that do not stand in the buffer's order give a
   //  figure that means nothing, and the bounds of ticket_units_of hold)
   hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     CC_BATCH * 2500u, CC_BATCH, d_ticket);
+                     CC_BATCH * 2500u, CC_BATCH, f.ticket);
   hipLaunchKernelGGL(k_code_counts, dim3(dx_grid_waves(ctx, n, 32)), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound,
-                     d_boff, d_beg, d_len, n, d_counts, (unsigned long long *) (d_w + CW_OUT), (unsigned long long *) (d_w + CW_BAD), d_ticket);
-  DX_HIP(ctx, hipGetLastError());
-  DX_HIP(ctx, hipMemcpyAsync(back, d_w, sizeof(back), hipMemcpyDeviceToHost, ctx->stream));
-  DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (back[CW_BAD] != UINT64_MAX)
-    { if (bad_unit) *bad_unit = back[CW_BAD];
-      return dx_fail(ctx, DX_E_FORMAT, "dx_code_counts: unit %llu does not lie inside the %llu packed bytes",
-                     (unsigned long long) back[CW_BAD], (unsigned long long) bound);
-    }
-  if (total) memcpy(total, back + CW_OUT, 32);
-  return DX_OK;
+                     d_boff, d_beg, d_len, n, d_counts, f.out, f.bad, f.ticket);
+  rc = units_end(ctx, f, back, bad_unit, "%s: unit %llu does not lie inside the %llu packed bytes", bound);
+  if (rc == DX_OK && total) memcpy(total, back + UF_OUT, 32);
+  return rc;
 }
 
 extern "C" int dx_byte_hist_ranges(dx_ctx *ctx, const uint8_t *d_buf, uint64_t buf_bytes, const uint64_t *d_off, const uint64_t *d_len,
@@ -416,19 +339,12 @@ extern "C" int dx_byte_hist_ranges(dx_ctx *ctx, const uint8_t *d_buf, uint64_t b
     return dx_fail(ctx, DX_E_ARG, "dx_byte_hist_ranges: %d tables (1 to %d)", nkinds, HS_KINDS);
   if (hist) memset(hist, 0, (size_t) nkinds * 256u * 8u);
   if (n == 0) return DX_OK;
-  if (n >= (1ull << 31))
-    return dx_fail(ctx, DX_E_ARG, "dx_byte_hist_ranges: more than 2^31 - 1 units in one batch");
-  if (!d_off || !d_len || (!d_buf && buf_bytes))
-    return dx_fail(ctx, DX_E_ARG, "dx_byte_hist_ranges: NULL device pointer");
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_after_pending(ctx);
-  if (rc != DX_OK) return rc;
-
-  const size_t words = (size_t) nkinds * 256u;
-  uint64_t *d_w;
+  const size_t   words = (size_t) nkinds * 256u;           // (more than the context's frame holds: the frame heads a scratch block,
+  units_frame    f;                                        //  so that the tables still come back with it in one copy)
   const uint64_t bound = buf_bytes;
-  if ((rc = cw_begin(ctx, words, &d_w, &d_buf, &buf_bytes)) != DX_OK) return rc;
-  std::vector<uint64_t> back(CW_OUT + words);
+  int rc = units_begin(ctx, "dx_byte_hist_ranges", n, d_off && d_len && (d_buf || !buf_bytes), NULL, words, 16, &d_buf, &buf_bytes, &f);
+  if (rc != DX_OK) return rc;
+  std::vector<uint64_t> back(UF_OUT + words);
   long long flush = dx_test_num("hist_flush", (long long) HS_FLUSH);               // (tests: the counters swept from this many bytes on)
   if (flush < (long long) DX_STEP || flush > (long long) HS_FLUSH) flush = (long long) HS_FLUSH;
   // a ticket: 64 units at least; of many units more, so that the draws stay few beside the work (as dx_crc32_ranges)
@@ -439,16 +355,8 @@ extern "C" int dx_byte_hist_ranges(dx_ctx *ctx, const uint8_t *d_buf, uint64_t b
   if (lds > (32u << 10))                                  // (up to 64 KB: eight tables)
     DX_HIP(ctx, hipFuncSetAttribute((const void *) k_byte_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
   hipLaunchKernelGGL(k_byte_hist, dim3(grid), dim3(DX_BLOCK), lds, ctx->stream, d_buf, buf_bytes, bound, d_off, d_len, d_kind,
-                     (uint32_t) nkinds, n, (unsigned long long *) d_sum, (unsigned long long *) (d_w + CW_OUT),
-                     (unsigned long long *) (d_w + CW_BAD), (uint32_t *) (d_w + CW_TICKET), (uint32_t) per, (uint64_t) flush);
-  DX_HIP(ctx, hipGetLastError());
-  DX_HIP(ctx, hipMemcpyAsync(back.data(), d_w, back.size() * 8u, hipMemcpyDeviceToHost, ctx->stream));
-  DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (back[CW_BAD] != UINT64_MAX)
-    { if (bad_unit) *bad_unit = back[CW_BAD];
-      return dx_fail(ctx, DX_E_FORMAT, "dx_byte_hist_ranges: range %llu does not lie inside the buffer's %llu bytes, or its kind is not below %d",
-                     (unsigned long long) back[CW_BAD], (unsigned long long) bound, nkinds);
-    }
-  if (hist) memcpy(hist, back.data() + CW_OUT, words * 8u);
-  return DX_OK;
+                     (uint32_t) nkinds, n, (unsigned long long *) d_sum, f.out, f.bad, f.ticket, (uint32_t) per, (uint64_t) flush);
+  rc = units_end(ctx, f, back.data(), bad_unit, "%s: range %llu does not lie inside the buffer's %llu bytes, or its kind is not below %d", bound, nkinds);
+  if (rc == DX_OK && hist) memcpy(hist, back.data() + UF_OUT, words * 8u);
+  return rc;
 }

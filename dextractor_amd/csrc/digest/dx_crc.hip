@@ -44,8 +44,7 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry
 // in the profiler's name table and are timed with events on the context's stream (tools/digest_rate.py).
-#include "dx_internal.hpp"
-#include "dx_device.hpp"
+#include "units/dx_units.hpp"
 extern "C" {
 #include "dx_host.h"              // dx_crc32_ranges_strided, dx_crc32_pairs
 }
@@ -171,33 +170,27 @@ void k_crc_ranges(const uint8_t *__restrict__ buf, uint64_t buf_bytes, const uin
   crc_table(s_tab);
   const uint32_t  lane = (uint32_t) lane_id();
   const uint32_t *tab  = s_tab + (lane & 31u);
-  for (uint64_t r0 = next_unit(ticket, per_ticket); r0 < n; r0 = next_unit(ticket, per_ticket))
-    { const uint64_t r1 = r0 + per_ticket < n ? r0 + per_ticket : n;
-      for (uint64_t u0 = r0; u0 < r1; u0 += 64u)
-        { const uint64_t i = u0 + lane;
-          uint64_t at = 0, L = 0;
-          int      kind = 0;                 // 1: this lane's, 2: the wave's, 3: set aside
-          if (i < r1)
-            { at = off[i * stride]; L = len[i * stride];
-              if (at <= buf_bytes && L <= buf_bytes - at) kind = L < CRC_WAVE_MIN ? 1 : (L < split ? 2 : 3);
-              else atomicMin(bad, (unsigned long long) i);
-            }
-          if (kind == 3)
-            { const uint32_t k = atomicAdd(huge_n, 1u);
-              if (k < CRC_HUGE_MAX) { huge[k] = (uint32_t) i; crc[i * stride] = 0xffffffffu; }      // (the final xor; the pieces' shares follow)
-              else kind = 2;
-            }
-          if (kind == 1) crc[i * stride] = ~crc_run(tab, buf + at, L, 0xffffffffu);
-          uint64_t longs = __ballot(kind == 2);
-          while (longs)
-            { const int from = __ffsll((unsigned long long) longs) - 1;
-              longs &= longs - 1u;
-              const uint64_t wat = uniform64(__shfl(at, from)), wL = uniform64(__shfl(L, from));
-              const uint32_t st  = crc_wave(tab, buf + wat, wL, 0xffffffffu);
-              if (lane == 0) crc[(u0 + (uint64_t) from) * stride] = ~st;
-            }
+  units_rounds<false>(ticket, per_ticket, n, [&](uint64_t u0, uint64_t r1)
+    { const uint64_t i = u0 + lane;
+      uint64_t at = 0, L = 0;
+      int      kind = 0;                     // 1: this lane's, 2: the wave's, 3: set aside
+      if (i < r1)
+        { at = off[i * stride]; L = len[i * stride];
+          if (range_ok(at, L, buf_bytes)) kind = L < CRC_WAVE_MIN ? 1 : (L < split ? 2 : 3);
+          else atomicMin(bad, (unsigned long long) i);
         }
-    }
+      if (kind == 3)
+        { const uint32_t k = atomicAdd(huge_n, 1u);
+          if (k < CRC_HUGE_MAX) { huge[k] = (uint32_t) i; crc[i * stride] = 0xffffffffu; }      // (the final xor; the pieces' shares follow)
+          else kind = 2;
+        }
+      if (kind == 1) crc[i * stride] = ~crc_run(tab, buf + at, L, 0xffffffffu);
+      units_each(__ballot(kind == 2), [&](int from)
+        { const uint64_t wat = uniform64(__shfl(at, from)), wL = uniform64(__shfl(L, from));
+          const uint32_t st  = crc_wave(tab, buf + wat, wL, 0xffffffffu);
+          if (lane == 0) crc[(u0 + (uint64_t) from) * stride] = ~st;
+        });
+    });
 }
 
 // The units on the list, piece by piece: the pieces of all of them are numbered through, and wave w of W takes the numbers
@@ -230,20 +223,12 @@ static int crc_ranges(dx_ctx *ctx, const char *who, const uint8_t *d_buf, uint64
 { if (ctx == NULL) return DX_E_ARG;
   if (bad_unit) *bad_unit = UINT64_MAX;
   if (n == 0) return DX_OK;
-  if (n >= (1ull << 31))
-    return dx_fail(ctx, DX_E_ARG, "%s: more than 2^31 - 1 units in one batch", who);
-  if (!d_off || !d_len || !d_crc || (!d_buf && buf_bytes) || stride == 0)
-    return dx_fail(ctx, DX_E_ARG, "%s: NULL device pointer", who);
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_after_pending(ctx);
+  units_frame f;                                           // (answer word 0: how many units are set aside)
+  uint64_t    back[UF_OUT + 1];
+  uint32_t   *d_huge;
+  int rc = units_begin(ctx, who, n, d_off && d_len && d_crc && (d_buf || !buf_bytes) && stride != 0, ctx->d_u64 + DXW_UNITS, 1, 0, NULL, NULL, &f);
   if (rc != DX_OK) return rc;
-
-  uint32_t           *d_ticket = (uint32_t *) (ctx->d_u64 + 41), *d_huge_n = (uint32_t *) (ctx->d_u64 + 43), *d_huge;
-  unsigned long long *d_bad    = (unsigned long long *) (ctx->d_u64 + 42), bad = ~0ull;
   if ((rc = dx_scratch(ctx, CRC_HUGE_MAX * sizeof(uint32_t), (void **) &d_huge)) != DX_OK) return rc;
-  DX_HIP(ctx, hipMemsetAsync(d_ticket, 0, 4, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(d_huge_n, 0, 4, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(d_bad, 0xff, 8, ctx->stream));
   long long split = dx_test_num("crc_split", (long long) CRC_SPLIT);                 // (tests: units split from this size on)
   if (split < (long long) CRC_WAVE_MIN) split = CRC_WAVE_MIN;
   // a ticket: 64 units at least; of many units more, so that the draws (an atomic on one address each) stay few beside the work
@@ -251,18 +236,11 @@ static int crc_ranges(dx_ctx *ctx, const char *who, const uint8_t *d_buf, uint64
   uint64_t  per  = n / ((uint64_t) grid * DX_WAVES_PER_BLK * 8u);
   per = per < 64u ? 64u : (per > 4096u ? 4096u : per & ~63ull);
   hipLaunchKernelGGL(k_crc_ranges, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_buf, buf_bytes, d_off, d_len, n, stride, d_crc,
-                     d_bad, d_ticket, (uint32_t) per, (uint64_t) split, d_huge, d_huge_n);
+                     f.bad, f.ticket, (uint32_t) per, (uint64_t) split, d_huge, (uint32_t *) f.out);
   DX_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_crc_huge, dim3(dx_grid_waves(ctx, UINT64_MAX, 20)), dim3(DX_BLOCK), 0, ctx->stream, d_buf, d_off, d_len, stride,
-                     d_crc, d_huge, d_huge_n);
-  DX_HIP(ctx, hipGetLastError());
-  DX_HIP(ctx, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-  DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (bad != ~0ull)
-    { if (bad_unit) *bad_unit = bad;
-      return dx_fail(ctx, DX_E_FORMAT, "%s: unit %llu does not lie inside the buffer's %llu bytes", who, bad, (unsigned long long) buf_bytes);
-    }
-  return DX_OK;
+                     d_crc, d_huge, (const uint32_t *) f.out);
+  return units_end(ctx, f, back, bad_unit, "%s: unit %llu does not lie inside the buffer's %llu bytes", buf_bytes);
 }
 
 extern "C" int dx_crc32_ranges(dx_ctx *ctx, const uint8_t *d_buf, uint64_t buf_bytes, const uint64_t *d_off, const uint64_t *d_len,
@@ -332,7 +310,7 @@ extern "C" int dx_crc32_fold(dx_ctx *ctx, const uint32_t *d_crc, const uint64_t 
   int rc = dx_after_pending(ctx);
   if (rc != DX_OK) return rc;
 
-  uint64_t *d_res = ctx->d_u64 + 44, back[2];              // the CRC's word, the length
+  uint64_t *d_res = ctx->d_u64 + DXW_UNITS + UF_OUT, back[2];   // the CRC's word, the length: the frame's answer words
   uint64_t  blocks = (n + 4u * DX_BLOCK - 1u) / (4u * DX_BLOCK);
   if (blocks > CRC_FOLD_BLKS) blocks = CRC_FOLD_BLKS;
   const uint64_t per = (n + blocks * DX_BLOCK - 1u) / (blocks * DX_BLOCK);

@@ -32,13 +32,10 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip), and the kernel has no entry in
 // the profiler's name table: tools/reads_rate.py times it with events on the context's stream, beside k_pack2_decode.
-#include "dx_internal.hpp"
-#include "dx_device.hpp"
+#include "units/dx_units.hpp"
 
 #define RD_BATCH   16u                   // units a ticket at least (k_ticket_units: more of short ones)
-#define RD_GROUP   16u                   // lanes that take a short unit together
-#define RD_SHORT   (16u * RD_GROUP)      // ... one whose bytes, from the 16-byte boundary in front of them on, are no more than this
-#define RD_LEN_MAX 0x7fffffffu           // symbols a unit (DAZZ_READ.rlen is an int); more are refused like a unit out of bounds
+#define RD_SHORT   (16u * UNITS_GROUP)   // a short unit (16 lanes'): its bytes, from the 16-byte boundary in front of them on, are no more than this
 
 template <int LETTERS>
 __device__ __forceinline__ uint32_t rd_letter(uint32_t code)
@@ -130,50 +127,35 @@ void k_reads_unpack(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t 
               | (rd_letter<LETTERS>((k >> 2) & 3u) << 16) | (rd_letter<LETTERS>(k & 3u) << 24);
   __syncthreads();
 
-  const uint32_t lane = (uint32_t) lane_id(), grp = lane / RD_GROUP, q_grp = 16u * (lane % RD_GROUP);
-  const uint32_t TB = ticket_units_of(ticket, RD_BATCH);
-  for (uint64_t r0 = next_unit(ticket, TB), nxt; r0 < n; r0 = nxt)
-  { nxt = next_unit(ticket, TB);                           // drawn early: hidden behind these units
-    const uint64_t r1 = r0 + TB < n ? r0 + TB : n;
-    for (uint64_t u0 = r0; u0 < r1; u0 += 64u)
+  const uint32_t lane = (uint32_t) lane_id(), q_grp = 16u * (lane % UNITS_GROUP);
+  units_rounds<true>(ticket, ticket_units_of(ticket, RD_BATCH), n, [&](uint64_t u0, uint64_t r1)
     { // unit u0 + lane is this lane's to read and to check
-      const uint64_t i = u0 + lane;
-      rd_unit mine = { 0ull, 0ull, 0u, 1u, 0u };
-      bool ok = false;
+      const uint64_t    i  = u0 + lane;
+      const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
+      rd_unit mine = { pu.at, 0ull, pu.beg, pu.len + 1u, 0u };
       if (i < r1)
-        { const uint64_t at = boff[i];
-          const uint32_t b = beg != NULL ? beg[i] : 0u, L = len[i];
-          ok = at <= bound && L <= RD_LEN_MAX && (L == 0u || (((uint64_t) b + L - 1u) >> 2) < bound - at);
-          if (!ok) atomicMin(bad, (unsigned long long) i);
-          mine.at = at; mine.beg = b; mine.N = L + 1u;
-          mine.to  = out_off[i];
+        { mine.to  = out_off[i];
           mine.adj = (uint32_t) ((uintptr_t) (out + mine.to) & 15u);
         }
-      const bool brief = ok && mine.N + mine.adj <= RD_SHORT;
-      const uint64_t briefs = __ballot(brief);
-      uint64_t       longs  = __ballot(ok && !brief);
+      const bool brief = pu.ok && mine.N + mine.adj <= RD_SHORT;
 
       // the short ones: lanes 16 g .. 16 g + 15 take unit k + g
-      for (uint32_t k = 0; k < 64u; k += 64u / RD_GROUP)
-        if ((briefs >> k) & ((1ull << (64u / RD_GROUP)) - 1u))
-          { const int from = (int) (k + grp);
-            rd_unit u;
-            u.at  = __shfl(mine.at, from);
-            u.beg = __shfl(mine.beg, from);
-            u.N   = __shfl(mine.N, from);
-            u.adj = __shfl(mine.adj, from);
-            u.to  = __shfl(mine.to, from);
-            if (((briefs >> from) & 1ull) && q_grp < u.N + u.adj)
-              { if (u.N >= 16u) rd_put<LETTERS>(s_quad, in_bytes, out, u, q_grp, rd_ask(in, in_bytes, u, q_grp));
-                else if (q_grp == 0u) rd_small<LETTERS>(in, s_quad, out, u);
-              }
-          }
+      units_by_fours(__ballot(brief), [&](int from, bool its)
+        { rd_unit u;
+          u.at  = __shfl(mine.at, from);
+          u.beg = __shfl(mine.beg, from);
+          u.N   = __shfl(mine.N, from);
+          u.adj = __shfl(mine.adj, from);
+          u.to  = __shfl(mine.to, from);
+          if (its && q_grp < u.N + u.adj)
+            { if (u.N >= 16u) rd_put<LETTERS>(s_quad, in_bytes, out, u, q_grp, rd_ask(in, in_bytes, u, q_grp));
+              else if (q_grp == 0u) rd_small<LETTERS>(in, s_quad, out, u);
+            }
+        });
 
       // the others: the whole wave, 1 KiB of the frame a step
-      while (longs)
-        { const int from = __ffsll((unsigned long long) longs) - 1;
-          longs &= longs - 1u;
-          rd_unit u;
+      units_each(__ballot(pu.ok && !brief), [&](int from)
+        { rd_unit u;
           u.at  = uniform64(__shfl(mine.at, from));
           u.beg = uniform(__shfl(mine.beg, from));
           u.N   = uniform(__shfl(mine.N, from));
@@ -211,9 +193,8 @@ void k_reads_unpack(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t 
               if (q + base < TS) rd_put<LETTERS>(s_quad, in_bytes, out, u, q + base, rawA);
               rawA = ahead;
             }
-        }
-    }
-  }
+        });
+    });
 }
 
 extern "C" int dx_reads_unpack(dx_ctx *ctx, int letters, const uint8_t *d_in, uint64_t in_bytes,
@@ -224,55 +205,34 @@ extern "C" int dx_reads_unpack(dx_ctx *ctx, int letters, const uint8_t *d_in, ui
   if (letters < DX_LETTERS_LOWER || letters > DX_LETTERS_NUMBERS)
     return dx_fail(ctx, DX_E_ARG, "dx_reads_unpack: unknown letter set %d", letters);
   if (n == 0) return DX_OK;
-  if (n >= (1ull << 31))
-    return dx_fail(ctx, DX_E_ARG, "dx_reads_unpack: more than 2^31 - 1 units in one batch");
-  if (!d_boff || !d_len || !d_out || !d_out_off || (!d_in && in_bytes))
-    return dx_fail(ctx, DX_E_ARG, "dx_reads_unpack: NULL device pointer");
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_after_pending(ctx);
+  units_frame    f;
+  uint64_t       back[UF_OUT];
+  const uint64_t bound = in_bytes;                         // (the kernel loads 8 bytes at a time: fewer are copied, zeros behind them)
+  int rc = units_begin(ctx, "dx_reads_unpack", n, d_boff && d_len && d_out && d_out_off && (d_in || !in_bytes),
+                       ctx->d_u64 + DXW_UNITS, 0, 8, &d_in, &in_bytes, &f);
   if (rc != DX_OK) return rc;
-
-  uint32_t           *d_ticket = (uint32_t *) (ctx->d_u64 + 36);
-  unsigned long long *d_bad    = (unsigned long long *) (ctx->d_u64 + 37), bad = ~0ull;
-  DX_HIP(ctx, hipMemsetAsync(d_ticket, 0, 4, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(d_bad, 0xff, 8, ctx->stream));
-  const uint64_t bound = in_bytes;
-  if (in_bytes < 8u)                                       // the kernel loads 8 bytes at a time: a copy with zeros behind it
-    { uint8_t *d_pad = (uint8_t *) (ctx->d_u64 + 38);
-      DX_HIP(ctx, hipMemsetAsync(d_pad, 0, 8, ctx->stream));
-      if (in_bytes) DX_HIP(ctx, hipMemcpyAsync(d_pad, d_in, in_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-      d_in = d_pad; in_bytes = 8u;
-    }
   // (units per ticket from the output's extent: outputs that do not stand in the units' order give a figure that means
   //  nothing, and the bounds of ticket_units_of hold)
   hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_out_off, d_out_off + (n - 1), d_len + (n - 1), n,
-                     RD_BATCH * 10000u, RD_BATCH, d_ticket);
+                     RD_BATCH * 10000u, RD_BATCH, f.ticket);
   const int grid = dx_grid_waves(ctx, n, 32);
   switch (letters)
     { case DX_LETTERS_LOWER:
         hipLaunchKernelGGL(k_reads_unpack<DX_LETTERS_LOWER>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream,
-                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, d_bad, d_ticket);
+                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, f.bad, f.ticket);
         break;
       case DX_LETTERS_UPPER:
         hipLaunchKernelGGL(k_reads_unpack<DX_LETTERS_UPPER>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream,
-                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, d_bad, d_ticket);
+                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, f.bad, f.ticket);
         break;
       case DX_LETTERS_ARROW:
         hipLaunchKernelGGL(k_reads_unpack<DX_LETTERS_ARROW>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream,
-                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, d_bad, d_ticket);
+                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, f.bad, f.ticket);
         break;
       default:
         hipLaunchKernelGGL(k_reads_unpack<DX_LETTERS_NUMBERS>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream,
-                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, d_bad, d_ticket);
+                           d_in, in_bytes, bound, d_boff, d_beg, d_len, n, d_out, d_out_off, f.bad, f.ticket);
         break;
     }
-  DX_HIP(ctx, hipGetLastError());
-  DX_HIP(ctx, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-  DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (bad != ~0ull)
-    { if (bad_unit) *bad_unit = bad;
-      return dx_fail(ctx, DX_E_FORMAT, "dx_reads_unpack: unit %llu does not lie inside the %llu packed bytes",
-                     bad, (unsigned long long) bound);
-    }
-  return DX_OK;
+  return units_end(ctx, f, back, bad_unit, "%s: unit %llu does not lie inside the %llu packed bytes", bound);
 }

@@ -16,8 +16,7 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip): its kernel has no entry
 // in the profiler's name table and is timed with HIP events where a time is wanted (profiles/verify_rate.txt).
-#include "dx_internal.hpp"
-#include "dx_device.hpp"
+#include "units/dx_units.hpp"
 
 #define VF_LONG   2048u                  // units from here on take the whole wave
 #define VF_NONE   0xffffffffu
@@ -64,12 +63,8 @@ void k_verify_ranges(const uint8_t *__restrict__ a, const uint64_t *__restrict__
                      const uint8_t *__restrict__ b, const uint64_t *__restrict__ b_off, const uint32_t *__restrict__ b_len,
                      uint64_t n, int skip, unsigned long long *res, uint32_t *ticket)
 { const int      lane = lane_id(), sub = lane >> 4, sl = lane & 15;
-  const uint32_t per  = ticket_units_of(ticket, VF_LEAST);
-  for (;;)
-    { const uint64_t t0 = next_unit(ticket, per);
-      if (t0 >= n) break;
-      const uint64_t t1 = t0 + per < n ? t0 + per : n;
-      if (skip && (uniform64(__hip_atomic_load(res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) < t0) continue;
+  units_tickets<false>(ticket, ticket_units_of(ticket, VF_LEAST), n, [&](uint64_t t0, uint64_t t1)
+    { if (skip && (uniform64(__hip_atomic_load(res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) < t0) return;
       for (uint64_t u0 = t0; u0 < t1; u0 += 4)
         { // four units, one to each 16 lanes
           const uint64_t u  = u0 + (uint64_t) sub;
@@ -100,11 +95,8 @@ void k_verify_ranges(const uint8_t *__restrict__ a, const uint64_t *__restrict__
           #pragma unroll
           for (int g = 0; g < 4; g++)
             todo |= (uint32_t) (__shfl((int) (in && !small), 16 * g) != 0) << g;
-          todo = uniform(todo);
-          while (todo)
-            { const int      g   = __builtin_ctz(todo);
-              todo &= todo - 1u;
-              const uint64_t w   = u0 + (uint64_t) g;
+          units_each(uniform(todo), [&](int g)
+            { const uint64_t w   = u0 + (uint64_t) g;
               const uint32_t wal = uniform(__shfl(al, 16 * g)), wbl = uniform(__shfl(bl, 16 * g)), wm = wal < wbl ? wal : wbl;
               const uint8_t *wa  = a + uniform64(a_off[w]) + 16u * lane, *wb = b + uniform64(b_off[w]) + 16u * lane;
               uint64_t at = 0;
@@ -140,29 +132,29 @@ void k_verify_ranges(const uint8_t *__restrict__ a, const uint64_t *__restrict__
               hit = uniform(hit);
               if (lane == 0 && (hit != VF_NONE || wal != wbl))
                 report(res, w, hit != VF_NONE ? hit : wm);
-            }
+            });
         }
-    }
+    });
 }
 
-// one launch over units [0, n), n < 2^32; first: unit << 32 | position, or all ones
+static_assert(DXW_COUNT == 64, "dx_ctx.hip allocates 64 words of d_u64");
+
+// one launch over units [0, n), 0 < n < 2^31; first: unit << 32 | position, or all ones
 static int verify_launch(dx_ctx *ctx, const uint8_t *d_a, const uint64_t *d_a_off, const uint32_t *d_a_len,
                          const uint8_t *d_b, const uint64_t *d_b_off, const uint32_t *d_b_len, uint64_t n, int skip,
                          uint64_t *first, uint64_t *differ)
-{ unsigned long long *d_res    = (unsigned long long *) (ctx->d_u64 + 32);
-  uint32_t           *d_ticket = (uint32_t *) (ctx->d_u64 + 34);
-  uint64_t            back[2];
-  DX_HIP(ctx, hipMemsetAsync(d_res, 0xff, 8, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(d_res + 1, 0, 8, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(d_ticket, 0, 4, ctx->stream));
+{ units_frame f;
+  uint64_t    back[UF_OUT + 2];
+  int rc = units_begin(ctx, "dx_verify_ranges", n, d_a && d_a_off && d_a_len && d_b && d_b_off && d_b_len,
+                       ctx->d_u64 + DXW_UNITS, 2, 0, NULL, NULL, &f);
+  if (rc != DX_OK) return rc;
+  DX_HIP(ctx, hipMemsetAsync(f.out, 0xff, 8, ctx->stream));
   hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_a_off, d_a_off + (n - 1), d_a_len + (n - 1), n,
-                     VF_TARGET, VF_LEAST, d_ticket);
+                     VF_TARGET, VF_LEAST, f.ticket);
   hipLaunchKernelGGL(k_verify_ranges, dim3(dx_grid_waves(ctx, (n + VF_LEAST - 1) / VF_LEAST, 16)), dim3(DX_BLOCK), 0, ctx->stream,
-                     d_a, d_a_off, d_a_len, d_b, d_b_off, d_b_len, n, skip, d_res, d_ticket);
-  DX_HIP(ctx, hipGetLastError());
-  DX_HIP(ctx, hipMemcpyAsync(back, d_res, 16, hipMemcpyDeviceToHost, ctx->stream));
-  DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *first = back[0]; *differ = back[1];
+                     d_a, d_a_off, d_a_len, d_b, d_b_off, d_b_len, n, skip, f.out, f.ticket);
+  if ((rc = units_end(ctx, f, back, NULL, NULL, 0)) != DX_OK) return rc;   // (no unit is refused: nothing words one)
+  *first = back[UF_OUT]; *differ = back[UF_OUT + 1];
   return DX_OK;
 }
 
@@ -174,11 +166,7 @@ extern "C" int dx_verify_ranges(dx_ctx *ctx, const uint8_t *d_a, const uint64_t 
     return dx_fail(ctx, DX_E_ARG, "dx_verify_ranges: nowhere to put the answer");
   *first_unit = UINT64_MAX; *first_pos = 0;
   if (n_differ) *n_differ = 0;
-  if (n == 0) return DX_OK;
-  if (!d_a || !d_a_off || !d_a_len || !d_b || !d_b_off || !d_b_len)
-    return dx_fail(ctx, DX_E_ARG, "dx_verify_ranges: NULL device pointer");
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t piece = 1ull << 31;                       // (the key holds 32 bits of unit index)
+  const uint64_t piece = (1ull << 31) - 1u;                // (the key holds 32 bits of unit index; a launch takes fewer than 2^31 units)
   for (uint64_t at = 0; at < n; at += piece)
     { const uint64_t m = n - at < piece ? n - at : piece;
       uint64_t first = 0, differ = 0;
