@@ -16,7 +16,7 @@ CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 # $(CSRC)/*.hip and *.hpp only); units/dx_units.hpp is what four of them share, dx_words.h the names of the words of ctx->d_u64
 HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads digest/dx_crc census/dx_census
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
-C_SRC    = dx_host dx_walk_host dx_files dx_file_pack2 dx_file_qv dx_file_check dx_select dx_compat
+C_SRC    = dx_host dx_walk_host dx_crew dx_files dx_file_pack2 dx_file_qv dx_file_qv_shard dx_file_check dx_select dx_compat
 C_OBJ    = $(C_SRC:%=$(BUILD)/%.o)
 TOOLS    = dexta undexta dexar undexar dexqv undexqv
 
@@ -32,7 +32,7 @@ $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/dx_internal.hpp $(CSRC)/dx_device.hpp $(CSRC
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.res; rc=$$?; \
 	  grep -v "kernel-resource-usage\|^ *[0-9]* | \|^ *| *^" $(BUILD)/$*.res >&2; exit $$rc
 
-$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_host.h $(CSRC)/dx_files.h $(CSRC)/dx_env.h include/dexgpu.h include/dexcompat.h
+$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/dx_layout.h $(CSRC)/dx_walk.h $(CSRC)/dx_host.h $(CSRC)/dx_files.h $(CSRC)/dx_crew.h $(CSRC)/dx_env.h include/dexgpu.h include/dexcompat.h
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 

@@ -10,6 +10,7 @@
 #include "dexgpu.h"
 #include "dx_env.h"
 #include "dx_host.h"
+#include "dx_crew.h"
 #include "dx_files.h"
 
 /* ==========================================================================================
@@ -152,8 +153,8 @@ static int pack2_piece(dx_ctx *ctx, int arrow, const uint8_t *text, size_t n, in
       TRY(dupload(&pool, text, n, &d_text));
       rc = dx_index_seq_device(ctx, arrow, d_text, n, &go, &gt, &gs, &ix.cnt, &ix.hdr4, &ix.cnr4, &ix.plen, errline, errcode);
       if (rc == DX_OK)
-        { d_off = go; d_tlen = gt; d_nsym = gs;
-          pool.p[pool.n++] = go; pool.p[pool.n++] = gt; pool.p[pool.n++] = gs;
+        { if (dadopt(&pool, go) | dadopt(&pool, gt) | dadopt(&pool, gs)) { rc = DX_E_NOMEM; goto done; }      /* (each of them, whatever becomes of the others) */
+          d_off = go; d_tlen = gt; d_nsym = gs;
           ix.nsym = malloc((ix.cnt + 1) * sizeof(*ix.nsym));
           if (!ix.nsym) { rc = DX_E_NOMEM; goto done; }
           TRY(dx_d2h(ctx, ix.nsym, d_nsym, ix.cnt * 4));
@@ -393,6 +394,7 @@ done:
  *  dexta / dexar of one file on several GPUs: reads are independent, so contiguous read ranges
  *  (balanced by text bytes) go to one host thread per context; nothing is exchanged -- the only
  *  cross-record datum, the previous well of a range's first read, is known from the host index.
+ *  The threads are a crew of one phase (dx_crew.h): all of them exist, or no range is packed.
  * ========================================================================================== */
 typedef struct
   { dx_ctx          *ctx;
@@ -403,11 +405,12 @@ typedef struct
     uint64_t         lo, hi;                  /* reads [lo, hi) */
   } p2_job;
 
-static void *p2_main(void *arg)
-{ p2_job *j = (p2_job *) arg;
+static void p2_range(void *arg)
+{ p2_job *j = arg;
   j->rc = pack2_range(j->ctx, j->arrow, j->text, j->ix, j->lo, j->hi, j->img);
-  return NULL;
 }
+
+static const dx_crew_phase p2_phases[] = { { p2_range, NULL } };
 
 int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *text, size_t n,
                           uint8_t **out, size_t *out_len, uint64_t *errline, int *errcode)
@@ -415,8 +418,7 @@ int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *tex
   int32_t   lwell = 0;
   uint8_t  *img = NULL;
   p2_job   *jobs = NULL;
-  pthread_t *th = NULL;
-  int       rc, k, started = 0;
+  int       rc, k;
 
   if (ctxs == NULL || nctx < 1 || out == NULL || out_len == NULL) return DX_E_ARG;
   if (nctx == 1) return dx_file_pack2(ctxs[0], arrow, text, n, out, out_len, errline, errcode);
@@ -430,8 +432,7 @@ int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *tex
   pack2_head(img, text, ix.plen);
 
   jobs = calloc((size_t) nctx, sizeof(*jobs));
-  th   = calloc((size_t) nctx, sizeof(*th));
-  if (!jobs || !th) { rc = DX_E_NOMEM; goto done; }
+  if (!jobs) { rc = DX_E_NOMEM; goto done; }
   { uint64_t lo = 0;
     const uint64_t tbytes = ix.cnt ? ix.off[ix.cnt - 1] + ix.tlen[ix.cnt - 1] - ix.off[0] : 0;
     for (k = 0; k < nctx; k++)
@@ -444,13 +445,7 @@ int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *tex
         lo = hi;
       }
   }
-  for (k = 0; k < nctx; k++)
-    { if (pthread_create(&th[k], NULL, p2_main, &jobs[k]) != 0) { rc = DX_E_NOMEM; break; }
-      started++;
-    }
-  for (k = 0; k < started; k++)
-    pthread_join(th[k], NULL);
-  if (started < nctx) goto done;
+  if (dx_crew_run(nctx, p2_phases, 1, jobs, sizeof(*jobs), NULL)) { rc = DX_E_NOMEM; goto done; }      /* (all the ranges, or none) */
   rc = DX_OK;
   for (k = 0; k < nctx; k++)
     if (jobs[k].rc != DX_OK) { rc = jobs[k].rc; break; }
@@ -459,7 +454,7 @@ int dx_file_pack2_sharded(dx_ctx **ctxs, int nctx, int arrow, const uint8_t *tex
 
 done:
   dxf_seq_index_free(&ix);
-  free(img); free(jobs); free(th);
+  free(img); free(jobs);
   return rc;
 }
 

@@ -1,8 +1,7 @@
 /*
- * dx_file_qv.c -- the file drivers of .quiva / .dexqv: dexqv of a whole text, in slices, and on several GPUs; undexqv as a plan and its
- * run.  dx_files.h has what the other drivers take from here.
+ * dx_file_qv.c -- the file drivers of .quiva / .dexqv: dexqv of a whole text and in slices; undexqv as a plan and its
+ * run (dexqv on several GPUs: dx_file_qv_shard.c).  dx_files.h has what the other drivers take from here.
  */
-#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,15 +40,11 @@ int dxf_quiva_index_host(quiva_index *qx, const uint8_t *text, size_t n, uint64_
 void dxf_quiva_index_free(quiva_index *qx)
 { free(qx->off); free(qx->len); free(qx->hdr4); }
 
-/* where entry e's five lines end in the text */
-static uint64_t quiva_end(const quiva_index *qx, uint64_t e)
-{ return qx->off[e] + 5 * ((uint64_t) qx->len[e] + 1); }
-
 /* a slice of whole entries from e0 on: as many as make at most `cap` bytes of text (an entry larger than the cap is a slice of its own) */
 static uint64_t quiva_slice_end(const quiva_index *qx, uint64_t e0, size_t cap)
-{ const uint64_t s0 = e0 ? quiva_end(qx, e0 - 1) : 0;
+{ const uint64_t s0 = e0 ? dxf_quiva_end(qx, e0 - 1) : 0;
   uint64_t e1 = e0 + 1;
-  while (e1 < qx->cnt && quiva_end(qx, e1) - s0 <= cap) e1++;
+  while (e1 < qx->cnt && dxf_quiva_end(qx, e1) - s0 <= cap) e1++;
   return e1;
 }
 
@@ -113,7 +108,7 @@ done:
 
 /* the head of a .dexqv image, dexqv.c:105-108: the key and the coding (Write_QVcoding; the prefix is the text's first plen bytes).
    *img: malloc'd, `head` bytes written, room for `more` behind them */
-static int qv_head(const dx_qv_coding *cd, const uint8_t *text, size_t plen, size_t more, uint8_t **img, size_t *head)
+int dxf_qv_head(const dx_qv_coding *cd, const uint8_t *text, size_t plen, size_t more, uint8_t **img, size_t *head)
 { const uint16_t key = 0x55aa;
   size_t clen = 0;
   int    rc = dx_qv_write_coding(cd, (const char *) text, plen, NULL, 0, &clen);            /* size of Write_QVcoding */
@@ -169,10 +164,10 @@ static int dexqv_sliced(dx_ctx *ctx, const uint8_t *text, size_t n, int lossy, s
   if (!cd || !hist || !junk) { rc = DX_E_NOMEM; goto done; }
   TRY(dxf_quiva_index_host(&qx, text, n, errline, errcode));
   for (e0 = 0; e0 < qx.cnt; e0 = e1)                      /* the widest slice in entries and bytes: one allocation serves them all */
-    { const uint64_t s0 = e0 ? quiva_end(&qx, e0 - 1) : 0;
+    { const uint64_t s0 = e0 ? dxf_quiva_end(&qx, e0 - 1) : 0;
       e1 = quiva_slice_end(&qx, e0, cap);
       if (e1 - e0 > maxent) maxent = (size_t) (e1 - e0);
-      if (quiva_end(&qx, e1 - 1) - s0 > slice_bytes) slice_bytes = (size_t) (quiva_end(&qx, e1 - 1) - s0);
+      if (dxf_quiva_end(&qx, e1 - 1) - s0 > slice_bytes) slice_bytes = (size_t) (dxf_quiva_end(&qx, e1 - 1) - s0);
     }
   rel = malloc((maxent + 1) * sizeof(*rel));
   if (!rel) { rc = DX_E_NOMEM; goto done; }
@@ -184,16 +179,16 @@ static int dexqv_sliced(dx_ctx *ctx, const uint8_t *text, size_t n, int lossy, s
     { if (pass == 2)
         { TRY(dx_qv_build((const uint64_t (*)[256]) hist, tot, &p, lossy, cd));          /* Create_QVcoding, dexqv.c:86 */
           TRY(dx_qv_set_coding(ctx, cd, lossy));
-          TRY(qv_head(cd, text, qx.plen, 0, &head_img, &head));
+          TRY(dxf_qv_head(cd, text, qx.plen, 0, &head_img, &head));
           if (sink(user, head_img, head, 0)) { rc = DX_E_IO; goto done; }
           at = head;
         }
       for (e0 = 0; e0 < qx.cnt; e0 = e1)
-        { const uint64_t s0 = e0 ? quiva_end(&qx, e0 - 1) : 0;
+        { const uint64_t s0 = e0 ? dxf_quiva_end(&qx, e0 - 1) : 0;
           uint64_t s1, k, m, total = 0;
           dx_qv_batch b;
           e1 = quiva_slice_end(&qx, e0, cap);
-          s1 = quiva_end(&qx, e1 - 1);
+          s1 = dxf_quiva_end(&qx, e1 - 1);
           m  = e1 - e0;
           for (k = 0; k < m; k++) rel[k] = qx.off[e0 + k] - s0;
           TRY(dx_h2d(ctx, d_text, text + s0, (size_t) (s1 - s0)));
@@ -293,8 +288,8 @@ static int dexqv_core(dx_ctx *ctx, const uint8_t *text, int fd, size_t n, int lo
     { uint64_t *go = NULL; uint32_t *gl = NULL;
       rc = dx_index_quiva_device(ctx, d_text, n, &go, &gl, &qx.cnt, &qx.hdr4, &qx.plen, errline, errcode);
       if (rc == DX_OK && qx.cnt > 0)
-        { d_off = go; d_len = gl;
-          pool.p[pool.n++] = go; pool.p[pool.n++] = gl;
+        { if (dadopt(&pool, go) | dadopt(&pool, gl)) { rc = DX_E_NOMEM; goto done; }      /* (each of them, whatever becomes of the other) */
+          d_off = go; d_len = gl;
         }
       else if (rc != DX_OK && rc != DX_E_FORMAT)
         goto done;
@@ -324,7 +319,7 @@ static int dexqv_core(dx_ctx *ctx, const uint8_t *text, int fd, size_t n, int lo
   /* pass 2, dexqv.c:112-143: Compress_Next_QVentry for every entry */
   TRY(dxf_qv_encode_batch(ctx, &st, (const uint64_t (*)[256]) hist, cd, lossy, &d_out, &out_cap, &total));
   fmark("dexqv: encoded");
-  TRY(qv_head(cd, text, qx.plen, out ? total : 0, &img, &head));
+  TRY(dxf_qv_head(cd, text, qx.plen, out ? total : 0, &img, &head));
   if (out)
     { TRY(dx_d2h(ctx, img + head, d_out, total));
       *out = img; img = NULL;
@@ -673,364 +668,5 @@ int dx_file_undexqv(dx_ctx *ctx, const uint8_t *img, size_t n, int upper, uint8_
   if (rc == DX_OK) { *out = m.res; *out_len = total; }
   else             free(m.res);
   dx_file_undexqv_plan_free(p);
-  return rc;
-}
-
-/* ==========================================================================================
- *  dexqv of one file on several GPUs: contiguous entry ranges, one host thread
- *  per context; the only exchange is on the host -- the merged scan state (32 bytes) and the sum
- *  of the 12 KB histograms -- after which every shard is encoded with identical tables and the
- *  record streams are concatenated in order.  No RCCL.
- * ========================================================================================== */
-
-typedef struct shard_job shard_job;
-
-typedef struct
-  { int               nsh, lossy, rc;
-    int               ok;                    /* written by shard 0 in its merge steps only, read by all after the next barrier */
-    int               go;                    /* start gate: 0 wait, 1 run, -1 a thread could not be created: leave */
-    pthread_mutex_t   gate_mx;
-    pthread_cond_t    gate_cv;
-    pthread_barrier_t bar;
-    const uint8_t    *text;
-    const uint64_t   *off;
-    const uint32_t   *len;
-    const int32_t    *hdr4;
-    uint64_t          cnt, cut;              /* cut: entry at which the running symbol count reaches 100000 */
-    dx_qv_params      p;
-    dx_qv_coding      cd;
-    uint64_t          hist[6][256], tot;
-    uint8_t          *img;
-    size_t            head, total;
-    shard_job        *jobs;
-    /* by bytes (large files): no index of the whole file exists; every shard finds and indexes its own records (shard_slice) */
-    int               by_bytes, again;       /* again: something is not as it should be -- the whole file once more, the serial way */
-    size_t            n, plen;
-  } shard_all;
-
-struct shard_job
-  { shard_all   *all;
-    dx_ctx      *ctx;
-    int          id, rc;
-    uint64_t     lo, hi;                      /* entries [lo, hi) */
-    dx_qv_params p;
-    uint64_t     hist[6][256], tot, bytes, at;
-    /* by bytes: the shard's byte range as dealt, the newlines in it, where its first record begins and the line that is, its own
-       index (hdr4 / len: host, the shard's entries; the offsets stay on the device) */
-    size_t       p0, p1, start;
-    uint64_t     nl, line0;
-    int32_t     *hdr4;
-    uint32_t    *len;
-  };
-
-/* Steps alternate between "every shard works and sets its own rc" and "shard 0 folds the results",
- * with a barrier after each: shard 0 reads the others' rc only in its folding steps (nobody writes
- * then) and publishes the verdict in a->ok, which the working steps read (nobody writes it then).   */
-static int all_ok(shard_all *a)
-{ int k;
-  for (k = 0; k < a->nsh; k++)
-    if (a->jobs[k].rc != DX_OK) return 0;
-  return a->rc == DX_OK;
-}
-
-static int shard_slice(shard_job *j, dpool *pool, void **d_text, void **d_off, void **d_len, uint64_t *span);
-
-/* The shard's entries staged on its device and prescanned (QV.c:993-1015, per shard).  By bytes, shard_slice has put text and index
-   there (d_text, d_off, d_len, span); else they are cut from the file's host index here. */
-static int shard_stage(shard_job *j, dpool *pool, void *d_text, void *d_off, void *d_len, uint64_t span, qv_staged *st)
-{ shard_all     *a = j->all;
-  const uint64_t m = j->hi - j->lo;
-  const int32_t *hdr4 = j->hdr4;
-  uint64_t      *roff = NULL, i;
-  int32_t        lwell;
-  int            rc;
-  if (a->by_bytes)
-    { const shard_job *prev = &a->jobs[j->id ? j->id - 1 : 0];
-      lwell = j->id ? prev->hdr4[4 * (prev->hi - prev->lo - 1)] : 0;
-    }
-  else                                                   /* this shard's slice of the text image */
-    { const uint64_t base = a->off[j->lo];
-      hdr4  = a->hdr4 + 4 * j->lo;
-      lwell = j->lo ? a->hdr4[4 * (j->lo - 1)] : 0;
-      span  = a->off[j->hi - 1] + 5 * ((uint64_t) a->len[j->hi - 1] + 1) - base;
-      roff  = malloc(m * sizeof(*roff));
-      if (!roff) return DX_E_NOMEM;
-      for (i = 0; i < m; i++) roff[i] = a->off[j->lo + i] - base;
-      TRY(dupload(pool, a->text + base, span, &d_text));
-      TRY(dupload(pool, roff, m * 8, &d_off));
-      TRY(dupload(pool, a->len + j->lo, m * 4, &d_len));
-    }
-  TRY(dxf_qv_stage(pool, hdr4, m, &lwell, d_text, d_off, d_len, span, 1, st));
-  TRY(dx_qv_prescan(j->ctx, &st->b, j->lo, &j->p));
-done:
-  free(roff);
-  return rc;
-}
-
-/* the file's first 100000 symbols (QV.c:1006-1015) reach beyond shard 0: the provisional subChar from a prefix batch of
-   entries [0, cut] instead */
-static int shard_prefix_sub(shard_job *j, dpool *pool)
-{ shard_all   *a = j->all;
-  const uint64_t mp = a->cut + 1, sp = a->off[a->cut] + 5 * ((uint64_t) a->len[a->cut] + 1) - a->off[0];
-  uint64_t    *po = malloc(mp * sizeof(*po)), i;
-  void        *pt = NULL, *pd_off = NULL, *pd_len = NULL;
-  dx_qv_batch  pb;
-  dx_qv_params pp = { 0, -1, 0, -1 };                     /* delChar "set": only the sub search runs */
-  int          rc;
-  if (po == NULL) return DX_E_NOMEM;
-  for (i = 0; i < mp; i++) po[i] = a->off[i] - a->off[0];
-  TRY(dupload(pool, a->text + a->off[0], sp, &pt));
-  TRY(dupload(pool, po, mp * 8, &pd_off));
-  TRY(dupload(pool, a->len, mp * 4, &pd_len));
-  pb = dxf_qv_batch(pt, pd_off, pd_len, mp, sp, 1);
-  TRY(dx_qv_prescan(j->ctx, &pb, 0, &pp));
-done:
-  j->p.subChar = pp.subChar; j->p.sub_first = pp.sub_first;
-  free(po);
-  return rc;
-}
-
-static void *shard_main(void *arg)
-{ shard_job  *j = arg;
-  shard_all  *a = j->all;
-  dpool       pool = { {0}, 0, j->ctx };
-  uint64_t    m = j->hi - j->lo, span = 0, total = 0;
-  void       *d_text = NULL, *d_off = NULL, *d_len = NULL, *d_out = NULL;
-  size_t      out_cap = 0;
-  qv_staged   st;
-  int         rc = DX_OK, k;
-
-  pthread_mutex_lock(&a->gate_mx);                        /* all threads exist, or none runs */
-  while (a->go == 0) pthread_cond_wait(&a->gate_cv, &a->gate_mx);
-  k = a->go;
-  pthread_mutex_unlock(&a->gate_mx);
-  if (k < 0) return NULL;
-
-  memset(&st, 0, sizeof(st));
-  j->p.delChar = j->p.subChar = -1; j->p.del_first = j->p.sub_first = -1;
-  memset(j->hist, 0, sizeof(j->hist)); j->tot = 0; j->bytes = 0;
-
-  if (a->by_bytes)
-    { rc = shard_slice(j, &pool, &d_text, &d_off, &d_len, &span);        /* (five barriers inside, whatever becomes of it) */
-      m = j->hi - j->lo;
-    }
-  if (rc == DX_OK && m > 0)
-    rc = shard_stage(j, &pool, d_text, d_off, d_len, span, &st);
-  if (rc == DX_OK && j->id == 0 && a->cut >= j->hi && !a->by_bytes)      /* (by bytes: shard_slice has seen to it that this is not so) */
-    rc = shard_prefix_sub(j, &pool);
-  j->rc = rc;
-  pthread_barrier_wait(&a->bar);
-
-  if (j->id == 0 && (a->ok = all_ok(a)))                 /* merge the scan state (lowest entry wins) */
-    { a->p.delChar = a->p.subChar = -1; a->p.del_first = a->p.sub_first = -1;
-      for (k = 0; k < a->nsh; k++)
-        if (a->jobs[k].p.delChar >= 0 && (a->p.delChar < 0 || a->jobs[k].p.del_first < a->p.del_first))
-          { a->p.delChar = a->jobs[k].p.delChar; a->p.del_first = a->jobs[k].p.del_first; }
-      for (k = 0; k < a->nsh; k++)
-        if (a->jobs[k].lo == 0 && a->jobs[k].hi > 0)
-          { a->p.subChar = a->jobs[k].p.subChar; a->p.sub_first = a->jobs[k].p.sub_first; }
-    }
-  pthread_barrier_wait(&a->bar);
-
-  if (a->ok && m > 0)
-    j->rc = dx_qv_hist(j->ctx, &st.b, j->lo, &a->p, j->hist, &j->tot);     /* QV.c:988-1017, per shard */
-  pthread_barrier_wait(&a->bar);
-
-  if (j->id == 0 && (a->ok = all_ok(a)))                 /* host-side sum + Create_QVcoding */
-    { int s, x;
-      memset(a->hist, 0, sizeof(a->hist)); a->tot = 0;
-      for (k = 0; k < a->nsh; k++)
-        { for (s = 0; s < 6; s++)
-            for (x = 0; x < 256; x++)
-              a->hist[s][x] += a->jobs[k].hist[s][x];
-          a->tot += a->jobs[k].tot;
-        }
-      a->rc = dx_qv_build((const uint64_t (*)[256]) a->hist, a->tot, &a->p, a->lossy, &a->cd);
-      a->ok = a->rc == DX_OK;
-    }
-  pthread_barrier_wait(&a->bar);
-
-  if (a->ok && m > 0)                                    /* Compress_Next_QVentry for the shard's entries */
-    { rc = dx_qv_set_coding(j->ctx, &a->cd, a->lossy);
-      if (rc == DX_OK) rc = dxf_qv_encode_batch(j->ctx, &st, (const uint64_t (*)[256]) j->hist, &a->cd, a->lossy, &d_out, &out_cap, &total);
-      j->bytes = total;
-      j->rc = rc;
-    }
-  pthread_barrier_wait(&a->bar);
-
-  if (j->id == 0 && (a->ok = all_ok(a)))                 /* layout of the final image */
-    { size_t plen = a->plen, records = 0;
-      if (!a->by_bytes)
-        { const uint8_t *h = a->text, *slash = memchr(h + 1, '/', (size_t) (a->off[0] - 1));
-          plen = slash ? (size_t) (slash - h) : 0;
-        }
-      for (k = 0; k < a->nsh; k++)
-        { a->jobs[k].at = records;                        /* (behind the head, once that is known) */
-          records += a->jobs[k].bytes;
-        }
-      a->rc = qv_head(&a->cd, a->text, plen, records, &a->img, &a->head);
-      for (k = 0; k < a->nsh; k++) a->jobs[k].at += a->head;
-      a->total = a->head + records;
-      a->ok = a->rc == DX_OK;
-    }
-  pthread_barrier_wait(&a->bar);
-
-  if (a->ok && m > 0)
-    j->rc = dx_d2h(j->ctx, a->img + j->at, d_out, total);
-  if (d_out) (void) dx_free(j->ctx, d_out);
-  dfree_all(&pool);
-  return NULL;
-}
-
-/* A file too large to be indexed by one thread first (a terabyte over eight GPUs): the bytes are dealt evenly, and
- * every shard finds the records that BEGIN in its range -- a record is six lines (QV.c:948-978), so all it needs of the others is
- * how many newlines stand in front of its range --, uploads exactly those and has its own device index them (dx_index_quiva_device:
- * structure checks and all).  Anything out of the ordinary (a line count that is no multiple of six, an indexer that says no, the
- * first 100000 symbols reaching beyond shard 0) sets a->again: dx_file_dexqv_sharded then does the file the serial way, which also has
- * the reference's words for a malformed file.  Every thread passes the same five barriers.                                     */
-static int shard_slice(shard_job *j, dpool *pool, void **d_text, void **d_off, void **d_len, uint64_t *span)
-{ shard_all *a = j->all;
-  int rc = DX_OK, k;
-  { const uint8_t *q = a->text + j->p0, *e = a->text + j->p1;            /* 1: the newlines of the range as dealt */
-    uint64_t c = 0;
-    while (q < e && (q = memchr(q, '\n', (size_t) (e - q))) != NULL) { c += 1; q += 1; }
-    j->nl = c;
-  }
-  pthread_barrier_wait(&a->bar);
-  if (j->id == 0)                                        /* 2: the lines in front of every range; six lines a record, the last one whole */
-    { uint64_t before = 0;
-      for (k = 0; k < a->nsh; k++) { a->jobs[k].line0 = before; before += a->jobs[k].nl; }
-      if (before % 6 != 0 || before == 0 || a->text[a->n - 1] != '\n') a->again = 1;
-      a->cnt = before / 6;
-    }
-  pthread_barrier_wait(&a->bar);
-  if (!a->again)                                         /* 3: the first record that begins in the range */
-    { const uint8_t *q = a->text + j->p0, *e = a->text + a->n;
-      uint64_t line = j->line0;                            /* (the line p0 stands in) */
-      if (j->p0 > 0 && q[-1] != '\n')                       /* ... which began in front of the range: the next one */
-        { q = memchr(q, '\n', (size_t) (e - q)); q = q ? q + 1 : e; line += 1; }
-      while (line % 6 != 0 && q < e)
-        { q = memchr(q, '\n', (size_t) (e - q)); q = q ? q + 1 : e; line += 1; }
-      j->start = (size_t) (q - a->text);
-      j->lo = line / 6;
-    }
-  pthread_barrier_wait(&a->bar);
-  if (!a->again)                                         /* 4: the shard's records, to its device, indexed there */
-    { const size_t end = j->id + 1 < a->nsh ? a->jobs[j->id + 1].start : a->n;
-      uint64_t cnt = 0, el = 0;
-      int      ec = 0;
-      j->hi = j->id + 1 < a->nsh ? a->jobs[j->id + 1].lo : a->cnt;
-      *span = end - j->start;
-      if (j->hi > j->lo)
-        { uint64_t *go = NULL; uint32_t *gl = NULL;
-          size_t plen = 0;
-          rc = dupload(pool, a->text + j->start, (size_t) *span, d_text);
-          if (rc == DX_OK) rc = dx_index_quiva_device(j->ctx, *d_text, *span, &go, &gl, &cnt, &j->hdr4, &plen, &el, &ec);
-          if (rc == DX_OK && cnt > 0) { pool->p[pool->n++] = go; pool->p[pool->n++] = gl; *d_off = go; *d_len = gl; }
-          if (rc == DX_OK && cnt != j->hi - j->lo) rc = DX_E_FORMAT;
-          if (rc == DX_OK && (j->len = malloc((size_t) cnt * 4)) == NULL) rc = DX_E_NOMEM;
-          if (rc == DX_OK) rc = dx_d2h(j->ctx, j->len, gl, (size_t) cnt * 4);
-          if (j->id == 0) a->plen = plen;
-        }
-      else if (j->hi < j->lo) rc = DX_E_FORMAT;
-      if (rc != DX_OK) { j->rc = rc; }
-    }
-  pthread_barrier_wait(&a->bar);
-  if (j->id == 0 && !a->again)                           /* the entry at which the running symbol count reaches 100000 (QV.c:1006-1015) */
-    { uint64_t run = 0, e2 = 0, m0 = a->jobs[0].hi - a->jobs[0].lo;
-      for (k = 0; k < a->nsh; k++) if (a->jobs[k].rc != DX_OK || a->jobs[k].hi <= a->jobs[k].lo) a->again = 1;
-      for (e2 = 0; !a->again && e2 < m0; e2++)
-        { run += a->jobs[0].len[e2];
-          if (run >= 100000) break;
-        }
-      if (!a->again && e2 >= m0) a->again = 1;             /* (not within shard 0: a small file, the serial way knows what to do) */
-      a->cut = e2;
-    }
-  pthread_barrier_wait(&a->bar);
-  if (a->again) { j->hi = j->lo; return DX_E_FORMAT; }
-  return rc;
-}
-
-#define DX_SHARD_BYTES_MIN ((size_t) 64 << 20)           /* per shard: from here on the shards index their own byte ranges */
-int dx_file_dexqv_sharded(dx_ctx **ctxs, int nctx, const uint8_t *text, size_t n, int lossy,
-                          uint8_t **out, size_t *out_len, uint64_t *errline, int *errcode)
-{ shard_all  a;
-  pthread_t *th = NULL;
-  quiva_index qx = { 0, NULL, NULL, NULL, 0 };
-  int        rc, k, started = 0, by_bytes;
-
-  if (ctxs == NULL || nctx < 1 || out == NULL || out_len == NULL) return DX_E_ARG;
-  if (nctx == 1) return dx_file_dexqv(ctxs[0], text, n, lossy, out, out_len, errline, errcode);
-  *out = NULL; *out_len = 0;
-  { const size_t least = (size_t) dx_test_num("shard_bytes_min", (long long) DX_SHARD_BYTES_MIN);     /* (tests: the by-bytes way on small files) */
-    by_bytes = n / (size_t) nctx >= least && n / (size_t) nctx >= 4096 && !dx_test_on("host_index");
-  }
-again:
-  memset(&a, 0, sizeof(a));
-  started = 0;
-  a.jobs = calloc((size_t) nctx, sizeof(*a.jobs));
-  th = calloc((size_t) nctx, sizeof(*th));
-  if (!a.jobs || !th) { rc = DX_E_NOMEM; goto done; }
-  a.nsh = nctx; a.lossy = lossy; a.text = text; a.n = n; a.rc = DX_OK; a.by_bytes = by_bytes;
-
-  if (!by_bytes)                                          /* the whole file indexed here first (small files; what the shards turn down) */
-    { TRY(dxf_quiva_index_host(&qx, text, n, errline, errcode));
-      a.off = qx.off; a.len = qx.len; a.hdr4 = qx.hdr4; a.cnt = qx.cnt;
-      { uint64_t run = 0, e;
-        a.cut = 0;
-        for (e = 0; e < qx.cnt; e++)
-          { run += qx.len[e];
-            if (run >= 100000) break;
-          }
-        a.cut = e < qx.cnt ? e : 0;             /* never reached: no subChar at all, shard 0 finds that too */
-      }
-    }
-  pthread_barrier_init(&a.bar, NULL, (unsigned) nctx);
-  pthread_mutex_init(&a.gate_mx, NULL);
-  pthread_cond_init(&a.gate_cv, NULL);
-  a.go = 0; a.ok = 1;
-  { uint64_t per = qx.cnt / (uint64_t) nctx, extra = qx.cnt % (uint64_t) nctx, lo = 0;
-    for (k = 0; k < nctx; k++)
-      { uint64_t m = per + ((uint64_t) k < extra ? 1 : 0);
-        a.jobs[k].all = &a; a.jobs[k].ctx = ctxs[k]; a.jobs[k].id = k;
-        a.jobs[k].lo = lo; a.jobs[k].hi = lo + m; a.jobs[k].rc = DX_OK;
-        lo += m;
-        a.jobs[k].p0 = (size_t) ((unsigned __int128) n * (unsigned) k / (unsigned) nctx);        /* (by bytes: the range as dealt) */
-        a.jobs[k].p1 = (size_t) ((unsigned __int128) n * (unsigned) (k + 1) / (unsigned) nctx);
-      }
-  }
-  for (k = 0; k < nctx; k++)                              /* the barriers count nctx threads: all of them or none */
-    { if (pthread_create(&th[k], NULL, shard_main, &a.jobs[k]) != 0) break;
-      started += 1;
-    }
-  pthread_mutex_lock(&a.gate_mx);
-  a.go = started == nctx ? 1 : -1;
-  pthread_cond_broadcast(&a.gate_cv);
-  pthread_mutex_unlock(&a.gate_mx);
-  for (k = 0; k < started; k++)
-    pthread_join(th[k], NULL);
-  if (started < nctx)
-    rc = DX_E_NOMEM;
-  else
-    { rc = a.rc;
-      for (k = 0; k < nctx && rc == DX_OK; k++)
-        rc = a.jobs[k].rc;
-    }
-  if (rc == DX_OK && !a.again)
-    { *out = a.img; *out_len = a.total; a.img = NULL; }
-
-  pthread_barrier_destroy(&a.bar);
-  pthread_mutex_destroy(&a.gate_mx);
-  pthread_cond_destroy(&a.gate_cv);
-done:
-  for (k = 0; a.jobs != NULL && k < nctx; k++) { free(a.jobs[k].hdr4); free(a.jobs[k].len); }
-  dxf_quiva_index_free(&qx);
-  memset(&qx, 0, sizeof(qx));
-  free(a.jobs); free(th); free(a.img);
-  th = NULL;
-  if (by_bytes && a.again && started == nctx)            /* the shards turned the file down: the serial way (and its words for what is wrong) */
-    { by_bytes = 0;
-      goto again;
-    }
   return rc;
 }

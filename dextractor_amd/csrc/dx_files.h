@@ -3,7 +3,9 @@
  *
  *     dx_files.c       what every driver uses, and the decoded text on its way out (header lines laid over it, slices of it)
  *     dx_file_pack2.c  dexta / dexar (whole, streamed, sharded), undexta / undexar
- *     dx_file_qv.c     dexqv (whole, sliced, sharded), undexqv plan / run
+ *     dx_file_qv.c     dexqv (whole, sliced), undexqv plan / run
+ *     dx_file_qv_shard.c  dexqv sharded: a table of phases that a crew of threads walks, one per context
+ *     dx_crew.c        that crew (dx_crew.h; dx_file_pack2_sharded is a crew of one phase): the library's only barrier wait
  *     dx_file_check.c  an image of any kind and its text where it is made: dx_file_verify, dx_file_digest, dx_file_census
  *     dx_select.c      the .qvs entry API, the .bps / .arw read loader
  *
@@ -22,14 +24,26 @@
 #define DX_GPU_INDEX_MIN (1u << 20)      /* .quiva images from 1 MiB on are indexed on the GPU */
 
 /* ---- device arrays that are freed together -------------------------------------------------------------------------- */
-typedef struct { void *p[24]; int n; dx_ctx *ctx; } dpool;
+#define DPOOL_SLOTS 24
+typedef struct { void *p[DPOOL_SLOTS]; int n; dx_ctx *ctx; } dpool;
 
 static inline int dalloc(dpool *pool, size_t bytes, void **out)
 { int rc;
-  if (pool->n >= (int) (sizeof(pool->p) / sizeof(pool->p[0])) - 2) return DX_E_NOMEM;   /* pool slots exhausted */
+  if (pool->n >= DPOOL_SLOTS) return DX_E_NOMEM;         /* pool slots exhausted */
   rc = dx_malloc(pool->ctx, bytes + 64, out);
   if (rc == DX_OK) pool->p[pool->n++] = *out;
   return rc;
+}
+
+/* a device array made elsewhere (an indexer's) joins the pool: the pool's to free from here on, or freed at once when no slot is left
+   (DX_E_NOMEM, nothing else) -- never the caller's again */
+static inline int dadopt(dpool *pool, void *p)
+{ if (pool->n >= DPOOL_SLOTS)
+    { (void) dx_free(pool->ctx, p);
+      return DX_E_NOMEM;
+    }
+  pool->p[pool->n++] = p;
+  return DX_OK;
 }
 
 static inline int dupload(dpool *pool, const void *src, size_t bytes, void **out)
@@ -143,6 +157,10 @@ typedef struct { uint64_t cnt, *off; uint32_t *len; int32_t *hdr4; size_t plen; 
 DXF_HIDDEN int  dxf_quiva_index_host(quiva_index *qx, const uint8_t *text, size_t n, uint64_t *errline, int *errcode);
 DXF_HIDDEN void dxf_quiva_index_free(quiva_index *qx);
 
+/* where entry e's five lines end in the text */
+static inline uint64_t dxf_quiva_end(const quiva_index *qx, uint64_t e)
+{ return qx->off[e] + 5 * ((uint64_t) qx->len[e] + 1); }
+
 DXF_HIDDEN dx_qv_batch dxf_qv_batch(const void *d_text, const void *d_off, const void *d_len, uint64_t m, uint64_t span, int line_pad);
 
 /* A batch of entries as the encoder wants it: the text (b), the framing bytes of the headers and their offsets (none of either for the bare
@@ -154,6 +172,10 @@ DXF_HIDDEN int dxf_qv_stage(dpool *pool, const int32_t *hdr4, uint64_t m, int32_
                             uint64_t span, int line_pad, qv_staged *s);
 DXF_HIDDEN int dxf_qv_encode_batch(dx_ctx *ctx, const qv_staged *s, const uint64_t (*hist)[256], const dx_qv_coding *cd, int lossy,
                                    void **d_out, size_t *out_cap, uint64_t *total);
+
+/* the head of a .dexqv image: the key and the coding, the prefix being the text's first plen bytes.  *img: malloc'd, `head` bytes written,
+   room for `more` behind them */
+DXF_HIDDEN int dxf_qv_head(const dx_qv_coding *cd, const uint8_t *text, size_t plen, size_t more, uint8_t **img, size_t *head);
 
 struct dx_undexqv_plan
   { const uint8_t *img;
