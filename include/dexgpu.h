@@ -167,8 +167,17 @@ int dx_index_seq(int arrow, const uint8_t *text, size_t n, uint64_t cap,
  * and entry index on the device; only the header lines come back to the host, where sscanf parses
  * them as QV.c:964 does.  Same results as dx_index_quiva.  *d_off / *d_len are device arrays
  * (release with dx_free), *hdr4 a host array (free()).  On DX_E_FORMAT *errline / *errcode name an
- * offending line; callers that need the reference's exact first message re-run dx_index_quiva
- * on the host copy (the error path is not performance relevant).                               */
+ * offending line, found in three steps.  (1) The text's last byte is looked at first and on its own: a
+ * header or a first data line without its newline is DX_IDX_NO_NEWLINE at the last line, whatever stands
+ * in front of it; where that is the text's one defect, line and code are dx_index_quiva's.  (2) Then the
+ * kernels check every entry for no '@', an empty header, no '/', ragged and missing data lines: of these
+ * the lowest line is named, in whichever workgroup it lies, with dx_index_quiva's line and code where
+ * the text has no defect of another step.  (3) The header fields are parsed only once (2) has passed: a
+ * header whose fields do not parse, standing in front of a defect of (1) or (2), is refused too, but at
+ * the later line.  (The sentence "the lowest offending line number wins" at the top of
+ * csrc/dx_index.hip is to be read with these limits: it holds within step (2).)  Callers that need the
+ * reference's exact first message re-run dx_index_quiva on the host copy (the error path is not
+ * performance relevant).  d_text needs no alignment.                                              */
 int dx_index_quiva_device(dx_ctx *ctx, const uint8_t *d_text, uint64_t nbytes,
                           uint64_t **d_off, uint32_t **d_len, uint64_t *count,
                           int32_t **hdr4, size_t *prefix_len, uint64_t *errline, int *errcode);
@@ -176,8 +185,12 @@ int dx_parse_quiva_headers(const uint8_t *blob, const uint64_t *pos, uint64_t n,
                            size_t *prefix_len, uint64_t *bad_entry);
 
 /* The same for a .fasta (arrow = 0) / .arrow (arrow = 1) image: records are delimited on the device by
- * their header lines ('>' first); results as dx_index_seq.  On DX_E_FORMAT re-run dx_index_seq on the
- * host copy for the reference's exact first message.                                             */
+ * their header lines ('>' first); results as dx_index_seq.  On DX_E_FORMAT a text whose one defect is a line that
+ * is too long, a first line that is no header or a missing final newline is refused with dx_index_seq's line
+ * and code.  With several defects the order is the device's: the last byte is looked at first (a missing final
+ * newline is named whatever stands in front of it), then the lines, then the headers' fields; a header that
+ * does not parse is DX_IDX_BAD_HEADER at *errline = 0.  Re-run dx_index_seq on the host copy for the
+ * reference's exact first message.  d_text needs no alignment.                                   */
 int dx_index_seq_device(dx_ctx *ctx, int arrow, const uint8_t *d_text, uint64_t nbytes,
                         uint64_t **d_off, uint32_t **d_tlen, uint32_t **d_nsym, uint64_t *count,
                         int32_t **hdr4, uint16_t **cnr4, size_t *prefix_len,
