@@ -11,16 +11,14 @@ import pytest
 from _flags import set_flag
 
 import _oracle as O
+from _pack2_cases import LETTERS, NUMBER_ARROW, NUMBER_READ
 from dextractor_amd import _lib as L
 from dextractor_amd import api
 
 pytestmark = pytest.mark.gpu
 
-LETTERS = {L.DX_LETTERS_LOWER: b"acgt", L.DX_LETTERS_UPPER: b"ACGT", L.DX_LETTERS_ARROW: b"1234", L.DX_LETTERS_NUMBERS: bytes(range(4))}
 DELIM = {L.DX_LETTERS_LOWER: 0, L.DX_LETTERS_UPPER: 0, L.DX_LETTERS_ARROW: 0, L.DX_LETTERS_NUMBERS: 4}   # DB.c:367-389, DB.c:362
 ALL_LETTERS = sorted(LETTERS)
-NUMBER_READ = bytes(1 if chr(c) in "cC" else 2 if chr(c) in "gG" else 3 if chr(c) in "tT" else 0 for c in range(256))    # DB.c:393-416
-NUMBER_ARROW = bytes(0 if chr(c) == "1" else 1 if chr(c) == "2" else 2 if chr(c) in "3G" else 3 for c in range(256))     # DB.c:418-441
 FILL, GUARD = 0xEE, 64
 TRANSPORTS = ["reads_packed", "reads_whole"]
 
