@@ -190,6 +190,8 @@ SIGNATURES = {
     "dx_file_subset_layout": (C.c_int, [C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t),
                                         C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "dx_file_subset": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "dx_file_extract": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_P),
+                                  C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),
@@ -202,6 +204,7 @@ SIGNATURES = {
     "dx_entries_uncompress": (C.c_int, [_P, C.POINTER(QVCoding), C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int,
                                         C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "dx_reads_unpack": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
+    "dx_reads_unpack_lines": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, C.POINTER(C.c_uint64)]),
     "dx_reads_uncompress": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P, _P, _P, C.c_uint64,
                                       C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "dx_synth_quiva": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.c_int,

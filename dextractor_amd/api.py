@@ -611,6 +611,42 @@ class Context:
         finally:
             self.lib.dx_file_free(out)
 
+    # ---- extract -----------------------------------------------------------------------------------
+    def reads_unpack_lines(self, letters, d_in, in_bytes, d_boff, d_beg, d_len, n, width, d_out, d_out_off):
+        """dx_reads_unpack_lines: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
+        whole reads from symbol 0) as the lines undexta -w<width> prints for them -- d_len[j] + ceil(d_len[j] / width) bytes at d_out +
+        d_out_off[j], not a byte outside them.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie
+        inside the in_bytes."""
+        bad = C.c_uint64()
+        rc = self.lib.dx_reads_unpack_lines(self.h, int(letters), d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
+                                            d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), int(width),
+                                            d_out.ptr if d_out else None, d_out_off.ptr if d_out_off else None, C.byref(bad))
+        if rc != 0:
+            raise self._bad_unit(rc, bad)
+
+    def extract(self, kind, img: bytes, ids=None, beg=None, end=None, upper=False, width=80, offsets=False):
+        """dx_file_extract: the text undexta [-U] [-w<width>] / undexar [-w<width>] / undexqv [-U] prints for img's records ids alone
+        (None: all of them; with beg and end too: records 0 .. len(beg) - 1), in that order -- any order, and an id may repeat --, whole
+        or cut to [beg[j], end[j]).  kind: "fasta", "arrow" or "quiva" (which ignores width).  offsets: (text, toff) with toff[j] where
+        unit j's header line begins and toff[n] = len(text)."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        ids, beg, end, n = _subset_selection(ids, beg, end)
+        every = n is None
+        out, ln, toff = C.c_void_p(), C.c_size_t(), C.c_void_p()
+        self._chk(self.lib.dx_file_extract(self.h, k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), 2 ** 64 - 1 if every else n,
+                                           int(bool(upper)), int(width), C.byref(out), C.byref(ln), C.byref(toff) if offsets else None))
+        try:
+            text = C.string_at(out.value, ln.value)
+            if not offsets:
+                return text
+            if every:                                        # (the count is the library's; every unit has a header line, so the
+                n, at = 0, C.cast(toff, C.POINTER(C.c_uint64))   #  offsets rise, and the first that is the text's length is the last)
+                while at[n] != ln.value:
+                    n += 1
+            return text, np.ctypeslib.as_array(C.cast(toff, C.POINTER(C.c_uint64)), (n + 1,)).copy()
+        finally:
+            self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
+
     def qv_subindex(self, on=True):
         self._chk(self.lib.dx_qv_subindex(self.h, int(bool(on))))
 

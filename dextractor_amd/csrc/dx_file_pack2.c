@@ -477,7 +477,20 @@ static uint16_t rd_u16(rsrc *r, int flip) { uint16_t v; rd(r, &v, 2); return fli
 void dxf_u2_index_free(u2_index *x)
 { free(x->ioff); free(x->hat); free(x->nsym); free(x->hd.p); free(x->hdr4); free(x->cnr4); }
 
-#define U2_NOT_YET 1                /* (a piece of an image that arrives in pieces: its head is not all here yet; nothing consumed) */
+int dxf_u2_header(tbuf *b, int arrow, const char *name, int well, int beg, int end, int qv, const uint16_t *cnr)
+{ int rc, k;
+  if ((rc = dxf_tb_room(b, strlen(name) + 160)) != DX_OK) return rc;
+  if (arrow)                                              /* undexar.c:199-203 */
+    { float snr[4];
+      for (k = 0; k < 4; k++) snr[k] = (float) (cnr[k] / 100.);
+      b->len += (size_t) sprintf(b->p + b->len, "%s/%d/%d_%d SN=%.2f,%.2f,%.2f,%.2f\n", name, well, beg, end, snr[0], snr[1], snr[2], snr[3]);
+    }
+  else                                                    /* undexta.c:242 */
+    b->len += (size_t) sprintf(b->p + b->len, "%s/%d/%d_%d RQ=0.%d\n", name, well, beg, end, qv);
+  return DX_OK;
+}
+
+#define U2_NOT_YET 1               /* (a piece of an image that arrives in pieces: its head is not all here yet; nothing consumed) */
 
 /* mode: DX_LETTERS_LOWER / _UPPER (dexta images) or _ARROW (dexar images); st: the image arrives in pieces (else NULL) */
 int dxf_u2_walk(int mode, const uint8_t *img, size_t n, u2_state *st, u2_index *x)
@@ -570,16 +583,8 @@ int dxf_u2_walk(int mode, const uint8_t *img, size_t n, u2_state *st, u2_index *
           if ((t = realloc(x->cnr4, cap * 4 * sizeof(*x->cnr4))) == NULL) { rc = DX_E_NOMEM; goto done; }
           x->cnr4 = t;
         }
-      if ((rc = dxf_tb_room(&x->hd, (size_t) plen + 160)) != DX_OK) goto done;
       x->hat[cnt] = x->hd.len;
-      if (arrow)                                          /* undexar.c:199-203 */
-        { float snr[4];
-          for (k = 0; k < 4; k++) snr[k] = (float) (cnr[k] / 100.);
-          x->hd.len += (size_t) sprintf(x->hd.p + x->hd.len, "%s/%d/%d_%d SN=%.2f,%.2f,%.2f,%.2f\n", name, well, beg, end,
-                                        snr[0], snr[1], snr[2], snr[3]);
-        }
-      else                                                /* undexta.c:242 */
-        x->hd.len += (size_t) sprintf(x->hd.p + x->hd.len, "%s/%d/%d_%d RQ=0.%d\n", name, well, beg, end, qv);
+      if ((rc = dxf_u2_header(&x->hd, arrow, name, well, beg, end, qv, cnr)) != DX_OK) goto done;
 
       x->ioff[cnt] = r.at;
       x->nsym[cnt] = rlen;

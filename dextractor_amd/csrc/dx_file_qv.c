@@ -377,10 +377,16 @@ void dx_file_undexqv_plan_free(dx_undexqv_plan *p)
   free(p);
 }
 
+int dxf_qv_header(tbuf *b, const char *prefix, const int32_t *h4)
+{ int rc;
+  if ((rc = dxf_tb_room(b, strlen(prefix) + 80)) != DX_OK) return rc;
+  b->len += (size_t) sprintf(b->p + b->len, "%s/%d/%d_%d RQ=0.%d\n", prefix, h4[0], h4[1], h4[2], h4[3]);
+  return DX_OK;
+}
+
 /* header lines (undexqv.c:182) and where every entry's lines go in the text, from p->x.n / len / hdr4 / prefix */
 static int plan_layout(dx_undexqv_plan *p)
-{ const size_t plen = strlen(p->x.prefix);
-  size_t   total = 0;
+{ size_t   total = 0;
   uint64_t i;
   int      rc;
   p->ooff = malloc((p->x.n + 1) * sizeof(*p->ooff));
@@ -388,9 +394,8 @@ static int plan_layout(dx_undexqv_plan *p)
   if (!p->ooff || !p->hat) return DX_E_NOMEM;
   for (i = 0; i < p->x.n; i++)
     { const int32_t *h = p->x.hdr4 + 4*i;
-      if ((rc = dxf_tb_room(&p->hd, plen + 80)) != DX_OK) return rc;
       p->hat[i]  = p->hd.len;
-      p->hd.len += (size_t) sprintf(p->hd.p + p->hd.len, "%s/%d/%d_%d RQ=0.%d\n", p->x.prefix, h[0], h[1], h[2], h[3]);
+      if ((rc = dxf_qv_header(&p->hd, p->x.prefix, h)) != DX_OK) return rc;
       total     += p->hd.len - (size_t) p->hat[i];
       p->ooff[i] = total;
       total     += 5 * ((size_t) p->x.len[i] + 1);        /* undexqv.c:206-207 */

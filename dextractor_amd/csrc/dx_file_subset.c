@@ -17,16 +17,9 @@
 #include "dx_files.h"
 
 /* ==========================================================================================
- *  the selection: unit j is record ids[j] (ids == NULL: j), all of it or its symbols [beg[j], end[j])
+ *  the selection (dx_files.h): unit j is record ids[j] (ids == NULL: j), all of it or its symbols [beg[j], end[j])
  * ========================================================================================== */
-typedef struct { const uint64_t *ids; const uint32_t *beg, *end; uint64_t n; } selection;
-
-static uint64_t sel_id(const selection *s, uint64_t j)                      { return s->ids ? s->ids[j] : j; }
-static uint32_t sel_beg(const selection *s, uint64_t j)                     { return s->beg ? s->beg[j] : 0; }
-static uint32_t sel_end(const selection *s, uint64_t j, const uint32_t *rl) { return s->end ? s->end[j] : rl[sel_id(s, j)]; }
-
-/* DX_E_ARG with the unit named (dx_last_error) unless the ids are non-decreasing and below cnt, and every interval lies in its record */
-static int sel_check(dx_ctx *ctx, selection *s, uint64_t cnt, const uint32_t *rlen)
+int dxf_sel_check(dx_ctx *ctx, const char *who, selection *s, uint64_t cnt, const uint32_t *rlen, int ordered)
 { uint64_t j, last = 0;
   if (s->ids == NULL && s->n == UINT64_MAX)               /* every record of the image */
     { if (cnt == 0) return DX_E_DEGENERATE;
@@ -34,24 +27,29 @@ static int sel_check(dx_ctx *ctx, selection *s, uint64_t cnt, const uint32_t *rl
     }
   for (j = 0; j < s->n; j++)
     { const uint64_t id = sel_id(s, j);
-      if (id < last)  return dx_unit_fail(ctx, DX_E_ARG, "dx_file_subset", j, "its id is below the one in front of it");
-      if (id >= cnt)  return dx_unit_fail(ctx, DX_E_ARG, "dx_file_subset", j, "its id is not below the image's record count");
-      if (s->beg != NULL && s->beg[j] > s->end[j]) return dx_unit_fail(ctx, DX_E_ARG, "dx_file_subset", j, "beg > end");
-      if (s->beg != NULL && s->end[j] > rlen[id])  return dx_unit_fail(ctx, DX_E_ARG, "dx_file_subset", j, "end > the record's length");
+      if (ordered && id < last) return dx_unit_fail(ctx, DX_E_ARG, who, j, "its id is below the one in front of it");
+      if (id >= cnt)  return dx_unit_fail(ctx, DX_E_ARG, who, j, "its id is not below the image's record count");
+      if (s->beg != NULL && s->beg[j] > s->end[j]) return dx_unit_fail(ctx, DX_E_ARG, who, j, "beg > end");
+      if (s->beg != NULL && s->end[j] > rlen[id])  return dx_unit_fail(ctx, DX_E_ARG, who, j, "end > the record's length");
       last = id;
     }
   return DX_OK;
 }
 
-/* what every entry point asks of its arguments before it looks at the image */
-static int sel_args(dx_ctx *ctx, const uint8_t *img, const uint64_t *ids, const uint32_t *beg, const uint32_t *end, uint64_t n_ids)
+int dxf_sel_args(dx_ctx *ctx, const char *who, const uint8_t *img, const uint64_t *ids, const uint32_t *beg, const uint32_t *end, uint64_t n_ids)
 { if (img == NULL) return DX_E_ARG;
   if ((beg == NULL) != (end == NULL))
-    return dx_unit_fail(ctx, DX_E_ARG, "dx_file_subset", 0, "beg and end are given together, or neither");
+    return dx_unit_fail(ctx, DX_E_ARG, who, 0, "beg and end are given together, or neither");
   if (n_ids == UINT64_MAX && (ids != NULL || beg != NULL))              /* (every record whole: no arrays to go with it) */
-    return dx_unit_fail(ctx, DX_E_ARG, "dx_file_subset", 0, "n_ids == UINT64_MAX (every record) goes with ids == beg == end == NULL");
+    return dx_unit_fail(ctx, DX_E_ARG, who, 0, "n_ids == UINT64_MAX (every record) goes with ids == beg == end == NULL");
   return n_ids == 0 ? DX_E_DEGENERATE : DX_OK;
 }
+
+/* dx_file_subset's own: its ids do not decrease (dexta's well-delta chain cannot say otherwise) */
+static int sel_check(dx_ctx *ctx, selection *s, uint64_t cnt, const uint32_t *rlen) { return dxf_sel_check(ctx, "dx_file_subset", s, cnt, rlen, 1); }
+
+static int sel_args(dx_ctx *ctx, const uint8_t *img, const uint64_t *ids, const uint32_t *beg, const uint32_t *end, uint64_t n_ids)
+{ return dxf_sel_args(ctx, "dx_file_subset", img, ids, beg, end, n_ids); }
 
 /* ==========================================================================================
  *  fasta / arrow: the framing anew (dexta.c:124-129, 187-198; dexar.c:193-204), the payload where it lies

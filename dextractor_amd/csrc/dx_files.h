@@ -9,6 +9,7 @@
  *     dx_file_check.c  an image of any kind and its text where it is made: dx_file_verify, dx_file_digest, dx_file_census
  *     dx_select.c      the .qvs entry API, the .bps / .arw read loader
  *     dx_file_subset.c a new image cut out of an old one: dx_file_subset_layout (host), dx_file_subset
+ *     dx_file_extract.c chosen records as text: dx_file_extract
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
  */
@@ -152,6 +153,9 @@ DXF_HIDDEN size_t dxf_u2_layout(const u2_index *x, uint32_t width, uint64_t *oof
 DXF_HIDDEN int    dxf_unpack2_slices(dx_ctx *ctx, int mode, const uint8_t *img, size_t n, uint32_t width, const u2_index *x, const hdr_patch *h,
                                      size_t cap, slice_fn deliver, void *arg);
 
+/* a read's header line as undexta / undexar print it (undexta.c:242, undexar.c:199-203) behind what b holds; the walk's own printer */
+DXF_HIDDEN int    dxf_u2_header(tbuf *b, int arrow, const char *name, int well, int beg, int end, int qv, const uint16_t *cnr);
+
 /* ---- dx_file_qv.c ---------------------------------------------------------------------------------------------------- */
 /* The host's index of a .quiva text (dx_index_quiva): per entry where its five lines begin, how long they are, the header's four fields */
 typedef struct { uint64_t cnt, *off; uint32_t *len; int32_t *hdr4; size_t plen; } quiva_index;
@@ -193,8 +197,46 @@ struct dx_undexqv_plan
 #define PLAN_HAS_IMAGE(p) ((p)->ctx != NULL && (p)->d_in != NULL)
 #define PLAN_HAS_INDEX(p) ((p)->ctx != NULL && (p)->dix.d_rec_off != NULL)
 
+/* an entry's header line as undexqv prints it (undexqv.c:182) behind what b holds: h4 = well, beg, end, qv; the plan's own printer */
+DXF_HIDDEN int    dxf_qv_header(tbuf *b, const char *prefix, const int32_t *h4);
+
 /* a plan's text in slices of whole entries, at most `cap` bytes of text each (0: in one), each to `deliver`; and the cap the device asks for */
 DXF_HIDDEN int    dxf_undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_fn deliver, void *arg, size_t cap, int whole_in_);
 DXF_HIDDEN size_t dxf_undexqv_cap(dx_ctx *ctx, const dx_undexqv_plan *p, int *whole_in);
+
+/* ---- dx_select.c ----------------------------------------------------------------------------------------------------- */
+/* the span of the input that a unit of a selection can reach, and the unit it belongs to */
+typedef struct { uint64_t lo, hi, j; } rspan;
+
+/* What decodes a slice -- units [j0, j0 + m) of the selection.  Their input is at d_in, in_bytes of it: the whole input, or (packed) the
+   slice's own spans side by side; unit j0 + k begins at d_start[k] of it, and its text goes to d_out + d_ooff[k].  `pool` lives as long as
+   the slice: for the hook's own arrays.  DX_E_FORMAT with *bad = k: unit j0 + k does not end inside the input. */
+typedef int (*sel_fn)(void *arg, dpool *pool, const void *d_in, uint64_t in_bytes, const uint64_t *d_start, const uint64_t *d_ooff,
+                      uint64_t j0, uint64_t m, int packed, void *d_out, uint64_t *bad);
+
+/* The one loader of a selection: n_ids units of the nbytes at `in`.  Unit j can reach the span un[j] of them, its first byte is at at[j]
+   (cut at the input's end or not), and its text goes to res + to[j] (to[n_ids]: the text's end).  The input goes up whole or packed
+   (packed_key / whole_key of DEXGPU_TEST decide for a test) -- or is taken where it is: d_have, the whole input on ctx's device
+   already --, the text is made in slices of whole units that fit the device (dxf_out_cap), every slice by `fn` and down to its place in
+   res.  A unit that `fn` turns down is named as the caller knows it: ids[j] (ids == NULL: j), which starts at start[id] (dx_entry_fail). */
+DXF_HIDDEN int dxf_sel_slices(dx_ctx *ctx, const uint8_t *in, size_t nbytes, const void *d_have, const rspan *un, const uint64_t *at,
+                              const uint64_t *to, const uint64_t *ids, uint64_t n_ids, const uint64_t *start, const char *packed_key,
+                              const char *whole_key, sel_fn fn, void *arg, uint8_t *res);
+
+/* ---- dx_file_subset.c ------------------------------------------------------------------------------------------------ */
+/* the selection of dx_file_subset and dx_file_extract: unit j is record ids[j] (ids == NULL: j), all of it or its symbols [beg[j], end[j]) */
+typedef struct { const uint64_t *ids; const uint32_t *beg, *end; uint64_t n; } selection;
+
+static inline uint64_t sel_id(const selection *s, uint64_t j)                      { return s->ids ? s->ids[j] : j; }
+static inline uint32_t sel_beg(const selection *s, uint64_t j)                     { return s->beg ? s->beg[j] : 0; }
+static inline uint32_t sel_end(const selection *s, uint64_t j, const uint32_t *rl) { return s->end ? s->end[j] : rl[sel_id(s, j)]; }
+
+/* what an entry point (`who`) asks of its arguments before it looks at the image: DX_E_DEGENERATE for n_ids == 0 */
+DXF_HIDDEN int dxf_sel_args(dx_ctx *ctx, const char *who, const uint8_t *img, const uint64_t *ids, const uint32_t *beg, const uint32_t *end,
+                            uint64_t n_ids);
+/* ... and of the selection once the image's cnt records and their lengths are known: DX_E_ARG with the unit named (dx_last_error) unless the
+   ids are below cnt -- and, `ordered`, do not decrease -- and every interval lies in its record.  n == UINT64_MAX becomes cnt
+   (DX_E_DEGENERATE when that is 0) */
+DXF_HIDDEN int dxf_sel_check(dx_ctx *ctx, const char *who, selection *s, uint64_t cnt, const uint32_t *rlen, int ordered);
 
 #endif

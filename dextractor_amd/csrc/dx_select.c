@@ -112,8 +112,6 @@ done:
  *  else the whole input goes up once -- unless the input, with a slice of 4 MB of text beside it, is
  *  more than the device has free: then the packed way is taken, since a slice's spans are what has to fit.
  * ========================================================================================== */
-typedef struct { uint64_t lo, hi, j; } rspan;
-
 static int rspan_cmp(const void *a, const void *b)
 { const rspan *x = a, *y = b;
   return x->lo < y->lo ? -1 : x->lo > y->lo ? 1 : x->j < y->j ? -1 : x->j > y->j;
@@ -158,35 +156,26 @@ static uint64_t sel_slice_end(const uint64_t *to, uint64_t j0, uint64_t n_ids, s
   return j1;
 }
 
-/* What decodes a slice -- units [j0, j0 + m) of the selection.  Their input is at d_in, in_bytes of it: the whole input, or (packed) the
-   slice's own spans side by side; unit j0 + k begins at d_start[k] of it, and its text goes to d_out + d_ooff[k].  `pool` lives as long as
-   the slice: for the hook's own arrays.  DX_E_FORMAT with *bad = k: unit j0 + k does not end inside the input. */
-typedef int (*sel_fn)(void *arg, dpool *pool, const void *d_in, uint64_t in_bytes, const uint64_t *d_start, const uint64_t *d_ooff,
-                      uint64_t j0, uint64_t m, int packed, void *d_out, uint64_t *bad);
-
-/* The one loader of a selection: n_ids units of the nbytes at `in`.  Unit j can reach the span un[j] of them, its first byte is at at[j]
-   (cut at the input's end or not), and its text goes to res + to[j] (to[n_ids]: the text's end).  The input goes up whole or packed
-   (sel_goes_whole; packed_key / whole_key), the text is made in slices of whole units that fit the device (dxf_out_cap), every slice by
-   `fn` and down to its place in res.  A unit that `fn` turns down is named as the caller knows it: ids[j] (ids == NULL: j), which
-   starts at start[id] (dx_entry_fail). */
-static int sel_slices(dx_ctx *ctx, const uint8_t *in, size_t nbytes, const rspan *un, const uint64_t *at, const uint64_t *to,
-                      const uint64_t *ids, uint64_t n_ids, const uint64_t *start, const char *packed_key, const char *whole_key,
-                      sel_fn fn, void *arg, uint8_t *res)
+/* The one loader of a selection (dx_files.h: the hook sel_fn, and what the arguments are): whole or packed by sel_goes_whole, unless the
+   input is on the device already. */
+int dxf_sel_slices(dx_ctx *ctx, const uint8_t *in, size_t nbytes, const void *d_have, const rspan *un, const uint64_t *at,
+                   const uint64_t *to, const uint64_t *ids, uint64_t n_ids, const uint64_t *start, const char *packed_key,
+                   const char *whole_key, sel_fn fn, void *arg, uint8_t *res)
 { dpool     all = { {0}, 0, ctx }, pool = { {0}, 0, ctx };
   rspan    *sp  = malloc((n_ids + 1) * sizeof(*sp));      /* a slice's spans, as spans_pack sorts them */
   uint64_t *rel = malloc((n_ids + 1) * sizeof(*rel)), j, j0, j1, covered;
   uint8_t  *stage = NULL;
-  void     *d_whole = NULL;
+  void     *d_whole = (void *) d_have;                    /* (there already: not this call's to bring up, or to free) */
   size_t    cap;
   int       rc = DX_OK, whole;
 
   if (!sp || !rel) { rc = DX_E_NOMEM; goto done; }
   memcpy(sp, un, (size_t) n_ids * sizeof(*sp));
   covered = spans_pack(sp, n_ids, in, NULL, NULL);
-  whole   = sel_goes_whole(ctx, covered, nbytes, packed_key, whole_key);
-  cap     = dxf_out_cap(ctx, whole ? nbytes : (size_t) covered, (size_t) to[n_ids], n_ids);
-  if (whole) TRY(dupload(&all, in, nbytes, &d_whole));
-  else                                                    /* (no slice's spans are more than the selection's) */
+  whole   = d_have != NULL || sel_goes_whole(ctx, covered, nbytes, packed_key, whole_key);
+  cap     = dxf_out_cap(ctx, d_have != NULL ? 0 : whole ? nbytes : (size_t) covered, (size_t) to[n_ids], n_ids);
+  if (whole && d_have == NULL) TRY(dupload(&all, in, nbytes, &d_whole));
+  if (!whole)                                             /* (no slice's spans are more than the selection's) */
     { stage = malloc((size_t) covered + 16);
       if (stage == NULL) { rc = DX_E_NOMEM; goto done; }
     }
@@ -320,7 +309,7 @@ int dx_entries_uncompress(dx_ctx *ctx, const dx_qv_coding *coding, int flip,
 
   TRY(dx_qv_set_coding(ctx, coding, 0));
   { qvs_job q = { ctx, coding, flip, (ascii == 2 ? DX_DECODE_UPPER : 0) | (flip ? DX_DECODE_FLIP : 0), nbytes, len, bits, at, seg };
-    TRY(sel_slices(ctx, records, nbytes, un, at, to, ids, n_ids, coff, "entries_packed", "entries_whole", qvs_slice, &q, res));
+    TRY(dxf_sel_slices(ctx, records, nbytes, NULL, un, at, to, ids, n_ids, coff, "entries_packed", "entries_whole", qvs_slice, &q, res));
   }
   if (ascii == 0)                                         /* DB.c:2605-2610: the tag line through Number_Read (DB.c:393-416) */
     for (j = 0; j < n_ids; j++)
@@ -412,7 +401,7 @@ int dx_reads_uncompress(dx_ctx *ctx, int letters, const uint8_t *payload, size_t
   if (n_ids == 0) goto deliver;
 
   { reads_job r = { ctx, letters, ph, len };
-    TRY(sel_slices(ctx, payload, nbytes, un, at, to, ids, n_ids, boff, "reads_packed", "reads_whole", reads_slice, &r, res));
+    TRY(dxf_sel_slices(ctx, payload, nbytes, NULL, un, at, to, ids, n_ids, boff, "reads_packed", "reads_whole", reads_slice, &r, res));
   }
 
 deliver:

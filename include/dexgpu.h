@@ -715,6 +715,47 @@ int dx_file_subset(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
                    int lossy /* quiva */, uint8_t **out, size_t *out_len);
 
 /* ------------------------------------------------------------------------------------------
+ *  extract: chosen records as text  (undexta | a text filter today; dx_file_subset + a decoder through this library)
+ * ------------------------------------------------------------------------------------------ */
+/* dx_reads_unpack_lines (device in, device out; csrc/reads/dx_lines.hip), dx_reads_unpack with k_pack2_decode's line ends: unit j is
+ * what it is there -- symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read that starts at d_in + d_boff[j], any byte offset,
+ * any phase, d_beg == NULL: all 0 -- and leaves as T = d_len[j] + (d_len[j] + width - 1) / width bytes at d_out + d_out_off[j]
+ * (any alignment): the letters with '\n' behind every width-th one and behind the last one (undexta.c:263-270).  NOT ONE BYTE
+ * outside those T is written, and there is no delimiter: in dx_file_extract's layout the neighbours are header lines.  d_len[j] ==
+ * 0 writes nothing.  letters: DX_LETTERS_LOWER, _UPPER or _ARROW (numbers have no lines: DX_E_ARG); width >= 1 (0: DX_E_ARG, as
+ * for dx_pack2_decode), and a width beyond every length is one line a unit.  Units may overlap or repeat in the input; the outputs
+ * are the caller's to keep disjoint.  Nothing outside [0, in_bytes) is read.  Bad units are dx_reads_unpack's: DX_E_FORMAT with
+ * *bad_unit = the smallest such j (UINT64_MAX otherwise; may be NULL), checked by the kernel, one read-back a call.  n < 2^31.  */
+int dx_reads_unpack_lines(dx_ctx *ctx, int letters, const uint8_t *d_in, uint64_t in_bytes,
+                          const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len,
+                          uint64_t n, uint32_t width, uint8_t *d_out, const uint64_t *d_out_off, uint64_t *bad_unit /* may be NULL */);
+
+/* The text undexta [-U] [-w<width>] / undexar [-w<width>] / undexqv [-U] prints for chosen records of img alone (a .dexta / .dexar /
+ * .dexqv image, kind DX_KIND_*; legacy and byte-swapped layouts as the decoders take them; arrow ignores upper, quiva ignores
+ * width).  The selection is dx_file_subset's -- unit j is record ids[j], whole or its symbols [beg[j], end[j]); ids == NULL: records
+ * 0 .. n_ids - 1; n_ids == UINT64_MAX with no array: every record -- but the ids may come in ANY order (a text has no well-delta
+ * chain), and may repeat.  *text (malloc'd, dx_file_free; *text_bytes of it) has the units in the selection's order: the header line
+ * with well/B_E rewritten to well/(B + beg)_(B + end), then the sequence (quiva: each of the five lines) cut to [beg, end); a unit
+ * with beg == end is its header line alone for the 2-bit kinds, its header line and five empty lines for quiva.  (*toff)[j] (n_ids
+ * + 1 values, malloc'd; toff may be NULL) is where unit j's header line begins, (*toff)[n_ids] = *text_bytes.  For a selection
+ * dx_file_subset accepts the text is, byte for byte, dx_file_unpack2 / dx_file_undexqv of dx_file_subset's image -- without
+ * that image: nothing is framed, no coding is built, nothing is encoded.
+ * fasta / arrow: the image is walked on the host, only the selected reads' packed spans travel (dx_reads_uncompress's loader and
+ * its rule), and one dx_reads_unpack_lines a slice writes the lines where they belong.  quiva: the stream is walked as
+ * dx_file_undexqv walks it (the format stores no lengths: that cost stays), only the selected records' bytes travel unless the
+ * walk has left the image on the device, and dx_qv_decode runs on the gathered starts.  A whole entry is decoded where it ends
+ * up; for an interval the WHOLE entry is decoded into scratch first -- a Huffman stream has no way in at symbol beg -- and
+ * dx_copy_ranges gathers the five line intervals, so an interval costs its entry's decode, and an entry selected k times is
+ * decoded k times.  A selection whose text exceeds DEXGPU_TEXT_BUDGET bytes, or what is free on the device, goes in slices of whole
+ * units; the text is the same.
+ * n_ids == 0: DX_OK and an empty text.  DX_E_ARG (dx_last_error names the unit j) for an id that is not below the record count,
+ * beg[j] > end[j], end[j] > the record's length, only one of beg / end, or width == 0 for a 2-bit kind; else the decoders' errors
+ * for img.                                                                                                                    */
+int dx_file_extract(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
+                    const uint64_t *ids, const uint32_t *beg, const uint32_t *end, uint64_t n_ids,
+                    int upper, uint32_t width, uint8_t **text, size_t *text_bytes, uint64_t **toff /* n_ids + 1, may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
