@@ -77,6 +77,16 @@ class Census(C.Structure):                       # dx_census
     _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("min_len", C.c_uint32), ("max_len", C.c_uint32),
                 ("n50", C.c_uint32), ("reserved", C.c_uint32), ("code", C.c_uint64 * 4), ("hist", (C.c_uint64 * 256) * 5)]
 
+class DiffTally(C.Structure):                    # dx_diff_tally
+    _fields_ = [("differ", C.c_uint64), ("units", C.c_uint64), ("sum_abs", C.c_uint64), ("max_abs", C.c_uint64)]
+
+class Compare(C.Structure):                      # dx_compare
+    _fields_ = [("same", C.c_int32), ("lines", C.c_int32), ("prefix_differs", C.c_int32), ("reserved", C.c_int32),
+                ("records_a", C.c_uint64), ("records_b", C.c_uint64), ("headers_differ", C.c_uint64), ("first_header", C.c_uint64),
+                ("lengths_differ", C.c_uint64), ("first_length", C.c_uint64), ("records_differ", C.c_uint64),
+                ("first_record", C.c_uint64), ("first_line", C.c_uint32), ("first_column", C.c_uint32),
+                ("differ", C.c_uint64 * 5), ("line_records", C.c_uint64 * 5), ("sum_abs", C.c_uint64 * 5), ("max_abs", C.c_uint64 * 5)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
@@ -192,6 +202,11 @@ SIGNATURES = {
     "dx_file_subset": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "dx_file_extract": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_P),
                                   C.POINTER(C.c_size_t), C.POINTER(_P)]),
+    "dx_diff_ranges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, C.c_int, _P, C.c_uint64, _P, _P, _P,
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_code_diff": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64 * 2),
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_file_compare": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_int, C.POINTER(Compare), C.POINTER(_P)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

@@ -572,6 +572,62 @@ class Context:
                 self.lib.dx_file_free(rl); self.lib.dx_file_free(rc_); self.lib.dx_file_free(rs)
         return out
 
+    # ---- compare -----------------------------------------------------------------------------------
+    def diff_ranges(self, d_a, a_bytes, d_a_off, d_b, b_bytes, d_b_off, d_len, n, d_kind=None, nkinds=1, a_and=None,
+                    d_differ=None, d_first=None) -> dict:
+        """dx_diff_ranges: unit j = d_a[d_a_off[j] .. + d_len[j]) against d_b[d_b_off[j] .. + d_len[j]) (offsets uint64, lengths
+        uint32, on the device); d_kind (uint8; None: all 0) names one of nkinds (1 to 8) tallies, a_and (nkinds byte values; None:
+        all 0xff) is ANDed onto side a's bytes first.  d_differ / d_first (uint32, n, or None) get every unit's differing bytes and
+        the first of them (2**32 - 1: none).  {"differ", "units", "sum_abs", "max_abs"} (uint64 arrays, a kind each) and "first":
+        (unit, position) of the first difference, or None.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) for a
+        range outside either buffer or a kind that is not below nkinds."""
+        nk = int(nkinds)
+        tally, first, bad = (L.DiffTally * max(nk, 1))(), C.c_uint64(), C.c_uint64()
+        masks = None if a_and is None else (C.c_uint8 * max(nk, 1))(*[int(v) for v in a_and])
+        rc = self.lib.dx_diff_ranges(self.h, d_a.ptr if d_a else None, int(a_bytes), d_a_off.ptr if d_a_off else None,
+                                     d_b.ptr if d_b else None, int(b_bytes), d_b_off.ptr if d_b_off else None,
+                                     d_len.ptr if d_len else None, d_kind.ptr if d_kind else None, nk, masks, int(n),
+                                     d_differ.ptr if d_differ else None, d_first.ptr if d_first else None, tally,
+                                     C.byref(first), C.byref(bad))
+        if rc != 0:
+            raise self._bad_unit(rc, bad)
+        out = {f: np.array([getattr(t, f) for t in tally][:nk], dtype=np.uint64) for f, _ in L.DiffTally._fields_}
+        out["first"] = None if first.value == 2**64 - 1 else (first.value >> 32, first.value & 0xffffffff)
+        return out
+
+    def code_diff(self, d_a, a_bytes, d_a_boff, d_b, b_bytes, d_b_boff, d_len, n, d_differ=None, d_first=None) -> dict:
+        """dx_code_diff: unit j = the first d_len[j] symbols of the packed read at d_a + d_a_boff[j] against those of the one at
+        d_b + d_b_boff[j]; the pad bits of a read's last byte are not compared.  d_differ / d_first as for diff_ranges, in
+        symbols.  {"symbols", "units", "first": (unit, symbol) or None}.  Raises DexGPUError (DX_E_FORMAT, .bad_unit) when a unit
+        does not lie inside its side's bytes."""
+        tot, first, bad = (C.c_uint64 * 2)(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.dx_code_diff(self.h, d_a.ptr if d_a else None, int(a_bytes), d_a_boff.ptr if d_a_boff else None,
+                                   d_b.ptr if d_b else None, int(b_bytes), d_b_boff.ptr if d_b_boff else None,
+                                   d_len.ptr if d_len else None, int(n), d_differ.ptr if d_differ else None,
+                                   d_first.ptr if d_first else None, C.byref(tot), C.byref(first), C.byref(bad))
+        if rc != 0:
+            raise self._bad_unit(rc, bad)
+        return {"symbols": tot[0], "units": tot[1],
+                "first": None if first.value == 2**64 - 1 else (first.value >> 32, first.value & 0xffffffff)}
+
+    def compare(self, kind, a: bytes, b: bytes, lossy=False, per_record=False) -> dict:
+        """dx_file_compare: how two images of one kind ("fasta", "arrow" or "quiva") differ, records paired by index, compared on the
+        device without either text.  The fields of dx_compare as a dict -- `same` a bool, the first_* None when there is none, the
+        per-line fields uint64 arrays of `lines` values -- and with per_record "rec_differ": uint32 [records compared, lines].
+        lossy (quiva): side a's insertion and merge lines are masked as dexqv -l rounds them."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        cm, rec = L.Compare(), C.c_void_p()
+        self._chk(self.lib.dx_file_compare(self.h, k, a, len(a), b, len(b), int(bool(lossy)), C.byref(cm),
+                                           C.byref(rec) if per_record else None))
+        out = compare_dict(cm)
+        if per_record:
+            n, ln = min(cm.records_a, cm.records_b), cm.lines
+            try:
+                out["rec_differ"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), ((n + 1) * ln,))[:n * ln].reshape(n, ln).copy()
+            finally:
+                self.lib.dx_file_free(rec)
+        return out
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -800,6 +856,20 @@ def census_dict(cs) -> dict:
     out = {f: int(getattr(cs, f)) for f in ("records", "symbols", "min_len", "max_len", "n50")}
     out["code"] = np.array(list(cs.code), dtype=np.uint64)
     out["hist"] = np.array([list(row) for row in cs.hist], dtype=np.uint64)
+    return out
+
+
+def compare_dict(cm) -> dict:
+    """a dx_compare as Context.compare returns it"""
+    none = 2**64 - 1
+    out = {f: int(getattr(cm, f)) for f in ("lines", "records_a", "records_b", "headers_differ", "lengths_differ", "records_differ")}
+    out["same"], out["prefix_differs"] = bool(cm.same), bool(cm.prefix_differs)
+    for f in ("first_header", "first_length", "first_record"):
+        out[f] = None if getattr(cm, f) == none else int(getattr(cm, f))
+    out["first_line"] = None if out["first_record"] is None else int(cm.first_line)
+    out["first_column"] = None if out["first_record"] is None else int(cm.first_column)
+    for f in ("differ", "line_records", "sum_abs", "max_abs"):
+        out[f] = np.array(list(getattr(cm, f))[:cm.lines], dtype=np.uint64)
     return out
 
 

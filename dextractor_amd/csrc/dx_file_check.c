@@ -13,29 +13,16 @@
 /* ==========================================================================================
  *  An image of any of the three kinds and the text it decodes to, for who wants the text's slices where they are made
  *  (dx_file_verify, dx_file_digest): the image's records walked, the header lines the decoder prints, the text's layout.
+ *  image_text is in dx_files.h: dx_file_compare.c opens two of them.
  * ========================================================================================== */
-typedef struct
-  { int              kind, mode, upper;            /* DX_KIND_*; the 2-bit kinds' DX_LETTERS_*; quiva: undexqv -U */
-    uint32_t         width;                        /* the 2-bit kinds' line width */
-    const uint8_t   *img;
-    size_t           n;
-    u2_index         ux;                           /* the 2-bit kinds' records */
-    dx_undexqv_plan *plan;                         /* quiva's */
-    uint64_t        *ooff;                         /* h.n + 1 (the last: h.total); owned for the 2-bit kinds, the plan's for quiva */
-    hdr_patch        h;                            /* the layout as the slice loops and their hooks read it (no sink): h.n records, h.total
-                                                      bytes of text, the header lines h.hd one after the other, hd_len bytes of them */
-    size_t           hd_len;
-  } image_text;
-
-static void image_close(image_text *im)
+void dxf_image_close(image_text *im)
 { dx_file_undexqv_plan_free(im->plan);
   dxf_u2_index_free(&im->ux);
   if (im->kind != DX_KIND_QUIVA) free(im->ooff);
   memset(im, 0, sizeof(*im));
 }
 
-/* an error leaves what there is to image_close */
-static int image_open(dx_ctx *ctx, int kind, int upper, uint32_t width, const uint8_t *img, size_t n, image_text *im)
+int dxf_image_open(dx_ctx *ctx, int kind, int upper, uint32_t width, const uint8_t *img, size_t n, image_text *im)
 { hdr_patch *h = &im->h;
   int rc;
   memset(im, 0, sizeof(*im));
@@ -61,6 +48,11 @@ static int image_open(dx_ctx *ctx, int kind, int upper, uint32_t width, const ui
 static int image_slices(dx_ctx *ctx, const image_text *im, size_t cap, int whole_in, slice_fn fn, void *arg)
 { if (im->kind == DX_KIND_QUIVA) return dxf_undexqv_sliced(ctx, im->plan, im->upper, fn, arg, cap, whole_in);
   return dxf_unpack2_slices(ctx, im->mode, im->img, im->n, im->width, &im->ux, &im->h, cap, fn, arg);
+}
+
+int dxf_image_range(dx_ctx *ctx, const image_text *im, uint64_t r0, uint64_t r1, int whole_in, slice_fn fn, void *arg)
+{ if (im->kind != DX_KIND_QUIVA) return DX_E_ARG;
+  return dxf_undexqv_range(ctx, im->plan, im->upper, r0, r1, fn, arg, 0, whole_in);
 }
 
 /* ==========================================================================================
@@ -245,7 +237,7 @@ int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const u
   rep->records_src = v.cnt;
 
   /* the image, decoded with those options */
-  rc = m ? image_open(ctx, kind, rep->upper, rep->width, img, m, &im) : DX_E_FORMAT;
+  rc = m ? dxf_image_open(ctx, kind, rep->upper, rep->width, img, m, &im) : DX_E_FORMAT;
   if (rc == DX_E_FORMAT || rc == DX_E_UNSUPPORTED || rc == DX_E_DEGENERATE)
     { rep->where = DX_VERIFY_IMAGE;                        /* (no image of anything) */
       rc = DX_OK; goto done;
@@ -308,7 +300,7 @@ int dx_file_verify(dx_ctx *ctx, int kind, const uint8_t *text, size_t n, const u
 done:
   if (v.d_src) (void) dx_free(ctx, v.d_src);
   if (v.d_arr) (void) dx_free(ctx, v.d_arr);
-  image_close(&im);
+  dxf_image_close(&im);
   dxf_seq_index_free(&sx); dxf_quiva_index_free(&qx);
   return rc;
 }
@@ -376,7 +368,7 @@ int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int uppe
   memset(&g, 0, sizeof(g));
   g.ctx = ctx; g.h = &im.h;
 
-  TRY(image_open(ctx, kind, upper, width, img, m, &im));
+  TRY(dxf_image_open(ctx, kind, upper, width, img, m, &im));
   cnt = im.h.n; g.hd_bytes = im.hd_len;
   if (rec_crc != NULL && (g.rec = malloc((cnt + 1) * sizeof(*g.rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
 
@@ -395,7 +387,7 @@ int dx_file_digest(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, int uppe
 done:
   if (g.d_hd) (void) dx_free(ctx, g.d_hd);
   if (g.d_arr) (void) dx_free(ctx, g.d_arr);
-  image_close(&im);
+  dxf_image_close(&im);
   free(g.rec);
   return rc;
 }
@@ -550,7 +542,7 @@ int dx_file_census(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, dx_censu
   if (rec_code) *rec_code = NULL;
   if (rec_sum) *rec_sum = NULL;
 
-  TRY(image_open(ctx, kind, 0, 1, img, m, &im));          /* (the tag line in lower case; the line width lays out a text nobody makes) */
+  TRY(dxf_image_open(ctx, kind, 0, 1, img, m, &im));      /* (the tag line in lower case; the line width lays out a text nobody makes) */
   cnt  = im.h.n;
   lens = kind == DX_KIND_QUIVA ? im.plan->x.len : im.ux.nsym;
   if ((cs = calloc(1, sizeof(*cs))) == NULL) { rc = DX_E_NOMEM; goto done; }
@@ -584,7 +576,7 @@ int dx_file_census(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, dx_censu
   rc = DX_OK;
 
 done:
-  image_close(&im);
+  dxf_image_close(&im);
   free(cs); free(rl); free(rcode); free(rsum);
   return rc;
 }

@@ -560,8 +560,19 @@ static int decode_flags(const dx_undexqv_plan *p, int upper)
  * uploaded -- are decoded into one buffer that goes to `deliver` before the next slice comes in.  Same text; a file in several
  * slices is bound by the host link.
  * The host walk's group index (DEXGPU_TEST=walk_index: a wavefront per line, dx_qv_use_index) is for the whole image in one
- * slice; with several slices it stays out.                                                                          */
+ * slice; with several slices it stays out.
+ * dxf_undexqv_range: the same for entries [r0, r1) alone -- who decodes two plans side by side (dx_file_compare.c) states the range
+ * and gets it in slices that end at r1.                                                                                 */
 int dxf_undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_fn deliver, void *arg, size_t cap, int whole_in_)
+{ return dxf_undexqv_range(ctx, p, upper, 0, p->x.n, deliver, arg, cap, whole_in_); }
+
+/* where the slice that begins with entry i0 ends: dxf_text_slice_end, and r1 at the latest */
+static uint64_t range_slice_end(const hdr_patch *h, uint64_t i0, size_t cap, uint64_t r1)
+{ const uint64_t i1 = dxf_text_slice_end(h, i0, cap);
+  return i1 < r1 ? i1 : r1;
+}
+
+int dxf_undexqv_range(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, uint64_t r0, uint64_t r1, slice_fn deliver, void *arg, size_t cap, int whole_in_)
 { const int whole_in = whole_in_ || PLAN_HAS_IMAGE(p);    /* (an image that is there is there whole) */
   dpool     pool = { {0}, 0, ctx };
   const uint64_t n = p->x.n;
@@ -571,8 +582,9 @@ int dxf_undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_f
   size_t    tmax = 0, imax = 0;
   const hdr_patch h = { n, p->ooff, p->hat, p->hd.p, NULL, NULL, 0, p->total };      /* (the layout, for the slices' bounds) */
   int       rc = DX_OK, indexed = 0;
-  for (i0 = 0; i0 < n; i0 = i1)                           /* the largest slice: one allocation serves them all */
-    { i1 = dxf_text_slice_end(&h, i0, cap);
+  if (r1 > n || r0 > r1) return DX_E_ARG;
+  for (i0 = r0; i0 < r1; i0 = i1)                         /* the largest slice: one allocation serves them all */
+    { i1 = range_slice_end(&h, i0, cap, r1);
       if (text_at(&h, i1) - text_at(&h, i0) > tmax) tmax = text_at(&h, i1) - text_at(&h, i0);
       if (i1 - i0 > most) most = i1 - i0;
       if (!whole_in && p->x.rec_off[i1] - p->x.rec_off[i0] > imax) imax = (size_t) (p->x.rec_off[i1] - p->x.rec_off[i0]);
@@ -582,17 +594,17 @@ int dxf_undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_f
   TRY(undexqv_stage(ctx, p, &pool, imax, most, &s, &indexed));
   TRY(dalloc(&pool, (most + 1) * 8, &d_ooff));
   TRY(dalloc(&pool, tmax, &d_out));
-  if (p->x.gidx != NULL && !p->x.flip && whole_in && dxf_text_slice_end(&h, 0, cap) == n)
+  if (p->x.gidx != NULL && !p->x.flip && whole_in && r0 == 0 && range_slice_end(&h, 0, cap, r1) == n)
     { void *d_gidx, *d_goff;
       TRY(dupload(&pool, p->x.gidx, (size_t) p->x.gidx_words * 4, &d_gidx));
       TRY(dupload(&pool, p->x.gidx_off, (n + 1) * 8, &d_goff));
       TRY(dx_qv_use_index(ctx, s.d_in, s.d_seg, n, d_gidx, d_goff, p->x.gidx_none));
       indexed = 1;
     }
-  for (i0 = 0; i0 < n; i0 = i1)
+  for (i0 = r0; i0 < r1; i0 = i1)
     { const size_t t0 = text_at(&h, i0);
       const uint64_t *rec = s.d_rec;
-      i1 = dxf_text_slice_end(&h, i0, cap);
+      i1 = range_slice_end(&h, i0, cap, r1);
       for (i = i0; i < i1; i++) rel[i - i0] = p->ooff[i] - t0;
       TRY(dx_h2d(ctx, d_ooff, rel, (i1 - i0) * 8));
       if (whole_in)

@@ -10,6 +10,7 @@
  *     dx_select.c      the .qvs entry API, the .bps / .arw read loader
  *     dx_file_subset.c a new image cut out of an old one: dx_file_subset_layout (host), dx_file_subset
  *     dx_file_extract.c chosen records as text: dx_file_extract
+ *     dx_file_compare.c how two images of the same records differ: dx_file_compare
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
  */
@@ -203,6 +204,43 @@ DXF_HIDDEN int    dxf_qv_header(tbuf *b, const char *prefix, const int32_t *h4);
 /* a plan's text in slices of whole entries, at most `cap` bytes of text each (0: in one), each to `deliver`; and the cap the device asks for */
 DXF_HIDDEN int    dxf_undexqv_sliced(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, slice_fn deliver, void *arg, size_t cap, int whole_in_);
 DXF_HIDDEN size_t dxf_undexqv_cap(dx_ctx *ctx, const dx_undexqv_plan *p, int *whole_in);
+/* ... and entries [r0, r1) of it alone, in slices that end at r1 (dxf_undexqv_sliced is the range of all entries) */
+DXF_HIDDEN int    dxf_undexqv_range(dx_ctx *ctx, const dx_undexqv_plan *p, int upper, uint64_t r0, uint64_t r1, slice_fn deliver, void *arg,
+                                    size_t cap, int whole_in_);
+
+/* ---- dx_file_check.c ------------------------------------------------------------------------------------------------- */
+/* An image of any of the three kinds and the text it decodes to, for who wants the text's slices where they are made (dx_file_verify,
+   dx_file_digest, dx_file_census, dx_file_compare): the image's records walked, the header lines the decoder prints, the text's layout. */
+typedef struct
+  { int              kind, mode, upper;            /* DX_KIND_*; the 2-bit kinds' DX_LETTERS_*; quiva: undexqv -U */
+    uint32_t         width;                        /* the 2-bit kinds' line width */
+    const uint8_t   *img;
+    size_t           n;
+    u2_index         ux;                           /* the 2-bit kinds' records */
+    dx_undexqv_plan *plan;                         /* quiva's */
+    uint64_t        *ooff;                         /* h.n + 1 (the last: h.total); owned for the 2-bit kinds, the plan's for quiva */
+    hdr_patch        h;                            /* the layout as the slice loops and their hooks read it (no sink): h.n records, h.total
+                                                      bytes of text, the header lines h.hd one after the other, hd_len bytes of them */
+    size_t           hd_len;
+  } image_text;
+
+/* an error leaves what there is to dxf_image_close */
+DXF_HIDDEN int  dxf_image_open(dx_ctx *ctx, int kind, int upper, uint32_t width, const uint8_t *img, size_t n, image_text *im);
+DXF_HIDDEN void dxf_image_close(image_text *im);
+/* records [r0, r1) of a quiva image decoded in one slice, to `fn`: for who holds two images' texts side by side and so states the
+   range himself (the 2-bit kinds' reads are compared where they lie: nobody asks for a range of their text, and it is DX_E_ARG) */
+DXF_HIDDEN int  dxf_image_range(dx_ctx *ctx, const image_text *im, uint64_t r0, uint64_t r1, int whole_in, slice_fn fn, void *arg);
+
+/* ---- dx_file_compare.c ----------------------------------------------------------------------------------------------- */
+/* Two images of one kind, walked and paired by index: the first `both` records of each are compared.  pa / pb (both + 1 each): what the
+   slices are measured by -- records [i0, i1) of a side cost p[i1] - p[i0] bytes of text (quiva) or of image (the 2-bit kinds).
+   The host part of dx_file_compare, apart so that it can run without a device (ctx == NULL: every walk on the host). */
+typedef struct { image_text a, b; uint64_t both, *pa, *pb; } cmp_pair;
+
+DXF_HIDDEN int      dxf_compare_open(dx_ctx *ctx, int kind, const uint8_t *img_a, size_t m_a, const uint8_t *img_b, size_t m_b,
+                                     cmp_pair *p, dx_compare *c, int *side);
+DXF_HIDDEN uint64_t dxf_compare_slice_end(const cmp_pair *p, uint64_t i0, size_t cap);
+DXF_HIDDEN void     dxf_compare_close(cmp_pair *p);
 
 /* ---- dx_select.c ----------------------------------------------------------------------------------------------------- */
 /* the span of the input that a unit of a selection can reach, and the unit it belongs to */

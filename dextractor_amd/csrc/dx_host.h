@@ -29,6 +29,11 @@ int dx_entry_fail(dx_ctx *ctx, uint64_t id, uint64_t at, uint64_t nbytes);
    dx_entry_fail, for the host files that check a selection's units (dx_file_subset.c); the library does not export it. */
 __attribute__((visibility("hidden"))) int dx_unit_fail(dx_ctx *ctx, int code, const char *who, uint64_t j, const char *what);
 
+/* `code`, with the letter of the image it is about ('a', 'b') in front of the context's error text: "a: <the words>".  side 0 empties the
+   text and changes nothing else: a host walk fails without words, and what an earlier call left must not pass for them.  Defined in
+   compare/dx_diff.hip, for dx_file_compare.c. */
+__attribute__((visibility("hidden"))) int dx_side_fail(dx_ctx *ctx, int code, int side);
+
 /* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
    arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their
    (crc, length) pairs are wanted side by side in record order.  dx_crc32_pairs: units 2 k and 2 k + 1 joined into unit k of the

@@ -756,6 +756,66 @@ int dx_file_extract(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
                     int upper, uint32_t width, uint8_t **text, size_t *text_bytes, uint64_t **toff /* n_ids + 1, may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ *  compare: how two archives of the same records differ, without either text  (undexqv of both and a text diff today)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { uint64_t differ, units, sum_abs, max_abs; } dx_diff_tally;
+
+/* n byte ranges of device buffer a against n of device buffer b, counted (csrc/compare/dx_diff.hip): unit j is d_a[d_a_off[j] .. +
+ * d_len[j]) against d_b[d_b_off[j] .. + d_len[j]), offsets of any alignment on either side, lengths from 0 up, ranges may overlap
+ * or repeat.  d_kind[j] (NULL: all 0) names one of nkinds (1 to 8) tallies, and a_and[kind] (host, nkinds bytes; NULL: all 0xff) is
+ * ANDed onto side a's bytes before they are compared: dexqv -l's rounding is 0xFE on the insertion and 0xFC on the merge line
+ * (QV.c:1406-1415).  d_differ[j] (may be NULL) = the unit's differing bytes, d_first[j] (may be NULL) = the first of them, UINT32_MAX
+ * if none.  tally[k] (host, nkinds; may be NULL): kind k's differing bytes, its units with at least one, the sum and the largest of
+ * |a - b| after the mask.  *first (may be NULL) = the smallest unit << 32 | position that differs, all ones if none does.  Where
+ * dx_verify_ranges stops at the first difference, this reads everything, and every byte once: nothing outside a unit's two ranges
+ * is read.  DX_E_FORMAT with *bad_unit = the smallest j whose range does not lie inside a_bytes / b_bytes or whose kind is not below
+ * nkinds (UINT64_MAX otherwise; may be NULL); one read-back a call.  n < 2^31; n == 0 gives zeros.                             */
+int dx_diff_ranges(dx_ctx *ctx, const uint8_t *d_a, uint64_t a_bytes, const uint64_t *d_a_off,
+                   const uint8_t *d_b, uint64_t b_bytes, const uint64_t *d_b_off, const uint32_t *d_len,
+                   const uint8_t *d_kind /* NULL: all 0 */, int nkinds /* 1..8 */, const uint8_t *a_and /* host; NULL: all 0xff */,
+                   uint64_t n, uint32_t *d_differ /* may be NULL */, uint32_t *d_first /* may be NULL */,
+                   dx_diff_tally *tally /* host, nkinds */, uint64_t *first, uint64_t *bad_unit);
+
+/* The same for packed reads where they lie, nothing decoded: unit j is symbols [0, d_len[j]) of the packed read at d_a + d_a_boff[j]
+ * against those of the one at d_b + d_b_boff[j] (four symbols a byte, the first in the top two bits: DB.c:319-338).  d_differ[j] =
+ * the symbols that differ, d_first[j] = the first of them (UINT32_MAX: none); total[0] (host; may be NULL) = the differing symbols
+ * of the call, total[1] = the units that have one; *first = the smallest unit << 32 | symbol.  The pad bits of a read's last byte
+ * are NOT compared: a foreign writer may leave anything there.  Bad units are dx_code_counts' on either side.  n < 2^31.          */
+int dx_code_diff(dx_ctx *ctx, const uint8_t *d_a, uint64_t a_bytes, const uint64_t *d_a_boff,
+                 const uint8_t *d_b, uint64_t b_bytes, const uint64_t *d_b_boff, const uint32_t *d_len, uint64_t n,
+                 uint32_t *d_differ /* may be NULL */, uint32_t *d_first /* may be NULL */, uint64_t total[2] /* host */,
+                 uint64_t *first, uint64_t *bad_unit);
+
+typedef struct
+  { int32_t  same;                               /* 1: the counts, the prefixes, every header, every length and every symbol (after the mask) are equal */
+    int32_t  lines;                              /* lines a record compared: 1 for the 2-bit kinds, 5 for quiva */
+    int32_t  prefix_differs, reserved;
+    uint64_t records_a, records_b;               /* the first min of them are compared */
+    uint64_t headers_differ, first_header;       /* records whose well, beg, end or qv / four SN words differ; the first (UINT64_MAX: none) */
+    uint64_t lengths_differ, first_length;       /* records whose symbol counts differ (compared over the shorter one); the first */
+    uint64_t records_differ, first_record;       /* records with a differing symbol; the first difference in file order: its record */
+    uint32_t first_line, first_column;           /* ... (UINT64_MAX: none), line and column */
+    uint64_t differ[5], line_records[5];         /* per line: differing symbols, records that have one */
+    uint64_t sum_abs[5], max_abs[5];             /* quiva: the sum and the largest of |a - b| (2-bit kinds: 0) */
+  } dx_compare;
+
+/* How two images of one kind (DX_KIND_*) differ: any key, legacy layout, byte order or coding on either side, as dx_file_unpack2 /
+ * dx_file_undexqv accept them; records are paired by index.  Quiva lines are del, tag, ins, mrg, sub; the tag line is compared in
+ * lower case on both sides; newlines and header lines are not compared (the headers' FIELDS are, as the host walks decode them).
+ * lossy (quiva only; DX_E_ARG else): side a's insertion and merge lines are masked as dexqv -l rounds them before the comparison,
+ * so same == 1 says "b is exactly what dexqv -l keeps of a".  *rec_differ (may be NULL; malloc'd, dx_file_free): min(records) x
+ * lines counts, the differing symbols of every compared record line by line.
+ * fasta / arrow: both images are walked on the host and uploaded, and the packed reads compared where they lie (dx_code_diff): no
+ * text is made.  quiva: both images are planned and decoded by the drivers' own code, each with its own coding, and the line ranges
+ * compared where they are made (dx_diff_ranges, kinds 0..4): nothing of either text comes back.  A pair that does not fit the
+ * device beside its two texts, or whose texts together exceed DEXGPU_TEXT_BUDGET (2-bit kinds: bytes of image), goes in slices of
+ * whole records, the same record range on both sides; the report is the same.
+ * An image that does not parse or decode is the error it is for its own driver, dx_last_error begins with "a:" or "b:", and *out
+ * is untouched.                                                                                                                 */
+int dx_file_compare(dx_ctx *ctx, int kind, const uint8_t *img_a, size_t m_a, const uint8_t *img_b, size_t m_b,
+                    int lossy, dx_compare *out, uint32_t **rec_differ /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
