@@ -87,6 +87,16 @@ class Compare(C.Structure):                      # dx_compare
                 ("first_record", C.c_uint64), ("first_line", C.c_uint32), ("first_column", C.c_uint32),
                 ("differ", C.c_uint64 * 5), ("line_records", C.c_uint64 * 5), ("sum_abs", C.c_uint64 * 5), ("max_abs", C.c_uint64 * 5)]
 
+class Query(C.Structure):                        # dx_query
+    _fields_ = [("code", C.c_uint64), ("len", C.c_uint32), ("max_mis", C.c_uint32)]
+
+class Hit(C.Structure):                          # dx_hit
+    _fields_ = [("record", C.c_uint64), ("pos", C.c_uint32), ("query", C.c_uint16), ("strand", C.c_uint8), ("mis", C.c_uint8)]
+
+class Find(C.Structure):                         # dx_find
+    _fields_ = [("records", C.c_uint64), ("records_hit", C.c_uint64), ("hits", C.c_uint64), ("listed", C.c_uint64),
+                ("per_pattern", (C.c_uint64 * 2) * 64)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
@@ -207,6 +217,10 @@ SIGNATURES = {
     "dx_code_diff": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64 * 2),
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dx_file_compare": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, C.c_int, C.POINTER(Compare), C.POINTER(_P)]),
+    "dx_code_find": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(Query), C.c_uint32, _P, _P, C.c_uint64, _P,
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_file_find": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint64,
+                               C.POINTER(Find), C.POINTER(_P), C.POINTER(_P)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

@@ -628,6 +628,59 @@ class Context:
                 self.lib.dx_file_free(rec)
         return out
 
+    # ---- find --------------------------------------------------------------------------------------
+    def code_find(self, d_in, in_bytes, d_boff, d_beg, d_len, n, queries, d_count=None, cap=0, d_hits=None):
+        """dx_code_find: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None: whole
+        reads from symbol 0); queries: (code, len, max_mis) triples, symbol i of a query in bits 2 (len - 1 - i) + 1, 2 (len - 1 - i)
+        of its code.  d_count (uint32, n, or None) gets every unit's hits; d_hits (16 cap bytes, or None: made here) the list.
+        ({"hits": all of them, "total": uint64 a query}, the first min(cap, hits) hits in the order (unit, pos, query) as a
+        HIT_DTYPE array).  Raises DexGPUError (DX_E_FORMAT,
+        .bad_unit = the first such j) when a unit does not lie inside the in_bytes."""
+        nq, cap = len(queries), int(cap)
+        q = (L.Query * max(nq, 1))(*[L.Query(int(c), int(m), int(x)) for c, m, x in queries])
+        tot, hits, bad = (C.c_uint64 * max(nq, 1))(), C.c_uint64(), C.c_uint64()
+        own = d_hits is None and cap > 0
+        if own:
+            d_hits = self.alloc(16 * cap + 16)
+        try:
+            rc = self.lib.dx_code_find(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
+                                       d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), q, nq,
+                                       d_count.ptr if d_count else None, d_hits.ptr if d_hits else None, cap, tot,
+                                       C.byref(hits), C.byref(bad))
+            if rc != 0:
+                raise self._bad_unit(rc, bad)
+            k = min(cap, hits.value)
+            lst = d_hits.download(np.uint8, 16 * k).view(HIT_DTYPE) if k else np.zeros(0, HIT_DTYPE)
+        finally:
+            if own:
+                d_hits.free()
+        return {"hits": hits.value, "total": np.array(list(tot)[:nq], dtype=np.uint64)}, lst
+
+    def find(self, kind, img: bytes, patterns, max_mismatches=0, both_strands=False, max_hits=1 << 20, per_record=False):
+        """dx_file_find: where the patterns (str, 1 to 32 letters: acgtACGT for "fasta", 1234 for "arrow") occur in the reads of the
+        image, within max_mismatches substitutions, searched on the device in the packed reads (no text is made).  both_strands
+        ("fasta"): the reverse complements too, strand 1.  ({"records", "records_hit", "hits", "listed", "per_pattern": uint64
+        [patterns, 2]} and with per_record "rec_hits": uint32 a record, the first max_hits hits in the order (record, pos, pattern,
+        strand) as a HIT_DTYPE array, `query` being the pattern's index)."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
+        arr = (C.c_char_p * max(len(pats), 1))(*pats)
+        fd, lst, rec = L.Find(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.dx_file_find(self.h, k, img, len(img), arr, len(pats), int(max_mismatches), int(bool(both_strands)),
+                                        int(max_hits), C.byref(fd), C.byref(lst), C.byref(rec) if per_record else None))
+        try:
+            out = {"records": fd.records, "records_hit": fd.records_hit, "hits": fd.hits, "listed": fd.listed,
+                   "per_pattern": np.array([[fd.per_pattern[p][0], fd.per_pattern[p][1]] for p in range(len(pats))],
+                                           dtype=np.uint64).reshape(len(pats), 2)}
+            hits = np.zeros(0, HIT_DTYPE)
+            if fd.listed:
+                hits = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * fd.listed,)).view(HIT_DTYPE).copy()
+            if per_record:
+                out["rec_hits"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), (fd.records + 1,))[:fd.records].copy()
+        finally:
+            self.lib.dx_file_free(lst); self.lib.dx_file_free(rec)
+        return out, hits
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -850,6 +903,8 @@ def pack2_sharded(contexts, text: bytes, arrow=False) -> bytes:
 
 
 # ---- host-only helpers (no GPU needed) ---------------------------------------------------------
+HIT_DTYPE = np.dtype([("record", "<u8"), ("pos", "<u4"), ("query", "<u2"), ("strand", "u1"), ("mis", "u1")])      # dx_hit
+
 
 def census_dict(cs) -> dict:
     """a dx_census as a dict: the scalars, "code" (uint64[4]) and "hist" (uint64[5, 256])"""

@@ -432,7 +432,7 @@ int dx_census_lengths(const uint32_t *len, uint64_t n, dx_census *out)
 
 /* how much of a 2-bit image of m bytes the device takes at once beside 48 bytes of arrays a record: 0 = all of it.  DEXGPU_TEXT_BUDGET
    counts bytes of image here (there is no text) */
-static size_t census_cap(dx_ctx *ctx, size_t m, uint64_t units)
+size_t dxf_u2_cap(dx_ctx *ctx, size_t m, uint64_t units)
 { uint64_t fr = 0, all = 0;
   size_t   cap;
   if (dxf_budget_env(m, 4096u, &cap)) return cap;
@@ -446,7 +446,7 @@ static size_t census_cap(dx_ctx *ctx, size_t m, uint64_t units)
 static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
 
 /* a slice of whole records from i0 on: as many as span at most `cap` bytes of image, and one at least; cap 0: all that are left */
-static uint64_t u2_slice_end(const u2_index *x, uint64_t i0, size_t cap)
+uint64_t dxf_u2_slice_end(const u2_index *x, uint64_t i0, size_t cap)
 { uint64_t i1 = i0 + 1;
   if (cap == 0) return x->cnt;
   while (i1 < x->cnt && u2_end(x, i1) - x->ioff[i0] <= cap) i1++;
@@ -461,7 +461,7 @@ static int census_pack2(dx_ctx *ctx, const uint8_t *img, const u2_index *x, size
   void     *d_in = NULL, *d_arr = NULL;
   int       rc = DX_OK;
   for (i0 = 0; i0 < cnt; i0 = i1)                         /* the largest slice: one allocation serves them all */
-    { i1 = u2_slice_end(x, i0, cap);
+    { i1 = dxf_u2_slice_end(x, i0, cap);
       if (u2_end(x, i1 - 1) - x->ioff[i0] > smax) smax = (size_t) (u2_end(x, i1 - 1) - x->ioff[i0]);
       if (i1 - i0 > most) most = i1 - i0;
     }
@@ -472,7 +472,7 @@ static int census_pack2(dx_ctx *ctx, const uint8_t *img, const u2_index *x, size
     { const uint64_t b0 = x->ioff[i0];
       uint64_t *d_boff = d_arr;
       uint32_t *d_cnt, *d_len;
-      i1 = u2_slice_end(x, i0, cap);
+      i1 = dxf_u2_slice_end(x, i0, cap);
       d_cnt = (uint32_t *) (d_boff + most); d_len = d_cnt + 4 * most;
       for (i = i0; i < i1; i++) rel[i - i0] = x->ioff[i] - b0;
       TRY(dx_h2d(ctx, d_in, img + b0, (size_t) (u2_end(x, i1 - 1) - b0)));
@@ -553,7 +553,7 @@ int dx_file_census(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, dx_censu
     }
   if (kind != DX_KIND_QUIVA)
     { if (rec_code != NULL && (rcode = malloc((cnt + 1) * 4 * sizeof(*rcode))) == NULL) { rc = DX_E_NOMEM; goto done; }
-      if (cnt > 0) TRY(census_pack2(ctx, img, &im.ux, census_cap(ctx, m, cnt), cs->code, rcode));
+      if (cnt > 0) TRY(census_pack2(ctx, img, &im.ux, dxf_u2_cap(ctx, m, cnt), cs->code, rcode));
     }
   else
     { census_job c;

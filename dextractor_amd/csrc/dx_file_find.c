@@ -1,0 +1,182 @@
+/*
+ * dx_file_find.c -- where given sequences occur in the reads of a .dexta / .dexar image: dx_file_find.
+ *
+ * Today the question takes undexta -U of the whole file and a text search on one core.  Here the image is walked on the host
+ * (dxf_image_open: any key, legacy layout or byte order) and uploaded, and the packed reads are searched where they lie
+ * (dx_code_find, units ux.ioff / ux.nsym): no text is made, a quarter of its bytes is read, and there are no header lines or line
+ * wraps to step over.
+ *
+ * The search is over what the archive HOLDS: an N that dexta stored as a is an a (Number_Read, DB.c:393-416, codes every letter that is not
+ * c, g or t as 0).  The hits are exactly those a search of the letters undexta -U / undexar prints, record by record, would find.
+ *
+ * A pattern becomes one query, or two with both_strands: the reverse complement is the codes 3 - c in reverse order, and a pattern
+ * that equals its own is searched once.  The queries stand in the order (pattern, strand), so that the kernel's order (unit, pos,
+ * query) is the file's (record, pos, pattern, strand); dxf_find_map then names every hit by its pattern and strand.
+ * An image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET, goes in slices of whole records (dxf_u2_slice_end): a
+ * slice's hits are listed into what max_hits has left, its record numbers moved by the slice's first record.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "dexgpu.h"
+#include "dx_host.h"
+#include "dx_files.h"
+
+#define FIND_ROOM ((uint64_t) 1 << 20)       /* hits a slice is listed into at first; one with more is searched again into enough */
+
+/* a letter's code (Number_Read / Number_Arrow, DB.c:393-441), or -1 when it is none of the kind's */
+static int letter_code(int arrow, int c)
+{ if (arrow) return c >= '1' && c <= '4' ? c - '1' : -1;
+  switch (c)
+    { case 'a': case 'A': return 0;
+      case 'c': case 'C': return 1;
+      case 'g': case 'G': return 2;
+      case 't': case 'T': return 3;
+      default:            return -1;
+    }
+}
+
+int dxf_find_plan(dx_ctx *ctx, int kind, const char *const *pattern, uint32_t npat, uint32_t max_mis, int both_strands, find_plan *fp)
+{ char     why[160];
+  uint32_t p, least = UINT32_MAX;
+  memset(fp, 0, sizeof(*fp));
+  if (kind == DX_KIND_QUIVA)
+    return dx_find_fail(ctx, DX_E_ARG, "a .dexqv image has no packed reads to search (DX_KIND_FASTA or DX_KIND_ARROW)");
+  if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW) return dx_find_fail(ctx, DX_E_ARG, "unknown kind");
+  if (both_strands && kind == DX_KIND_ARROW)
+    return dx_find_fail(ctx, DX_E_ARG, "both_strands: pulse widths have no complement (DX_KIND_FASTA only)");
+  if (pattern == NULL || npat < 1 || npat > (both_strands ? 32u : 64u))
+    { snprintf(why, sizeof(why), "%u patterns (1 to %u%s)", npat, both_strands ? 32u : 64u, both_strands ? " with both_strands" : "");
+      return dx_find_fail(ctx, DX_E_ARG, why);
+    }
+  for (p = 0; p < npat; p++)
+    { const char *s = pattern[p];
+      const size_t len = s ? strlen(s) : 0;
+      uint64_t code = 0, rev = 0;
+      size_t   i;
+      if (len < 1 || len > 32)
+        { snprintf(why, sizeof(why), "pattern %u has %zu letters (1 to 32)", p, len);
+          return dx_find_fail(ctx, DX_E_ARG, why);
+        }
+      for (i = 0; i < len; i++)
+        { const int c = letter_code(kind == DX_KIND_ARROW, (unsigned char) s[i]);
+          if (c < 0)
+            { snprintf(why, sizeof(why), "pattern %u, column %zu: not one of %s", p, i + 1, kind == DX_KIND_ARROW ? "1234" : "acgtACGT");
+              return dx_find_fail(ctx, DX_E_ARG, why);
+            }
+          code = (code << 2) | (uint64_t) c;
+          rev |= (uint64_t) (3 - c) << (2 * i);            /* letter i is letter len - 1 - i of the reverse: in the bits 2 i + 1, 2 i */
+        }
+      if (len < least) least = (uint32_t) len;
+      fp->q[fp->nq].code = code; fp->q[fp->nq].len = (uint32_t) len; fp->q[fp->nq].max_mis = max_mis;
+      fp->pat[fp->nq] = (uint16_t) p; fp->strand[fp->nq] = 0; fp->nq++;
+      if (both_strands && rev != code)
+        { fp->q[fp->nq].code = rev; fp->q[fp->nq].len = (uint32_t) len; fp->q[fp->nq].max_mis = max_mis;
+          fp->pat[fp->nq] = (uint16_t) p; fp->strand[fp->nq] = 1; fp->nq++;
+        }
+    }
+  if (max_mis >= least)
+    { snprintf(why, sizeof(why), "%u mismatches: not below the shortest pattern's %u letters", max_mis, least);
+      return dx_find_fail(ctx, DX_E_ARG, why);
+    }
+  return DX_OK;
+}
+
+void dxf_find_map(const find_plan *fp, dx_hit *h, uint64_t cnt, uint64_t i0)
+{ uint64_t k;
+  for (k = 0; k < cnt; k++)
+    { const uint16_t q = h[k].query;
+      h[k].record += i0; h[k].query = fp->pat[q]; h[k].strand = fp->strand[q];
+    }
+}
+
+static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
+
+int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char *const *pattern, uint32_t npat, uint32_t max_mis,
+                 int both_strands, uint64_t max_hits, dx_find *out, dx_hit **hits, uint32_t **rec_hits)
+{ image_text im;
+  find_plan  fp;
+  dx_find   *fd = NULL;
+  dx_hit    *list = NULL;
+  uint32_t  *rec = NULL;
+  uint64_t  *rel = NULL, cnt, i, i0, i1, most = 0, list_cap = 0, kept = 0, tot[64];
+  const uint64_t keep = hits != NULL ? max_hits : 0;       /* hits the list is to hold (nobody takes it: none) */
+  size_t     cap, smax = 0, in_cap = 0, arr_cap = 0, hit_cap = 0;
+  void      *d_in = NULL, *d_arr = NULL, *d_hits = NULL;
+  const u2_index *x;
+  int        rc;
+
+  if (ctx == NULL || out == NULL || (img == NULL && m)) return DX_E_ARG;
+  if (hits) *hits = NULL;
+  if (rec_hits) *rec_hits = NULL;
+  if ((rc = dxf_find_plan(ctx, kind, pattern, npat, max_mis, both_strands, &fp)) != DX_OK) return rc;
+
+  TRY(dxf_image_open(ctx, kind, 0, 1, img, m, &im));       /* (the line width lays out a text nobody makes) */
+  x = &im.ux; cnt = x->cnt;
+  if ((fd = calloc(1, sizeof(*fd))) == NULL || (rec = malloc((cnt + 1) * sizeof(*rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
+  fd->records = cnt;
+
+  cap = cnt ? dxf_u2_cap(ctx, m, cnt) : 0;
+  for (i0 = 0; i0 < cnt; i0 = i1)                          /* the largest slice: one allocation serves them all */
+    { i1 = dxf_u2_slice_end(x, i0, cap);
+      if (u2_end(x, i1 - 1) - x->ioff[i0] > smax) smax = (size_t) (u2_end(x, i1 - 1) - x->ioff[i0]);
+      if (i1 - i0 > most) most = i1 - i0;
+    }
+  if (cnt)
+    { if ((rel = malloc((most + 1) * sizeof(*rel))) == NULL) { rc = DX_E_NOMEM; goto done; }
+      TRY(dgrow(ctx, &d_in, &in_cap, smax + 64));
+      TRY(dgrow(ctx, &d_arr, &arr_cap, (size_t) most * 16 + 64));            /* offsets (8), symbols (4), counts (4) */
+    }
+  for (i0 = 0; i0 < cnt; i0 = i1)
+    { const uint64_t b0 = x->ioff[i0];
+      uint64_t *d_boff = d_arr, n, found = 0, room, bytes;
+      uint32_t *d_len, *d_cnt;
+      i1 = dxf_u2_slice_end(x, i0, cap); n = i1 - i0; bytes = u2_end(x, i1 - 1) - b0;
+      d_len = (uint32_t *) (d_boff + most); d_cnt = d_len + most;
+      for (i = i0; i < i1; i++) rel[i - i0] = x->ioff[i] - b0;
+      TRY(dx_h2d(ctx, d_in, img + b0, (size_t) bytes));
+      TRY(dx_h2d(ctx, d_boff, rel, (size_t) n * 8));
+      TRY(dx_h2d(ctx, d_len, x->nsym + i0, (size_t) n * 4));
+      room = keep - kept < FIND_ROOM ? keep - kept : FIND_ROOM;
+      for (;;)                                              /* (a second time only for a slice with more hits than FIND_ROOM that are wanted) */
+        { TRY(dgrow(ctx, &d_hits, &hit_cap, (size_t) room * sizeof(dx_hit) + 64));
+          TRY(dx_code_find(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp.q, fp.nq, d_cnt, d_hits, room, tot, &found, NULL));
+          if (found <= room || room == keep - kept) break;
+          room = found < keep - kept ? found : keep - kept;
+          if (room > UINT32_MAX) { rc = dx_find_fail(ctx, DX_E_NOMEM, "more than 2^32 - 1 hits of one slice to list: lower max_hits"); goto done; }
+        }
+      TRY(dx_d2h(ctx, rec + i0, d_cnt, (size_t) n * 4));
+      for (i = 0; i < fp.nq; i++) fd->per_pattern[fp.pat[i]][fp.strand[i]] += tot[i];
+      fd->hits += found;
+      { const uint64_t got = found < room ? found : room;
+        if (got)
+          { if (kept + got > list_cap)
+              { const uint64_t want = kept + got > 2 * list_cap ? kept + got : 2 * list_cap;
+                dx_hit *bigger = realloc(list, (size_t) want * sizeof(*list));
+                if (bigger == NULL) { rc = DX_E_NOMEM; goto done; }
+                list = bigger; list_cap = want;
+              }
+            TRY(dx_d2h(ctx, list + kept, d_hits, (size_t) got * sizeof(*list)));
+            dxf_find_map(&fp, list + kept, got, i0);
+            kept += got;
+          }
+      }
+    }
+  for (i = 0; i < cnt; i++) fd->records_hit += rec[i] != 0;
+  fd->listed = fd->hits < max_hits ? fd->hits : max_hits;
+  if (hits != NULL && list == NULL && (list = malloc(sizeof(*list))) == NULL) { rc = DX_E_NOMEM; goto done; }
+
+  *out = *fd;
+  if (hits) { *hits = list; list = NULL; }
+  if (rec_hits) { *rec_hits = rec; rec = NULL; }
+  rc = DX_OK;
+
+done:
+  if (d_in) (void) dx_free(ctx, d_in);
+  if (d_arr) (void) dx_free(ctx, d_arr);
+  if (d_hits) (void) dx_free(ctx, d_hits);
+  dxf_image_close(&im);
+  free(fd); free(list); free(rec); free(rel);
+  return rc;
+}

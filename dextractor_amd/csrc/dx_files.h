@@ -11,6 +11,7 @@
  *     dx_file_subset.c a new image cut out of an old one: dx_file_subset_layout (host), dx_file_subset
  *     dx_file_extract.c chosen records as text: dx_file_extract
  *     dx_file_compare.c how two images of the same records differ: dx_file_compare
+ *     dx_file_find.c   where given sequences occur in an image's reads: dx_file_find
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
  */
@@ -230,6 +231,23 @@ DXF_HIDDEN void dxf_image_close(image_text *im);
 /* records [r0, r1) of a quiva image decoded in one slice, to `fn`: for who holds two images' texts side by side and so states the
    range himself (the 2-bit kinds' reads are compared where they lie: nobody asks for a range of their text, and it is DX_E_ARG) */
 DXF_HIDDEN int  dxf_image_range(dx_ctx *ctx, const image_text *im, uint64_t r0, uint64_t r1, int whole_in, slice_fn fn, void *arg);
+
+/* how much of a 2-bit image of m bytes the device takes at once beside 48 bytes of arrays a record: 0 = all of it (DEXGPU_TEXT_BUDGET counts
+   bytes of image here); and a slice of whole records from i0 on: as many as span at most `cap` bytes of image, and one at least */
+DXF_HIDDEN size_t   dxf_u2_cap(dx_ctx *ctx, size_t m, uint64_t units);
+DXF_HIDDEN uint64_t dxf_u2_slice_end(const u2_index *x, uint64_t i0, size_t cap);
+
+/* ---- dx_file_find.c -------------------------------------------------------------------------------------------------- */
+/* The host part of dx_file_find, apart so that it can run without a device (ctx == NULL: no error text is kept).  The patterns as the
+   queries of dx_code_find: query k is pattern pat[k] on strand strand[k], the queries in the order (pattern, strand), so that the
+   kernel's order (unit, pos, query) is the file's (record, pos, pattern, strand). */
+typedef struct { dx_query q[64]; uint16_t pat[64]; uint8_t strand[64]; uint32_t nq; } find_plan;
+
+DXF_HIDDEN int  dxf_find_plan(dx_ctx *ctx, int kind, const char *const *pattern, uint32_t npat, uint32_t max_mis, int both_strands,
+                              find_plan *fp);
+/* a slice's hits as dx_code_find listed them -- record: the unit in the slice, query: the query -- become the file's: record + i0, the
+   pattern's index, the strand */
+DXF_HIDDEN void dxf_find_map(const find_plan *fp, dx_hit *h, uint64_t cnt, uint64_t i0);
 
 /* ---- dx_file_compare.c ----------------------------------------------------------------------------------------------- */
 /* Two images of one kind, walked and paired by index: the first `both` records of each are compared.  pa / pb (both + 1 each): what the

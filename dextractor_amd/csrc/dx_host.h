@@ -34,6 +34,10 @@ __attribute__((visibility("hidden"))) int dx_unit_fail(dx_ctx *ctx, int code, co
    compare/dx_diff.hip, for dx_file_compare.c. */
 __attribute__((visibility("hidden"))) int dx_side_fail(dx_ctx *ctx, int code, int side);
 
+/* `code` with the words for it (dx_last_error; ctx NULL: nothing is kept): "dx_file_find: <what>".  Defined in find/dx_find.hip, for
+   dx_file_find.c, which words its refusals itself (the pattern's index and the column). */
+__attribute__((visibility("hidden"))) int dx_find_fail(dx_ctx *ctx, int code, const char *what);
+
 /* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
    arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their
    (crc, length) pairs are wanted side by side in record order.  dx_crc32_pairs: units 2 k and 2 k + 1 joined into unit k of the

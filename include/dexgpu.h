@@ -816,6 +816,59 @@ int dx_file_compare(dx_ctx *ctx, int kind, const uint8_t *img_a, size_t m_a, con
                     int lossy, dx_compare *out, uint32_t **rec_differ /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ *  find: where given sequences occur in an archive, without its text  (undexta -U of the whole file and a text search today)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { uint64_t code; uint32_t len, max_mis; } dx_query;      /* symbol i of the query in bits 2 (len - 1 - i) + 1, 2 (len - 1 - i) of
+                                                                            code: the first symbol on top, as in a packed read; bits above 2 len are 0 */
+typedef struct { uint64_t record; uint32_t pos; uint16_t query; uint8_t strand, mis; } dx_hit;   /* 16 bytes */
+
+/* Up to 64 queries of 1 to 32 symbols searched in n packed reads where they lie, nothing decoded (csrc/find/dx_find.hip; a text
+ * search of the decoded reads on one core today).  Unit j is what it is for dx_code_counts: symbols [d_beg[j], d_beg[j] + d_len[j])
+ * of the packed read at d_in + d_boff[j], any byte offset, any phase, units may overlap or repeat.  Query k hits unit j at pos when
+ * 0 <= pos <= d_len[j] - q[k].len and the unit's symbols [pos, pos + q[k].len) differ from the query's in at most q[k].max_mis
+ * places; overlapping hits all count, a unit shorter than a query has no hit of it, duplicate queries each report.  The symbols in
+ * front of d_beg[j], those behind the unit's end, the pad bits of a read's last byte and every byte that is not the unit's are part
+ * of no window, and nothing outside [0, in_bytes) is read.
+ * d_count[j] (may be NULL) = the unit's hits over all queries, UINT32_MAX when there are more; total[k] (host, nq; may be NULL) =
+ * query k's hits over the call; *hits = their sum, listed or not.  d_hits (cap entries; may be NULL when cap == 0) gets the first
+ * min(cap, *hits) hits in the order (unit, pos, query) -- record = j, strand = 0, mis = the distance --, the same on every call:
+ * places come from counts and prefix sums, no atomic cursor.  Not one byte behind d_hits[min(cap, *hits)] is written; cap == 0 runs
+ * the counting pass alone.  cap < 2^32.
+ * DX_E_FORMAT with *bad_unit = the smallest j that does not lie inside the in_bytes (UINT64_MAX otherwise; may be NULL); such units
+ * are not searched; checked by the kernel, one read-back a call (with a list: two).  DX_E_ARG for nq outside 1..64, a len outside
+ * 1..32, bits of code above 2 len, a NULL pointer that is needed, n >= 2^31.  n == 0 gives zeros.                               */
+int dx_code_find(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                 const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                 const dx_query *q /* host */, uint32_t nq /* 1..64 */,
+                 uint32_t *d_count /* n, may be NULL */, dx_hit *d_hits /* cap, may be NULL when cap == 0 */, uint64_t cap,
+                 uint64_t total[] /* host, nq; may be NULL */, uint64_t *hits /* host: all of them, listed or not */,
+                 uint64_t *bad_unit /* may be NULL */);
+
+typedef struct { uint64_t records, records_hit, hits, listed; uint64_t per_pattern[64][2]; } dx_find;
+
+/* Which records of a .dexta / .dexar image (kind DX_KIND_FASTA or DX_KIND_ARROW; any key, legacy layout or byte order, as
+ * dx_file_unpack2 takes them) contain the given patterns, and where (undexta -U | a text search today).  A pattern is 1 to 32
+ * letters, acgtACGT for fasta, 1234 for arrow; npat is 1 to 64, with both_strands 1 to 32.  max_mis (one figure for all patterns,
+ * below the shortest pattern's length) is the Hamming distance a window may have.  both_strands (fasta only): every pattern is
+ * also searched as its reverse complement; such a hit has strand 1 and pos = the leftmost symbol of the window on the read as
+ * stored; a pattern that is its own reverse complement is searched once and reports strand 0 only.
+ * The search is over what the archive HOLDS: an N that dexta stored as a is an a.  The hits are exactly those a search of the letters
+ * undexta -U / undexar prints, record by record, would find; a window never spans two records.
+ * out->records = the image's records, records_hit those with a hit, hits all hits, listed = min(hits, max_hits),
+ * per_pattern[p][s] the hits of pattern p on strand s.  *hits (may be NULL; malloc'd, dx_file_free) has `listed` entries in the
+ * order (record, pos, pattern, strand), query = the pattern's index; *rec_hits (may be NULL; malloc'd) one count a record,
+ * UINT32_MAX when there are more.
+ * The image is walked on the host and uploaded, and the reads are searched where they lie (dx_code_find): no text is made.  An
+ * image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET (bytes of image, as for dx_file_census), goes in slices of
+ * whole records; record numbers, the order and max_hits run across the slices as if there were none.
+ * DX_E_ARG (dx_last_error says why; for a letter the pattern's index and the column) for DX_KIND_QUIVA, a pattern of 0 or more
+ * than 32 letters or with a letter that is not the kind's, npat out of range, max_mis not below the shortest pattern,
+ * both_strands for arrow; else dx_file_unpack2's errors for the image, and *out is untouched.                                    */
+int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
+                 const char *const *pattern, uint32_t npat, uint32_t max_mis, int both_strands,
+                 uint64_t max_hits, dx_find *out, dx_hit **hits /* may be NULL */, uint32_t **rec_hits /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
