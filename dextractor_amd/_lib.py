@@ -90,6 +90,9 @@ class Compare(C.Structure):                      # dx_compare
 class Query(C.Structure):                        # dx_query
     _fields_ = [("code", C.c_uint64), ("len", C.c_uint32), ("max_mis", C.c_uint32)]
 
+class EQuery(C.Structure):                       # dx_equery
+    _fields_ = [("code", C.c_uint64 * 2), ("len", C.c_uint32), ("max_err", C.c_uint32)]
+
 class Hit(C.Structure):                          # dx_hit
     _fields_ = [("record", C.c_uint64), ("pos", C.c_uint32), ("query", C.c_uint16), ("strand", C.c_uint8), ("mis", C.c_uint8)]
 
@@ -221,6 +224,10 @@ SIGNATURES = {
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dx_file_find": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint64,
                                C.POINTER(Find), C.POINTER(_P), C.POINTER(_P)]),
+    "dx_code_find_edit": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(EQuery), C.c_uint32, _P, _P, C.c_uint64, _P,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_file_find_edit": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint64,
+                                    C.POINTER(Find), C.POINTER(_P), C.POINTER(_P)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

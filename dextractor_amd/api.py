@@ -662,12 +662,16 @@ class Context:
         ("fasta"): the reverse complements too, strand 1.  ({"records", "records_hit", "hits", "listed", "per_pattern": uint64
         [patterns, 2]} and with per_record "rec_hits": uint32 a record, the first max_hits hits in the order (record, pos, pattern,
         strand) as a HIT_DTYPE array, `query` being the pattern's index)."""
+        return self._file_find(self.lib.dx_file_find, kind, img, patterns, max_mismatches, both_strands, max_hits, per_record)
+
+    def _file_find(self, fn, kind, img, patterns, bound, both_strands, max_hits, per_record):
+        """dx_file_find / dx_file_find_edit: one argument list, one report"""
         k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
         pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
         arr = (C.c_char_p * max(len(pats), 1))(*pats)
         fd, lst, rec = L.Find(), C.c_void_p(), C.c_void_p()
-        self._chk(self.lib.dx_file_find(self.h, k, img, len(img), arr, len(pats), int(max_mismatches), int(bool(both_strands)),
-                                        int(max_hits), C.byref(fd), C.byref(lst), C.byref(rec) if per_record else None))
+        self._chk(fn(self.h, k, img, len(img), arr, len(pats), int(bound), int(bool(both_strands)),
+                     int(max_hits), C.byref(fd), C.byref(lst), C.byref(rec) if per_record else None))
         try:
             out = {"records": fd.records, "records_hit": fd.records_hit, "hits": fd.hits, "listed": fd.listed,
                    "per_pattern": np.array([[fd.per_pattern[p][0], fd.per_pattern[p][1]] for p in range(len(pats))],
@@ -680,6 +684,40 @@ class Context:
         finally:
             self.lib.dx_file_free(lst); self.lib.dx_file_free(rec)
         return out, hits
+
+    # ---- find with indels ----------------------------------------------------------------------------
+    def code_find_edit(self, d_in, in_bytes, d_boff, d_beg, d_len, n, queries, d_count=None, cap=0, d_hits=None):
+        """dx_code_find_edit: units as for code_find; queries: (codes, max_err) pairs, codes being 1 to 64 symbols 0..3, or ready
+        (code0, code1, len, max_err) tuples (symbol i in bits 2 (31 - (i & 31)) + 1, 2 (31 - (i & 31)) of code[i >> 5]).  A hit is an
+        end e with c(e) <= k, c(e) < c(e - 1) and c(e) <= c(e + 1), c being the semi-global edit distance capped at k + 1: one hit for
+        each valley of the distance, at the leftmost end of its floor; pos = e, the exclusive end of the occurrence, mis = the
+        distance.  Returns what code_find returns, in the same order (unit, pos, query)."""
+        nq, cap = len(queries), int(cap)
+        q = (L.EQuery * max(nq, 1))(*[equery(*x) for x in queries])
+        tot, hits, bad = (C.c_uint64 * max(nq, 1))(), C.c_uint64(), C.c_uint64()
+        own = d_hits is None and cap > 0
+        if own:
+            d_hits = self.alloc(16 * cap + 16)
+        try:
+            rc = self.lib.dx_code_find_edit(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
+                                            d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), q, nq,
+                                            d_count.ptr if d_count else None, d_hits.ptr if d_hits else None, cap, tot,
+                                            C.byref(hits), C.byref(bad))
+            if rc != 0:
+                raise self._bad_unit(rc, bad)
+            k = min(cap, hits.value)
+            lst = d_hits.download(np.uint8, 16 * k).view(HIT_DTYPE) if k else np.zeros(0, HIT_DTYPE)
+        finally:
+            if own:
+                d_hits.free()
+        return {"hits": hits.value, "total": np.array(list(tot)[:nq], dtype=np.uint64)}, lst
+
+    def find_edit(self, kind, img: bytes, patterns, max_errors=0, both_strands=False, max_hits=1 << 20, per_record=False):
+        """dx_file_find_edit: where the patterns (str, 1 to 64 letters) END in the reads of the image within max_errors edits
+        (substitution, insertion and deletion cost one each; the start in the read is free): one hit for each valley of the distance,
+        at the leftmost end of its floor, pos = the exclusive end of the occurrence on the read as stored, mis = the distance.
+        Everything else, and what is returned, as for find."""
+        return self._file_find(self.lib.dx_file_find_edit, kind, img, patterns, max_errors, both_strands, max_hits, per_record)
 
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
@@ -904,6 +942,17 @@ def pack2_sharded(contexts, text: bytes, arrow=False) -> bytes:
 
 # ---- host-only helpers (no GPU needed) ---------------------------------------------------------
 HIT_DTYPE = np.dtype([("record", "<u8"), ("pos", "<u4"), ("query", "<u2"), ("strand", "u1"), ("mis", "u1")])      # dx_hit
+
+
+def equery(*x):
+    """a dx_equery from (codes, max_err) -- 1 to 64 symbols 0..3, the first on top of code[0] -- or from (code0, code1, len, max_err)"""
+    if len(x) == 4:
+        return L.EQuery((C.c_uint64 * 2)(int(x[0]), int(x[1])), int(x[2]), int(x[3]))
+    codes, max_err = x
+    code = [0, 0]
+    for i, c in enumerate(codes):
+        code[i >> 5] |= int(c) << (2 * (31 - (i & 31)))
+    return L.EQuery((C.c_uint64 * 2)(*code), len(codes), int(max_err))
 
 
 def census_dict(cs) -> dict:

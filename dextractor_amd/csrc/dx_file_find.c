@@ -14,6 +14,8 @@
  * query) is the file's (record, pos, pattern, strand); dxf_find_map then names every hit by its pattern and strand.
  * An image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET, goes in slices of whole records (dxf_u2_slice_end): a
  * slice's hits are listed into what max_hits has left, its record numbers moved by the slice's first record.
+ *
+ * Everything behind the plan is dxf_find_run, which dx_file_find_edit.c calls with its own plan and kernel (edit = 1).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,7 +28,7 @@
 #define FIND_ROOM ((uint64_t) 1 << 20)       /* hits a slice is listed into at first; one with more is searched again into enough */
 
 /* a letter's code (Number_Read / Number_Arrow, DB.c:393-441), or -1 when it is none of the kind's */
-static int letter_code(int arrow, int c)
+int dxf_find_letter(int arrow, int c)
 { if (arrow) return c >= '1' && c <= '4' ? c - '1' : -1;
   switch (c)
     { case 'a': case 'A': return 0;
@@ -60,7 +62,7 @@ int dxf_find_plan(dx_ctx *ctx, int kind, const char *const *pattern, uint32_t np
           return dx_find_fail(ctx, DX_E_ARG, why);
         }
       for (i = 0; i < len; i++)
-        { const int c = letter_code(kind == DX_KIND_ARROW, (unsigned char) s[i]);
+        { const int c = dxf_find_letter(kind == DX_KIND_ARROW, (unsigned char) s[i]);
           if (c < 0)
             { snprintf(why, sizeof(why), "pattern %u, column %zu: not one of %s", p, i + 1, kind == DX_KIND_ARROW ? "1234" : "acgtACGT");
               return dx_find_fail(ctx, DX_E_ARG, why);
@@ -95,8 +97,18 @@ static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((u
 
 int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char *const *pattern, uint32_t npat, uint32_t max_mis,
                  int both_strands, uint64_t max_hits, dx_find *out, dx_hit **hits, uint32_t **rec_hits)
+{ find_plan fp;
+  int       rc;
+  if (ctx == NULL || out == NULL || (img == NULL && m)) return DX_E_ARG;
+  if (hits) *hits = NULL;
+  if (rec_hits) *rec_hits = NULL;
+  if ((rc = dxf_find_plan(ctx, kind, pattern, npat, max_mis, both_strands, &fp)) != DX_OK) return rc;
+  return dxf_find_run(ctx, kind, img, m, &fp, 0, max_hits, out, hits, rec_hits);
+}
+
+int dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find_plan *fp, int edit, uint64_t max_hits, dx_find *out,
+                 dx_hit **hits, uint32_t **rec_hits)
 { image_text im;
-  find_plan  fp;
   dx_find   *fd = NULL;
   dx_hit    *list = NULL;
   uint32_t  *rec = NULL;
@@ -106,11 +118,6 @@ int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char
   void      *d_in = NULL, *d_arr = NULL, *d_hits = NULL;
   const u2_index *x;
   int        rc;
-
-  if (ctx == NULL || out == NULL || (img == NULL && m)) return DX_E_ARG;
-  if (hits) *hits = NULL;
-  if (rec_hits) *rec_hits = NULL;
-  if ((rc = dxf_find_plan(ctx, kind, pattern, npat, max_mis, both_strands, &fp)) != DX_OK) return rc;
 
   TRY(dxf_image_open(ctx, kind, 0, 1, img, m, &im));       /* (the line width lays out a text nobody makes) */
   x = &im.ux; cnt = x->cnt;
@@ -141,13 +148,17 @@ int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char
       room = keep - kept < FIND_ROOM ? keep - kept : FIND_ROOM;
       for (;;)                                              /* (a second time only for a slice with more hits than FIND_ROOM that are wanted) */
         { TRY(dgrow(ctx, &d_hits, &hit_cap, (size_t) room * sizeof(dx_hit) + 64));
-          TRY(dx_code_find(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp.q, fp.nq, d_cnt, d_hits, room, tot, &found, NULL));
+          if (edit) TRY(dx_code_find_edit(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp->eq, fp->nq, d_cnt, d_hits, room, tot, &found, NULL));
+          else      TRY(dx_code_find(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp->q, fp->nq, d_cnt, d_hits, room, tot, &found, NULL));
           if (found <= room || room == keep - kept) break;
           room = found < keep - kept ? found : keep - kept;
-          if (room > UINT32_MAX) { rc = dx_find_fail(ctx, DX_E_NOMEM, "more than 2^32 - 1 hits of one slice to list: lower max_hits"); goto done; }
+          if (room > UINT32_MAX)
+            { rc = (edit ? dx_find_edit_fail : dx_find_fail)(ctx, DX_E_NOMEM, "more than 2^32 - 1 hits of one slice to list: lower max_hits");
+              goto done;
+            }
         }
       TRY(dx_d2h(ctx, rec + i0, d_cnt, (size_t) n * 4));
-      for (i = 0; i < fp.nq; i++) fd->per_pattern[fp.pat[i]][fp.strand[i]] += tot[i];
+      for (i = 0; i < fp->nq; i++) fd->per_pattern[fp->pat[i]][fp->strand[i]] += tot[i];
       fd->hits += found;
       { const uint64_t got = found < room ? found : room;
         if (got)
@@ -158,7 +169,7 @@ int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char
                 list = bigger; list_cap = want;
               }
             TRY(dx_d2h(ctx, list + kept, d_hits, (size_t) got * sizeof(*list)));
-            dxf_find_map(&fp, list + kept, got, i0);
+            dxf_find_map(fp, list + kept, got, i0);
             kept += got;
           }
       }

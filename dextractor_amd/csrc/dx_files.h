@@ -12,6 +12,7 @@
  *     dx_file_extract.c chosen records as text: dx_file_extract
  *     dx_file_compare.c how two images of the same records differ: dx_file_compare
  *     dx_file_find.c   where given sequences occur in an image's reads: dx_file_find
+ *     dx_file_find_edit.c  ... within an edit distance: dx_file_find_edit
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
  */
@@ -240,14 +241,27 @@ DXF_HIDDEN uint64_t dxf_u2_slice_end(const u2_index *x, uint64_t i0, size_t cap)
 /* ---- dx_file_find.c -------------------------------------------------------------------------------------------------- */
 /* The host part of dx_file_find, apart so that it can run without a device (ctx == NULL: no error text is kept).  The patterns as the
    queries of dx_code_find: query k is pattern pat[k] on strand strand[k], the queries in the order (pattern, strand), so that the
-   kernel's order (unit, pos, query) is the file's (record, pos, pattern, strand). */
-typedef struct { dx_query q[64]; uint16_t pat[64]; uint8_t strand[64]; uint32_t nq; } find_plan;
+   kernel's order (unit, pos, query) is the file's (record, pos, pattern, strand).  eq: the same patterns as the queries of
+   dx_code_find_edit, which dxf_find_edit_plan leaves in q's stead. */
+typedef struct { dx_query q[64]; uint16_t pat[64]; uint8_t strand[64]; uint32_t nq; dx_equery eq[64]; } find_plan;
 
 DXF_HIDDEN int  dxf_find_plan(dx_ctx *ctx, int kind, const char *const *pattern, uint32_t npat, uint32_t max_mis, int both_strands,
                               find_plan *fp);
 /* a slice's hits as dx_code_find listed them -- record: the unit in the slice, query: the query -- become the file's: record + i0, the
    pattern's index, the strand */
 DXF_HIDDEN void dxf_find_map(const find_plan *fp, dx_hit *h, uint64_t cnt, uint64_t i0);
+/* a letter's code (Number_Read / Number_Arrow, DB.c:393-441), or -1 when it is none of the kind's */
+DXF_HIDDEN int  dxf_find_letter(int arrow, int c);
+/* what dx_file_find does once its patterns are a plan: the image walked, its slices searched, the report and the lists made.  edit 0:
+   the queries are fp->q, searched by dx_code_find; 1: fp->eq, by dx_code_find_edit (dx_file_find_edit.c) */
+DXF_HIDDEN int  dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find_plan *fp, int edit, uint64_t max_hits, dx_find *out,
+                             dx_hit **hits, uint32_t **rec_hits);
+
+/* ---- dx_file_find_edit.c --------------------------------------------------------------------------------------------- */
+/* The host part of dx_file_find_edit, apart so that it can run without a device (ctx == NULL: no error text is kept): the patterns as
+   the queries of dx_code_find_edit in fp->eq, with pat, strand and nq as dxf_find_plan leaves them (fp->q stays empty). */
+DXF_HIDDEN int  dxf_find_edit_plan(dx_ctx *ctx, int kind, const char *const *pattern, uint32_t npat, uint32_t max_err, int both_strands,
+                                   find_plan *fp);
 
 /* ---- dx_file_compare.c ----------------------------------------------------------------------------------------------- */
 /* Two images of one kind, walked and paired by index: the first `both` records of each are compared.  pa / pb (both + 1 each): what the

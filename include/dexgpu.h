@@ -869,6 +869,52 @@ int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
                  uint64_t max_hits, dx_find *out, dx_hit **hits /* may be NULL */, uint32_t **rec_hits /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ *  find with indels: where given sequences occur within an edit distance  (raw reads err by insertion and deletion, which the
+ *  Hamming distance of find does not see: an adapter with one inserted base is half its length away from the pattern)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { uint64_t code[2]; uint32_t len, max_err; } dx_equery;  /* symbol i of the query in bits 2 (31 - (i & 31)) + 1, 2 (31 - (i & 31))
+                                                                           of code[i >> 5]: the first symbol on top of code[0]; unused bits are 0 */
+#define DX_FIND_EDIT_STRETCH 128u       /* the ends a lane of the kernel takes at a time (csrc/find/dx_find_edit.hip says why): no part of the
+                                           answer, which is the same for any value; here for the tests, which lay hits across its multiples */
+
+/* Up to 64 queries of 1 to 64 symbols searched in n packed reads where they lie, nothing decoded, by Myers' bit-vector algorithm
+ * (csrc/find/dx_find_edit.hip).  Unit j is what it is for dx_code_find.  For a unit U of L symbols and a query P of m symbols with the
+ * error bound k = max_err, 0 <= k < m:
+ *     D(e) = min over 0 <= s <= e of Levenshtein(P, U[s, e)) for 1 <= e <= L; substitution, insertion and deletion each cost one; the
+ *            alignment is semi-global: the start in the read is free;
+ *     c(e) = min(D(e), k + 1), and c(0) = c(L + 1) = k + 1.
+ * A hit of the query in the unit is an end e with c(e) <= k, c(e) < c(e - 1) and c(e) <= c(e + 1): one hit for each valley of the
+ * distance, at the leftmost end of its floor.  The hit reports pos = e, the EXCLUSIVE END of the occurrence, not its start, and
+ * mis = D(e).  The start lies in [e - m - D(e), e - m + D(e)]; finding it exactly is out of scope.  A unit shorter than m - k has no
+ * hit; duplicate queries each report.  The symbols in front of d_beg[j], those behind the unit's end, the pad bits of a read's last
+ * byte and every byte that is not the unit's take part in nothing, and nothing outside [0, in_bytes) is read.
+ * d_count, total, *hits, d_hits, cap and the list's order (unit, pos, query) are dx_code_find's: d_count[j] saturated at UINT32_MAX,
+ * a total a query, *hits all hits listed or not, the first min(cap, *hits) in d_hits, the same on every call (places come from
+ * counts and prefix sums, no atomic cursor), not one byte written at cap or beyond, cap == 0 runs the counting pass alone.
+ * DX_E_FORMAT with *bad_unit as for dx_code_find.  DX_E_ARG for nq outside 1..64, a len outside 1..64, max_err >= len, bits of code
+ * behind the len symbols, a NULL pointer that is needed, n >= 2^31, cap >= 2^32.  n == 0 gives zeros.                              */
+int dx_code_find_edit(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                      const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                      const dx_equery *q /* host */, uint32_t nq /* 1..64 */,
+                      uint32_t *d_count /* n, may be NULL */, dx_hit *d_hits /* cap, may be NULL when cap == 0 */, uint64_t cap,
+                      uint64_t total[] /* host, nq; may be NULL */, uint64_t *hits /* host: all of them, listed or not */,
+                      uint64_t *bad_unit /* may be NULL */);
+
+/* dx_file_find with that distance: which records of a .dexta / .dexar image contain the patterns within max_err edits, and where
+ * they END.  A pattern is 1 to 64 letters; npat is 1 to 64, with both_strands 1 to 32; max_err (one figure for all patterns) is
+ * below the shortest pattern's length.  A hit is what it is for dx_code_find_edit -- one for each valley of the distance, pos = the
+ * exclusive end of the occurrence on the read as stored, mis = the distance --; a reverse complement's hit has strand 1 and its pos
+ * is the end of the reverse complement's occurrence on the read as stored.  Everything else is dx_file_find's: the letters, the
+ * kinds, both_strands (a pattern that is its own reverse complement is searched once), what *out, *hits and *rec_hits hold, their
+ * order (record, pos, pattern, strand), the slices of whole records with record numbers, order and max_hits running across them,
+ * and the errors (DX_E_ARG for DX_KIND_QUIVA, a pattern of 0 or more than 64 letters or with a letter that is not the kind's --
+ * dx_last_error names the pattern's index and the column --, npat out of range, max_err not below the shortest pattern,
+ * both_strands for arrow).                                                                                                       */
+int dx_file_find_edit(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
+                      const char *const *pattern, uint32_t npat, uint32_t max_err, int both_strands,
+                      uint64_t max_hits, dx_find *out, dx_hit **hits /* may be NULL */, uint32_t **rec_hits /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed

@@ -29,6 +29,7 @@
 
 /* (find/dx_find.hip has it in the library, hidden: here no context has a text to keep) */
 int dx_find_fail(dx_ctx *ctx, int code, const char *what) { (void) ctx; (void) what; return code; }
+int dx_find_edit_fail(dx_ctx *ctx, int code, const char *what) { (void) ctx; (void) what; return code; }      /* (dx_file_find.c's driver serves dx_file_find_edit too) */
 
 static uint8_t *slurp(const char *path, size_t *n)
 { FILE *f = fopen(path, "rb");
