@@ -100,7 +100,11 @@ class Find(C.Structure):                         # dx_find
     _fields_ = [("records", C.c_uint64), ("records_hit", C.c_uint64), ("hits", C.c_uint64), ("listed", C.c_uint64),
                 ("per_pattern", (C.c_uint64 * 2) * 64)]
 
+class Cut(C.Structure):                          # dx_cut
+    _fields_ = [(f, C.c_uint64) for f in ("records_in", "records_cut", "records_dropped", "pieces", "symbols_in", "symbols_kept", "spans")]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
+DX_CUT_SPLIT, DX_CUT_LONGEST, DX_CUT_DROP = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
 # name -> (restype, argtypes); every symbol include/dexgpu.h declares
@@ -228,6 +232,15 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dx_file_find_edit": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint64,
                                     C.POINTER(Find), C.POINTER(_P), C.POINTER(_P)]),
+    "dx_code_hit_starts": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(EQuery), C.c_uint32, _P, C.c_uint64, _P,
+                                     C.POINTER(C.c_uint64)]),
+    "dx_file_find_edit_spans": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint64,
+                                          C.POINTER(Find), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "dx_hits_cut_plan": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                   C.POINTER(C.c_uint64), C.POINTER(Cut)]),
+    "dx_file_cut": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int,
+                              C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(Cut), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                              C.POINTER(C.c_uint64)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

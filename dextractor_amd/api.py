@@ -719,6 +719,82 @@ class Context:
         Everything else, and what is returned, as for find."""
         return self._file_find(self.lib.dx_file_find_edit, kind, img, patterns, max_errors, both_strands, max_hits, per_record)
 
+    # ---- cut: where the occurrences start, and an image cut at them ----------------------------------
+    def code_hit_starts(self, d_in, in_bytes, d_boff, d_beg, d_len, n, queries, d_hits, n_hits, d_start=None):
+        """dx_code_hit_starts: units and queries as for code_find_edit; d_hits: n_hits hits on the device exactly as code_find_edit
+        left them.  For every hit the LARGEST s with Levenshtein(query, unit[s, pos)) == mis -- the start of the shortest stretch that
+        ends at pos and lies mis edits from the query.  d_start (uint32, n_hits, or None: made here): the starts, which come back as a
+        uint32 array.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the smallest index of a bad hit, whose start is 2**32 - 1; the
+        others' are written, and .starts has them all) for a hit that is none of these units and queries."""
+        nq, n_hits = len(queries), int(n_hits)
+        q = (L.EQuery * max(nq, 1))(*[equery(*x) for x in queries])
+        bad = C.c_uint64()
+        own = d_start is None and n_hits > 0
+        if own:
+            d_start = self.alloc(4 * n_hits + 16)
+        try:
+            rc = self.lib.dx_code_hit_starts(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
+                                             d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), q, nq,
+                                             d_hits.ptr if d_hits else None, n_hits, d_start.ptr if d_start else None, C.byref(bad))
+            starts = None
+            if rc in (0, -3) and n_hits and d_start is not None and n_hits < 2**32:
+                starts = d_start.download(np.uint32, n_hits)
+            if rc != 0:
+                e = self._bad_unit(rc, bad)
+                e.starts = starts
+                raise e
+        finally:
+            if own:
+                d_start.free()
+        return starts if starts is not None else np.zeros(0, np.uint32)
+
+    def find_spans(self, kind, img: bytes, patterns, max_errors=0, both_strands=False, max_hits=1 << 20, per_record=False):
+        """dx_file_find_edit_spans: find_edit's return -- the same report, the same hits -- and in the report "start": uint32, one a
+        listed hit, the first symbol of its occurrence on the read as stored (the occurrence is the record's symbols [start, pos)),
+        and "rec_len": uint32 a record, its symbols."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
+        arr = (C.c_char_p * max(len(pats), 1))(*pats)
+        fd, lst, rec, st, rl = L.Find(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.dx_file_find_edit_spans(self.h, k, img, len(img), arr, len(pats), int(max_errors), int(bool(both_strands)),
+                                                   int(max_hits), C.byref(fd), C.byref(lst), C.byref(rec) if per_record else None,
+                                                   C.byref(st), C.byref(rl)))
+        try:
+            out = {"records": fd.records, "records_hit": fd.records_hit, "hits": fd.hits, "listed": fd.listed,
+                   "per_pattern": np.array([[fd.per_pattern[p][0], fd.per_pattern[p][1]] for p in range(len(pats))],
+                                           dtype=np.uint64).reshape(len(pats), 2)}
+            hits, out["start"] = np.zeros(0, HIT_DTYPE), np.zeros(0, np.uint32)
+            if fd.listed:
+                hits = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * fd.listed,)).view(HIT_DTYPE).copy()
+                out["start"] = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint32)), (fd.listed,)).copy()
+            out["rec_len"] = np.ctypeslib.as_array(C.cast(rl, C.POINTER(C.c_uint32)), (fd.records + 1,))[:fd.records].copy()
+            if per_record:
+                out["rec_hits"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), (fd.records + 1,))[:fd.records].copy()
+        finally:
+            for p in (lst, rec, st, rl):
+                self.lib.dx_file_free(p)
+        return out, hits
+
+    def cut(self, kind, img: bytes, patterns, max_errors=0, both_strands=False, min_len=0, mode="split"):
+        """dx_file_cut: the image ("fasta" or "arrow") with the occurrences of the patterns within max_errors edits cut out of its
+        records -- find_spans with every hit listed, cut_plan, subset -- byte for byte what dexta / dexar writes for the cut text.
+        mode: "split" (every piece of at least min_len symbols between the occurrences, the id repeating), "longest" (the longest
+        such piece of a record, on a tie the first) or "drop" (only the records without an occurrence, whole).  Returns (image,
+        report, selection): the report is cut_plan's, and the selection {"ids", "beg", "end"} is what Context.subset takes to cut the
+        .dexar and the .dexqv of the same records in the same places."""
+        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
+        arr = (C.c_char_p * max(len(pats), 1))(*pats)
+        out, ln, cut, n = C.c_void_p(), C.c_size_t(), L.Cut(), C.c_uint64()
+        sel = [C.c_void_p() for _ in range(3)]
+        self._chk(self.lib.dx_file_cut(self.h, k, img, len(img), arr, len(pats), int(max_errors), int(bool(both_strands)), int(min_len),
+                                       _cut_mode(mode), C.byref(out), C.byref(ln), C.byref(cut), *[C.byref(a) for a in sel], C.byref(n)))
+        try:
+            return C.string_at(out.value, ln.value), cut_dict(cut), _cut_selection(sel, n.value)
+        finally:
+            for p in [out] + sel:
+                self.lib.dx_file_free(p)
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -953,6 +1029,44 @@ def equery(*x):
     for i, c in enumerate(codes):
         code[i >> 5] |= int(c) << (2 * (31 - (i & 31)))
     return L.EQuery((C.c_uint64 * 2)(*code), len(codes), int(max_err))
+
+
+def _cut_mode(mode):
+    return mode if isinstance(mode, int) else {"split": L.DX_CUT_SPLIT, "longest": L.DX_CUT_LONGEST, "drop": L.DX_CUT_DROP}[mode]
+
+
+def cut_dict(cut) -> dict:
+    """a dx_cut as a dict"""
+    return {f: int(getattr(cut, f)) for f, _ in L.Cut._fields_}
+
+
+def _cut_selection(sel, n):
+    return {name: np.ctypeslib.as_array(C.cast(a, C.POINTER(t)), (n + 1,))[:n].copy()
+            for name, a, t in zip(("ids", "beg", "end"), sel, (C.c_uint64, C.c_uint32, C.c_uint32))}
+
+
+def cut_plan(hits, start, rec_len, min_len=0, mode="split"):
+    """dx_hits_cut_plan (host, no GPU): what is kept of every record once the occurrences [start[i], hits[i].pos) are cut out.  hits: a
+    HIT_DTYPE array (record and pos are read), start: uint32 beside it, rec_len: every record's symbols; mode as for Context.cut.
+    Returns (selection {"ids", "beg", "end"} as Context.subset takes it, report {"records_in", "records_cut", "records_dropped",
+    "pieces", "symbols_in", "symbols_kept", "spans"})."""
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    st = np.ascontiguousarray(start, dtype=np.uint32)
+    rl = np.ascontiguousarray(rec_len, dtype=np.uint32)
+    if len(h) != len(st):
+        raise ValueError("hits / start: one start a hit")
+    lib = L.load()
+    sel, n, cut = [C.c_void_p() for _ in range(3)], C.c_uint64(), L.Cut()
+    rc = lib.dx_hits_cut_plan(h.ctypes.data if len(h) else None, st.ctypes.data if len(st) else None, len(h),
+                              rl.ctypes.data if len(rl) else None, len(rl), int(min_len), _cut_mode(mode),
+                              *[C.byref(a) for a in sel], C.byref(n), C.byref(cut))
+    if rc != 0:
+        raise L.DexGPUError(rc, "dx_hits_cut_plan")
+    try:
+        return _cut_selection(sel, n.value), cut_dict(cut)
+    finally:
+        for a in sel:
+            lib.dx_file_free(a)
 
 
 def census_dict(cs) -> dict:

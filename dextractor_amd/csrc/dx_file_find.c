@@ -15,7 +15,8 @@
  * An image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET, goes in slices of whole records (dxf_u2_slice_end): a
  * slice's hits are listed into what max_hits has left, its record numbers moved by the slice's first record.
  *
- * Everything behind the plan is dxf_find_run, which dx_file_find_edit.c calls with its own plan and kernel (edit = 1).
+ * Everything behind the plan is dxf_find_run, which dx_file_find_edit.c calls with its own plan and kernel (edit = 1) -- and, for
+ * dx_file_find_edit_spans, with a place for the occurrences' starts: dx_code_hit_starts then runs once a slice behind its listing.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -103,19 +104,19 @@ int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char
   if (hits) *hits = NULL;
   if (rec_hits) *rec_hits = NULL;
   if ((rc = dxf_find_plan(ctx, kind, pattern, npat, max_mis, both_strands, &fp)) != DX_OK) return rc;
-  return dxf_find_run(ctx, kind, img, m, &fp, 0, max_hits, out, hits, rec_hits);
+  return dxf_find_run(ctx, kind, img, m, &fp, 0, max_hits, out, hits, rec_hits, NULL, NULL);
 }
 
 int dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find_plan *fp, int edit, uint64_t max_hits, dx_find *out,
-                 dx_hit **hits, uint32_t **rec_hits)
+                 dx_hit **hits, uint32_t **rec_hits, uint32_t **start, uint32_t **rec_len)
 { image_text im;
   dx_find   *fd = NULL;
   dx_hit    *list = NULL;
-  uint32_t  *rec = NULL;
+  uint32_t  *rec = NULL, *st = NULL, *rlen = NULL;
   uint64_t  *rel = NULL, cnt, i, i0, i1, most = 0, list_cap = 0, kept = 0, tot[64];
   const uint64_t keep = hits != NULL ? max_hits : 0;       /* hits the list is to hold (nobody takes it: none) */
-  size_t     cap, smax = 0, in_cap = 0, arr_cap = 0, hit_cap = 0;
-  void      *d_in = NULL, *d_arr = NULL, *d_hits = NULL;
+  size_t     cap, smax = 0, in_cap = 0, arr_cap = 0, hit_cap = 0, st_cap = 0;
+  void      *d_in = NULL, *d_arr = NULL, *d_hits = NULL, *d_st = NULL;
   const u2_index *x;
   int        rc;
 
@@ -123,6 +124,10 @@ int dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find
   x = &im.ux; cnt = x->cnt;
   if ((fd = calloc(1, sizeof(*fd))) == NULL || (rec = malloc((cnt + 1) * sizeof(*rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
   fd->records = cnt;
+  if (rec_len)
+    { if ((rlen = malloc((cnt + 1) * sizeof(*rlen))) == NULL) { rc = DX_E_NOMEM; goto done; }
+      if (cnt) memcpy(rlen, x->nsym, (size_t) cnt * sizeof(*rlen));
+    }
 
   cap = cnt ? dxf_u2_cap(ctx, m, cnt) : 0;
   for (i0 = 0; i0 < cnt; i0 = i1)                          /* the largest slice: one allocation serves them all */
@@ -167,6 +172,16 @@ int dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find
                 dx_hit *bigger = realloc(list, (size_t) want * sizeof(*list));
                 if (bigger == NULL) { rc = DX_E_NOMEM; goto done; }
                 list = bigger; list_cap = want;
+                if (start)
+                  { uint32_t *more = realloc(st, (size_t) want * sizeof(*st));
+                    if (more == NULL) { rc = DX_E_NOMEM; goto done; }
+                    st = more;
+                  }
+              }
+            if (start)                                      /* the slice's image and its unit-relative hits are still on the device */
+              { TRY(dgrow(ctx, &d_st, &st_cap, (size_t) got * sizeof(*st) + 64));
+                TRY(dx_code_hit_starts(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp->eq, fp->nq, d_hits, got, d_st, NULL));
+                TRY(dx_d2h(ctx, st + kept, d_st, (size_t) got * sizeof(*st)));
               }
             TRY(dx_d2h(ctx, list + kept, d_hits, (size_t) got * sizeof(*list)));
             dxf_find_map(fp, list + kept, got, i0);
@@ -177,17 +192,21 @@ int dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find
   for (i = 0; i < cnt; i++) fd->records_hit += rec[i] != 0;
   fd->listed = fd->hits < max_hits ? fd->hits : max_hits;
   if (hits != NULL && list == NULL && (list = malloc(sizeof(*list))) == NULL) { rc = DX_E_NOMEM; goto done; }
+  if (start != NULL && st == NULL && (st = malloc(sizeof(*st))) == NULL) { rc = DX_E_NOMEM; goto done; }
 
   *out = *fd;
   if (hits) { *hits = list; list = NULL; }
   if (rec_hits) { *rec_hits = rec; rec = NULL; }
+  if (start) { *start = st; st = NULL; }
+  if (rec_len) { *rec_len = rlen; rlen = NULL; }
   rc = DX_OK;
 
 done:
   if (d_in) (void) dx_free(ctx, d_in);
   if (d_arr) (void) dx_free(ctx, d_arr);
   if (d_hits) (void) dx_free(ctx, d_hits);
+  if (d_st) (void) dx_free(ctx, d_st);
   dxf_image_close(&im);
-  free(fd); free(list); free(rec); free(rel);
+  free(fd); free(list); free(rec); free(rel); free(st); free(rlen);
   return rc;
 }

@@ -1,6 +1,6 @@
 /*
  * dx_file_find_edit.c -- where given sequences occur in the reads of a .dexta / .dexar image with insertions and deletions allowed:
- * dx_file_find_edit.
+ * dx_file_find_edit, and dx_file_find_edit_spans, which lists where every occurrence BEGINS beside where it ends.
  *
  * dx_file_find's distance is Hamming's, and the reads these archives hold err by insertion and deletion: an adapter with one inserted
  * base is half its length away from the pattern.  Here the distance is Levenshtein's, the alignment semi-global (the start in the read
@@ -10,7 +10,7 @@
  * complement is the codes 3 - c in reverse order, and a pattern that equals its own is searched once --, in the order (pattern,
  * strand).  Everything else is dx_file_find.c's (dxf_find_run): the image's walk, the slices of whole records, the FIND_ROOM retry,
  * the record numbers, the order and max_hits across slices, dxf_find_map.  A strand-1 hit's pos is the end of the reverse complement's
- * occurrence on the read as stored.
+ * occurrence on the read as stored, and its start (dx_file_find_edit_spans) the leftmost symbol of that occurrence.
  */
 #include <stdio.h>
 #include <string.h>
@@ -75,5 +75,20 @@ int dx_file_find_edit(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const
   if (hits) *hits = NULL;
   if (rec_hits) *rec_hits = NULL;
   if ((rc = dxf_find_edit_plan(ctx, kind, pattern, npat, max_err, both_strands, &fp)) != DX_OK) return rc;
-  return dxf_find_run(ctx, kind, img, m, &fp, 1, max_hits, out, hits, rec_hits);
+  return dxf_find_run(ctx, kind, img, m, &fp, 1, max_hits, out, hits, rec_hits, NULL, NULL);
+}
+
+int dx_file_find_edit_spans(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char *const *pattern, uint32_t npat, uint32_t max_err,
+                            int both_strands, uint64_t max_hits, dx_find *out, dx_hit **hits, uint32_t **rec_hits, uint32_t **start,
+                            uint32_t **rec_len)
+{ find_plan fp;
+  int       rc;
+  if (ctx == NULL || out == NULL || (img == NULL && m)) return DX_E_ARG;
+  if (hits) *hits = NULL;
+  if (rec_hits) *rec_hits = NULL;
+  if (start) *start = NULL;
+  if (rec_len) *rec_len = NULL;
+  if (start != NULL && hits == NULL) return dx_find_edit_fail(ctx, DX_E_ARG, "the starts stand beside the hits: start without hits");
+  if ((rc = dxf_find_edit_plan(ctx, kind, pattern, npat, max_err, both_strands, &fp)) != DX_OK) return rc;
+  return dxf_find_run(ctx, kind, img, m, &fp, 1, max_hits, out, hits, rec_hits, start, rec_len);
 }

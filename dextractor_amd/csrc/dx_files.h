@@ -12,7 +12,8 @@
  *     dx_file_extract.c chosen records as text: dx_file_extract
  *     dx_file_compare.c how two images of the same records differ: dx_file_compare
  *     dx_file_find.c   where given sequences occur in an image's reads: dx_file_find
- *     dx_file_find_edit.c  ... within an edit distance: dx_file_find_edit
+ *     dx_file_find_edit.c  ... within an edit distance: dx_file_find_edit, dx_file_find_edit_spans
+ *     dx_file_cut.c    what is kept of the records once the occurrences are cut out, and the image of it: dx_hits_cut_plan (host), dx_file_cut
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
  */
@@ -253,9 +254,11 @@ DXF_HIDDEN void dxf_find_map(const find_plan *fp, dx_hit *h, uint64_t cnt, uint6
 /* a letter's code (Number_Read / Number_Arrow, DB.c:393-441), or -1 when it is none of the kind's */
 DXF_HIDDEN int  dxf_find_letter(int arrow, int c);
 /* what dx_file_find does once its patterns are a plan: the image walked, its slices searched, the report and the lists made.  edit 0:
-   the queries are fp->q, searched by dx_code_find; 1: fp->eq, by dx_code_find_edit (dx_file_find_edit.c) */
+   the queries are fp->q, searched by dx_code_find; 1: fp->eq, by dx_code_find_edit (dx_file_find_edit.c).  start (edit alone; NULL:
+   nothing is launched for it) gets the listed hits' starts, one dx_code_hit_starts a slice behind its listing; rec_len (may be NULL)
+   every record's symbols */
 DXF_HIDDEN int  dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find_plan *fp, int edit, uint64_t max_hits, dx_find *out,
-                             dx_hit **hits, uint32_t **rec_hits);
+                             dx_hit **hits, uint32_t **rec_hits, uint32_t **start, uint32_t **rec_len);
 
 /* ---- dx_file_find_edit.c --------------------------------------------------------------------------------------------- */
 /* The host part of dx_file_find_edit, apart so that it can run without a device (ctx == NULL: no error text is kept): the patterns as

@@ -8,7 +8,8 @@
 //     c(e) = min(D(e), k + 1),   c(0) = c(L + 1) = k + 1
 // and a HIT is an end e with c(e) <= k, c(e) < c(e - 1) and c(e) <= c(e + 1): one hit for each valley of the distance, at the
 // leftmost end of its floor.  pos = e is the EXCLUSIVE END of the occurrence, not its start; mis = D(e).  The start lies in
-// [e - m - D(e), e - m + D(e)]; finding it exactly (a traceback, or the reverse pattern run backwards from e) is out of scope here.
+// [e - m - D(e), e - m + D(e)]; dx_code_hit_starts (find/dx_find_span.hip: the reverse pattern run backwards from e) finds it exactly,
+// and dx_file_find_edit_spans lists it beside every hit of a file.
 //
 // D is computed by the bit-vector algorithm of Myers (1999) in the formulation of Hyyro: a column of the DP matrix is one word of
 // vertical deltas (Pv, Mv), a text symbol costs a fixed number of word operations, and the semi-global form (the start in the read is
@@ -62,23 +63,18 @@
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip), like find/dx_find.hip; its kernels
 // are timed with events on the context's stream (tools/find_edit_rate.py).
 #include "units/dx_units.hpp"
+#include "find/dx_find_edit.hpp"           // fe_query, fe_queries, FE_QMAX: the queries as the kernel reads them (dx_find_span.hip's too)
 
 extern "C" {
 #include "dx_host.h"
 }
 
-#define FE_QMAX    64u                     // queries a call
-#define FE_BATCH   1u                      // units a ticket at least
+#define FE_BATCH   1u                     // units a ticket at least
 #define FE_TARGET  (4u << 10)              // packed bytes a ticket and query (a symbol costs some three times k_find's): FE_FLOOR at least
 #define FE_FLOOR   (1u << 10)
 #define FE_STRETCH DX_FIND_EDIT_STRETCH    // ends a lane takes at a time (dexgpu.h; the size is argued above)
 #define FE_LANE    4u                      // stretches: a unit of up to so many is its lane's
 #define FE_GROUP   UNITS_GROUP             // stretches: up to here 16 lanes take the unit, beyond the wave
-
-// a query as the kernel reads it: the two bit planes of its symbols (b0: the low bits, b1: the high), symbol i in bit 64 - len + i --
-// the query's LAST symbol in the word's top bit, where the score's delta is read without a shift by len --, and `low`: the bits below
-struct fe_query   { uint64_t b0, b1, low; uint32_t len, err; };     // 32 bytes
-struct fe_queries { fe_query q[FE_QMAX]; };
 
 int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
 
@@ -328,7 +324,7 @@ void k_find_edit(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bou
 // ---------------------------------------------------------------------------------------------
 //  the entry point
 // ---------------------------------------------------------------------------------------------
-static_assert(sizeof(dx_hit) == 16 && sizeof(dx_equery) == 24 && sizeof(fe_query) == 32, "a hit is one 16-byte store; 64 queries fit a kernel argument");
+static_assert(sizeof(dx_hit) == 16, "a hit is one 16-byte store");
 static_assert(FE_STRETCH * FE_QMAX <= 0xffffu + 1u && FE_STRETCH * DX_BLOCK * 2u <= (64u << 10), "the place words: 16 bits each, 64 KiB a workgroup");
 
 extern "C" int dx_code_find_edit(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
@@ -343,20 +339,8 @@ extern "C" int dx_code_find_edit(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_b
   if (cap > 0xffffffffull) return dx_fail(ctx, DX_E_ARG, "dx_code_find_edit: a list of more than 2^32 - 1 hits");
   if (total) memset(total, 0, (size_t) nq * 8u);
   fe_queries Q;
-  memset(&Q, 0, sizeof(Q));
-  for (uint32_t k = 0; k < nq; k++)
-    { const uint32_t m = q[k].len;
-      if (m < 1u || m > 64u) return dx_fail(ctx, DX_E_ARG, "dx_code_find_edit: query %u has %u symbols (1 to 64)", k, m);
-      if (q[k].max_err >= m)
-        return dx_fail(ctx, DX_E_ARG, "dx_code_find_edit: query %u: %u errors are not below its %u symbols", k, q[k].max_err, m);
-      for (uint32_t i = 0; i < 64u; i++)
-        { const uint64_t c = (q[k].code[i >> 5] >> (2u * (31u - (i & 31u)))) & 3u;
-          if (i < m) { Q.q[k].b0 |= (c & 1u) << (64u - m + i); Q.q[k].b1 |= (c >> 1) << (64u - m + i); }
-          else if (c) return dx_fail(ctx, DX_E_ARG, "dx_code_find_edit: query %u has bits behind its %u symbols", k, m);
-        }
-      Q.q[k].low = m < 64u ? (1ull << (64u - m)) - 1u : 0ull;
-      Q.q[k].len = m; Q.q[k].err = q[k].max_err;
-    }
+  int rq = fe_queries_make(ctx, "dx_code_find_edit", q, nq, false, &Q);
+  if (rq != DX_OK) return rq;
   if (n >= (1ull << 31)) return dx_fail(ctx, DX_E_ARG, "dx_code_find_edit: more than 2^31 - 1 units in one batch");
   if (n == 0) return DX_OK;
 

@@ -885,7 +885,7 @@ typedef struct { uint64_t code[2]; uint32_t len, max_err; } dx_equery;  /* symbo
  *     c(e) = min(D(e), k + 1), and c(0) = c(L + 1) = k + 1.
  * A hit of the query in the unit is an end e with c(e) <= k, c(e) < c(e - 1) and c(e) <= c(e + 1): one hit for each valley of the
  * distance, at the leftmost end of its floor.  The hit reports pos = e, the EXCLUSIVE END of the occurrence, not its start, and
- * mis = D(e).  The start lies in [e - m - D(e), e - m + D(e)]; finding it exactly is out of scope.  A unit shorter than m - k has no
+ * mis = D(e).  The start lies in [e - m - D(e), e - m + D(e)]; dx_code_hit_starts finds it exactly.  A unit shorter than m - k has no
  * hit; duplicate queries each report.  The symbols in front of d_beg[j], those behind the unit's end, the pad bits of a read's last
  * byte and every byte that is not the unit's take part in nothing, and nothing outside [0, in_bytes) is read.
  * d_count, total, *hits, d_hits, cap and the list's order (unit, pos, query) are dx_code_find's: d_count[j] saturated at UINT32_MAX,
@@ -913,6 +913,84 @@ int dx_code_find_edit(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
 int dx_file_find_edit(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
                       const char *const *pattern, uint32_t npat, uint32_t max_err, int both_strands,
                       uint64_t max_hits, dx_find *out, dx_hit **hits /* may be NULL */, uint32_t **rec_hits /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
+ *  cut: where the occurrences start, and an archive cut at them  (undexta of the whole file, a text scan on one core and dexta again
+ *  today -- and the same once more for the .dexar and the .dexqv of the same run)
+ * ------------------------------------------------------------------------------------------ */
+/* The starts of the occurrences dx_code_find_edit found (csrc/find/dx_find_span.hip).  Units and queries are dx_code_find_edit's, and
+ * d_hits is a list exactly as that call leaves it: record = the unit j, pos = the end e, query = the index into q, mis = the distance
+ * d (strand is not read).  For every hit
+ *     d_start[i] = the LARGEST s, 0 <= s <= e, with Levenshtein(P, U_j[s, e)) == d
+ * -- the shortest stretch of the unit that ends at e and lies d edits from the pattern; |(e - s) - m| <= d.  It is found by the
+ * bit-vector recurrence with the query reversed and the start anchored at e, stepped backwards from symbol e - 1 for at most m + d
+ * symbols, one lane a hit.  No symbol in front of d_beg[j] is read, and nothing outside [0, in_bytes).  Hit i writes d_start[i] and
+ * nothing else; n_hits == 0 launches nothing.
+ * A hit is BAD when record >= n, its unit does not lie inside the in_bytes (the unit is not read), pos == 0 or pos > d_len[record],
+ * query >= nq, mis > q[query].max_err, or no stretch that ends at pos lies mis from the query (the hit is not one of this data): its
+ * d_start is UINT32_MAX, the good hits' starts are written all the same, and the call returns DX_E_FORMAT with *bad_hit = the
+ * smallest such index (UINT64_MAX otherwise; may be NULL), one read-back a call.  DX_E_ARG for what dx_code_find_edit refuses in q and
+ * nq, a NULL pointer that is needed, n >= 2^31, n_hits >= 2^32.                                                                    */
+int dx_code_hit_starts(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                       const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                       const dx_equery *q /* host */, uint32_t nq /* 1..64 */,
+                       const dx_hit *d_hits, uint64_t n_hits, uint32_t *d_start /* n_hits */, uint64_t *bad_hit /* may be NULL */);
+
+/* dx_file_find_edit with both ends of every listed occurrence: the same arguments, the same *out, *hits and *rec_hits, and beside them
+ * *start (malloc'd, dx_file_free): `listed` values, (*start)[i] the first symbol of hit i's occurrence on the read as stored, so that
+ * the occurrence is the record's symbols [(*start)[i], (*hits)[i].pos) -- for a strand-1 hit the leftmost symbol of the reverse
+ * complement's occurrence.  The start is dx_code_hit_starts': the shortest stretch that ends at pos and lies mis edits from the
+ * pattern.  *rec_len (may be NULL; malloc'd) = every record's symbols, from the walk the driver makes anyway.  The starts of a slice are
+ * computed while its image and its hits are still on the device, one launch a slice behind the listing; record numbers, the order and
+ * max_hits run across slices as for dx_file_find_edit.  start != NULL wants hits != NULL (DX_E_ARG); start == NULL is
+ * dx_file_find_edit.                                                                                                              */
+int dx_file_find_edit_spans(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
+                            const char *const *pattern, uint32_t npat, uint32_t max_err, int both_strands,
+                            uint64_t max_hits, dx_find *out, dx_hit **hits, uint32_t **rec_hits /* may be NULL */,
+                            uint32_t **start, uint32_t **rec_len /* may be NULL */);
+
+#define DX_CUT_SPLIT   0                /* every piece between the occurrences, in order */
+#define DX_CUT_LONGEST 1                /* the longest piece of a record; on a tie the first */
+#define DX_CUT_DROP    2                /* only the records without an occurrence, whole */
+typedef struct
+  { uint64_t records_in;                /* the records the plan was made for */
+    uint64_t records_cut;               /* records with an occurrence of which something is kept */
+    uint64_t records_dropped;           /* records with an occurrence of which nothing is kept */
+    uint64_t pieces;                    /* units of the selection: the kept pieces and the untouched records */
+    uint64_t symbols_in, symbols_kept;
+    uint64_t spans;                     /* occurrences after the union of those that overlap or touch */
+  } dx_cut;
+
+/* Host only, no GPU: what is kept of every record once the occurrences are cut out, as a selection dx_file_subset accepts.  hits and
+ * start are n_hits values as dx_file_find_edit_spans leaves them (record, pos and the start beside it; any order: they are sorted
+ * here); rec_len has `records` lengths.  Within a record the spans [start, pos) of all patterns and strands are united -- spans that
+ * overlap or touch become one --, and the PIECES are what lies between the united spans, in front of the first and behind the last;
+ * a piece has one symbol at least.  (An empty span, start == pos, which the search never reports, cuts nothing out and parts the
+ * record where it stands.)
+ *   DX_CUT_SPLIT:   every piece of at least min_len symbols, in order; the id repeats, as dextract writes several subreads of a well;
+ *   DX_CUT_LONGEST: the longest such piece of a record, on a tie the first;
+ *   DX_CUT_DROP:    nothing of a record with an occurrence.
+ * A record without an occurrence is kept whole, [0, its length), in every mode and whatever min_len is.  *ids, *beg, *end (malloc'd,
+ * dx_file_free; *n_ids values each) come out with the ids not decreasing and the pieces of a record in order; *n_ids == 0 is DX_OK
+ * here (dx_file_subset refuses it).  *report may be NULL.  DX_E_ARG for a hit with start > pos (a bad hit's UINT32_MAX among them),
+ * pos > its record's length, record >= records, an unknown mode, a NULL pointer that is needed; nothing is handed back then.    */
+int dx_hits_cut_plan(const dx_hit *hits, const uint32_t *start, uint64_t n_hits, const uint32_t *rec_len, uint64_t records,
+                     uint32_t min_len, int mode, uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids,
+                     dx_cut *report /* may be NULL */);
+
+/* A .dexta / .dexar image with the occurrences of the patterns cut out: dx_file_find_edit_spans with max_hits unlimited (patterns,
+ * max_err, both_strands and their refusals are dx_file_find_edit's), dx_hits_cut_plan, dx_file_subset.  *out (malloc'd, dx_file_free;
+ * *out_len bytes) is BYTE FOR BYTE the file dexta / dexar writes for the text of img with every record cut as the plan says and the
+ * well/B_E of its header lines rewritten, as for dx_file_subset.  The selection comes back too (*ids, *beg, *end: malloc'd, *n_ids
+ * values each; each may be NULL), so that the caller can apply it with dx_file_subset to the .dexar and the .dexqv of the same
+ * records (INTEGRATION.md shows the three calls).  *report may be NULL.
+ * It never cuts from part of the hits: a list that came back shorter than the hits is DX_E_NOMEM.  A selection without a unit (every
+ * record dropped, or no record) is DX_E_DEGENERATE, as for dx_file_subset, and hands nothing back.  DX_E_ARG for DX_KIND_QUIVA (a
+ * .dexqv has no reads to search: cut its .dexta, then apply the selection), an unknown mode, and what dx_file_find_edit refuses.  */
+int dx_file_cut(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
+                const char *const *pattern, uint32_t npat, uint32_t max_err, int both_strands,
+                uint32_t min_len, int mode, uint8_t **out, size_t *out_len, dx_cut *report /* may be NULL */,
+                uint64_t **ids /* may be NULL */, uint32_t **beg /* may be NULL */, uint32_t **end /* may be NULL */, uint64_t *n_ids /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
