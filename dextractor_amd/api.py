@@ -795,6 +795,92 @@ class Context:
             for p in [out] + sel:
                 self.lib.dx_file_free(p)
 
+    # ---- k-mers ------------------------------------------------------------------------------------
+    def code_kmers(self, d_in, boff, beg, length, k, canonical=False, table=None, in_bytes=None, n=None):
+        """dx_code_kmers: unit j = symbols [beg[j], beg[j] + length[j]) of the packed read at d_in + boff[j] (beg None: whole reads
+        from symbol 0); every window of k symbols (1 to 14) adds one to cell `code` of the table, the first symbol on top of the
+        code, with canonical to cell min(code, rc).  The arguments are device arrays: torch tensors (uint8; int64 / uint64; int32 /
+        uint32) or DevBufs; in_bytes and n default to what d_in and length hold.  table: 4^k 64-bit counters that are ADDED to; None
+        makes a zeroed torch int64 tensor on the context's device (a process that uses torch starts it before it opens a Context,
+        torch.cuda.init(), as tools/ do).  Returns (table, windows of this call).  Raises DexGPUError
+        (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie inside the in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        k = int(k)
+        if table is None and 1 <= k <= 14:
+            import torch                                          # (only here: who brings a table of their own needs none)
+            table = torch.zeros(4 ** k, dtype=torch.int64, device=f"cuda:{self.device}")
+            torch.cuda.synchronize(self.device)                   # (zeroed on torch's stream, counted into on the context's)
+        win, bad = C.c_uint64(), C.c_uint64()
+        rc = self.lib.dx_code_kmers(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _dev(boff)[0], _dev(beg)[0], p_len,
+                                    int(b_len // 4 if n is None else n), k, int(bool(canonical)), _dev(table)[0], C.byref(win),
+                                    C.byref(bad))
+        if rc != 0:
+            raise self._bad_unit(rc, bad)
+        return table, win.value
+
+    def kmer_spectrum(self, table, k, nspec=256) -> dict:
+        """dx_kmer_spectrum of a device table of 4^k counters: {"spectrum": uint64[nspec] -- [c] the codes counted c times, the last
+        bin everything from nspec - 1 on, [0] always 0 --, "distinct", "max_count", "max_code": the smallest code with the largest
+        count}; nspec None or 0: no spectrum."""
+        spec = np.zeros(int(nspec), np.uint64) if nspec else None
+        d, m, mc = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._chk(self.lib.dx_kmer_spectrum(self.h, _dev(table)[0], int(k), spec.ctypes.data if spec is not None else None,
+                                            int(nspec or 0), C.byref(d), C.byref(m), C.byref(mc)))
+        return {"spectrum": spec, "distinct": d.value, "max_count": m.value, "max_code": mc.value}
+
+    def kmer_list(self, table, k, min_count, cap):
+        """dx_kmer_list of a device table: (found: the codes counted min_count times at least, the first min(cap, found) of them in
+        ascending code order as a KMER_DTYPE array)."""
+        cap, found = int(cap), C.c_uint64()
+        d_out = self.alloc(16 * cap + 16) if cap else None
+        try:
+            self._chk(self.lib.dx_kmer_list(self.h, _dev(table)[0], int(k), int(min_count), d_out.ptr if d_out else None, cap,
+                                            C.byref(found)))
+            got = min(cap, found.value)
+            lst = d_out.download(np.uint8, 16 * got).view(KMER_DTYPE) if got else np.zeros(0, KMER_DTYPE)
+        finally:
+            if d_out:
+                d_out.free()
+        return found.value, lst
+
+    def kmers_add(self, kind, img: bytes, k, canonical, table) -> dict:
+        """dx_file_kmers_add: the k-mers of the reads of the image ("fasta" or "arrow") added to the device table of 4^k counters,
+        so that several files are counted into one.  {"records", "symbols", "windows"} of this image."""
+        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        r, s, w = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.dx_file_kmers_add(self.h, kd, img, len(img), int(k), int(bool(canonical)), _dev(table)[0], C.byref(r),
+                                             C.byref(s), C.byref(w)))
+        return {"records": r.value, "symbols": s.value, "windows": w.value}
+
+    def kmers(self, kind, img: bytes, k, canonical=False, nspec=256, min_count=0, max_list=0, table=False):
+        """dx_file_kmers: the exact counts of all k-mers (1 <= k <= 14) of the reads of the image ("fasta" or "arrow"), counted on
+        the device in the packed reads (no text is made); canonical ("fasta"): a window counts under min(code, reverse complement).
+        Returns (report, spectrum, list) and with table=True the 4^k counters behind them (uint64).  report: {"records", "symbols",
+        "windows", "distinct", "max_count", "max_code", "k", "listed"}; spectrum: uint64[nspec] as kmer_spectrum's; list: the first
+        max_list codes counted min_count times at least (min_count 0: none), ascending, as a KMER_LIST_DTYPE array whose `letters`
+        are what Context.find takes as a pattern."""
+        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        km, lst, n, tab = L.Kmers(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+        spec = np.zeros(int(nspec), np.uint64)
+        self._chk(self.lib.dx_file_kmers(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), int(max_list),
+                                         C.byref(km), spec.ctypes.data, int(nspec), C.byref(lst), C.byref(n),
+                                         C.byref(tab) if table else None))
+        try:
+            rep = {f: getattr(km, f) for f, _ in L.Kmers._fields_}
+            rep["listed"] = n.value
+            out = np.zeros(n.value, KMER_LIST_DTYPE)
+            if n.value:
+                raw = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * n.value,)).view(KMER_DTYPE)
+                out["count"], out["code"] = raw["count"], raw["code"]
+                out["letters"] = [kmer_letters(int(c), int(k), arrow=kind == "arrow") for c in raw["code"]]
+            res = (rep, spec, out)
+            if table:
+                res += (np.ctypeslib.as_array(C.cast(tab, C.POINTER(C.c_uint64)), (4 ** int(k),)).copy(),)
+            return res
+        finally:
+            self.lib.dx_file_free(lst); self.lib.dx_file_free(tab)
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -1018,6 +1104,40 @@ def pack2_sharded(contexts, text: bytes, arrow=False) -> bytes:
 
 # ---- host-only helpers (no GPU needed) ---------------------------------------------------------
 HIT_DTYPE = np.dtype([("record", "<u8"), ("pos", "<u4"), ("query", "<u2"), ("strand", "u1"), ("mis", "u1")])      # dx_hit
+
+
+KMER_DTYPE = np.dtype([("count", "<u8"), ("code", "<u4"), ("reserved", "<u4")])                                   # dx_kmer
+KMER_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u4"), ("letters", "S14")])                              # Context.kmers' list
+
+
+def _dev(x):
+    """a device array -> (its address, its bytes): a DevBuf, a DevView (bytes unknown: None), a torch tensor, or None"""
+    if x is None:
+        return None, 0
+    if hasattr(x, "data_ptr"):
+        return x.data_ptr(), x.numel() * x.element_size()
+    return x.ptr, getattr(x, "nbytes", None)
+
+
+def kmer_code(letters, arrow=False, canonical=False) -> int:
+    """dx_kmer_code: 1 to 14 letters (acgtACGT, or 1234 with arrow) -> the k-mer's code, the first letter on top; canonical:
+    min(code, reverse complement's).  Host only."""
+    s = letters.encode() if isinstance(letters, str) else bytes(letters)
+    code = C.c_uint32()
+    rc = L.load().dx_kmer_code(int(bool(arrow)), s, len(s), int(bool(canonical)), C.byref(code))
+    if rc != 0:
+        raise L.DexGPUError(rc, f"dx_kmer_code: {letters!r} is not 1 to 14 letters of the kind's")
+    return code.value
+
+
+def kmer_letters(code, k, arrow=False) -> bytes:
+    """dx_kmer_letters: a code of k symbols -> its letters, upper case or 1234.  Host only."""
+    out = C.create_string_buffer(16)
+    code, k = int(code), int(k)
+    rc = L.load().dx_kmer_letters(int(bool(arrow)), code, k, out) if 0 <= code < 2**32 and 0 <= k < 2**32 else -1
+    if rc != 0:
+        raise L.DexGPUError(rc, f"dx_kmer_letters: code {code} is not one of {k} symbols, or k is not 1 to 14")
+    return out.value
 
 
 def equery(*x):

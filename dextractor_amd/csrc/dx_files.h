@@ -13,6 +13,7 @@
  *     dx_file_compare.c how two images of the same records differ: dx_file_compare
  *     dx_file_find.c   where given sequences occur in an image's reads: dx_file_find
  *     dx_file_find_edit.c  ... within an edit distance: dx_file_find_edit, dx_file_find_edit_spans
+ *     dx_file_kmers.c  the k-mers of an image's reads, counted: dx_file_kmers_add, dx_file_kmers; dx_kmer_code, dx_kmer_letters (host)
  *     dx_file_cut.c    what is kept of the records once the occurrences are cut out, and the image of it: dx_hits_cut_plan (host), dx_file_cut
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.

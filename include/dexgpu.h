@@ -993,6 +993,72 @@ int dx_file_cut(dx_ctx *ctx, int kind, const uint8_t *img, size_t m,
                 uint64_t **ids /* may be NULL */, uint32_t **beg /* may be NULL */, uint32_t **end /* may be NULL */, uint64_t *n_ids /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ *  k-mers: what is in the reads that nobody thought to ask for  (undexta -U of the whole file and a counting loop on one core today)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { uint64_t count; uint32_t code, reserved; } dx_kmer;          /* 16 bytes */
+typedef struct { uint64_t records, symbols, windows, distinct, max_count; uint32_t max_code, k; } dx_kmers;   /* 48 bytes */
+
+/* Exact counts of all k-mers, 1 <= k <= 14, of n packed reads in a direct-addressed table of 4^k 64-bit counters on the device
+ * (csrc/kmers/dx_kmers.hip; 2 GiB at k = 14).  The code of a k-mer is its symbols as a base-4 number, the first on top:
+ * code = sum s_i 4^(k - 1 - i), the order of a packed read and of dx_query.code.  With canonical a window counts under
+ * min(code, rc(code)), rc being the codes 3 - c in reverse order; a k-mer that is its own reverse complement counts once a window.
+ * Unit j is what it is for dx_code_counts and dx_code_find: symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at
+ * d_in + d_boff[j], any byte offset, any phase; units may overlap or repeat, and their windows add.  A window never spans two units,
+ * a unit shorter than k has none; the symbols in front of d_beg[j], those behind the unit's end, the pad bits of a read's last byte
+ * and every byte that is not the unit's are part of no window, and nothing outside [0, in_bytes) is read.
+ * d_table is ADDED to: the caller zeroes it, and two calls over disjoint halves of the units leave what one call over all of them
+ * leaves.  *windows (may be NULL) = sum max(0, d_len[j] - k + 1) over this call's good units.
+ * DX_E_FORMAT with *bad_unit = the smallest j that does not lie inside the in_bytes (UINT64_MAX otherwise; may be NULL); such units
+ * add nothing; checked by the kernel, one read-back a call.  DX_E_ARG for k outside 1..14, a NULL pointer that is needed,
+ * n >= 2^31.  n == 0 changes nothing.  (canonical is a property of the codes here; dx_file_kmers refuses it for arrow.)          */
+int dx_code_kmers(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                  const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                  uint32_t k /* 1..14 */, int canonical,
+                  uint64_t *d_table /* 4^k counters, ADDED to */, uint64_t *windows /* host, may be NULL: this call's */,
+                  uint64_t *bad_unit /* may be NULL */);
+
+/* What a table of 4^k counters holds.  spectrum[c] (host, nspec >= 2 values; may be NULL), 1 <= c < nspec - 1, = the codes whose
+ * counter is c; spectrum[nspec - 1] gathers every counter >= nspec - 1; spectrum[0] is 0 always (the unseen codes are
+ * 4^k - *distinct, and in canonical mode half the cells are never used).  *distinct = the counters >= 1, *max_count the largest,
+ * *max_code the smallest code that has it (both 0 for an empty table); each may be NULL.  One read-back a call.                  */
+int dx_kmer_spectrum(dx_ctx *ctx, const uint64_t *d_table, uint32_t k,
+                     uint64_t *spectrum /* host, nspec; may be NULL */, uint32_t nspec,
+                     uint64_t *distinct, uint64_t *max_count, uint32_t *max_code);
+
+/* The codes whose counter is >= min_count (>= 1), in ascending code order, the same on every call: places come from counts and a
+ * prefix sum, no atomic cursor.  *found counts all of them, listed or not; d_out gets the first min(cap, *found), and nothing is
+ * written at cap or beyond; cap == 0 counts only.                                                                               */
+int dx_kmer_list(dx_ctx *ctx, const uint64_t *d_table, uint32_t k, uint64_t min_count /* >= 1 */,
+                 dx_kmer *d_out /* cap; may be NULL when cap == 0 */, uint64_t cap, uint64_t *found);
+
+/* The k-mers of the reads of a .dexta / .dexar image (kind DX_KIND_FASTA or DX_KIND_ARROW; any key, legacy layout or byte order, as
+ * dx_file_unpack2 takes them) added to the caller's table, so that several files can be counted into one.  The count is over what
+ * the archive HOLDS (an N that dexta stored as a is an a): exactly the k-mers of the letters undexta -U / undexar prints, record by
+ * record; a window never spans two records.  The image is walked on the host and uploaded, and the reads are counted where they lie
+ * (dx_code_kmers); an image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET (bytes of image), goes in slices of whole
+ * records.  *records, *symbols, *windows (each may be NULL) = this image's.  canonical: fasta only.  The refusals are
+ * dx_file_kmers'; an image that is refused has added nothing.                                                                   */
+int dx_file_kmers_add(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical,
+                      uint64_t *d_table, uint64_t *records, uint64_t *symbols, uint64_t *windows);
+
+/* ... with a table of its own, zeroed, and then the spectrum and the list of it: *out = the image's records, symbols and windows,
+ * the table's distinct, max_count and max_code, and k.  With min_count >= 1 and list != NULL, *list (malloc'd, dx_file_free) has
+ * *listed = min(found, max_list) entries in ascending code order (reserved = 0); with min_count == 0 or list == NULL there is no
+ * list.  *table (may be NULL; malloc'd, dx_file_free) = the 4^k counters.
+ * DX_E_ARG (dx_last_error says why) for DX_KIND_QUIVA, an unknown kind, canonical with arrow, k outside 1..14, nspec < 2 with a
+ * spectrum; else dx_file_unpack2's errors for the image, and *out is untouched.                                                  */
+int dx_file_kmers(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical,
+                  uint64_t min_count, uint64_t max_list, dx_kmers *out,
+                  uint64_t *spectrum /* host, nspec; may be NULL */, uint32_t nspec,
+                  dx_kmer **list /* may be NULL */, uint64_t *listed, uint64_t **table /* may be NULL: 4^k, malloc'd */);
+
+/* Host only, no GPU: k letters (acgtACGT, or 1234 with arrow) -> their code, with canonical min(code, rc); and a code -> its k
+ * letters, upper case or 1234, and a NUL (out: k + 1 bytes).  DX_E_ARG for k outside 1..14, a letter that is not the kind's (the
+ * text's end among them), a code of more than 2 k bits, a NULL pointer.                                                          */
+int dx_kmer_code(int arrow, const char *letters, uint32_t k, int canonical, uint32_t *code);
+int dx_kmer_letters(int arrow, uint32_t code, uint32_t k, char *out /* k + 1 */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
