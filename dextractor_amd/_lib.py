@@ -110,6 +110,13 @@ class Kmers(C.Structure):                        # dx_kmers
     _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("distinct", C.c_uint64),
                 ("max_count", C.c_uint64), ("max_code", C.c_uint32), ("k", C.c_uint32)]
 
+class Kmer64(C.Structure):                       # dx_kmer64
+    _fields_ = [("code", C.c_uint64), ("count", C.c_uint64)]
+
+class Kmers64(C.Structure):                      # dx_kmers64
+    _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("distinct", C.c_uint64),
+                ("max_count", C.c_uint64), ("max_code", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 DX_CUT_SPLIT, DX_CUT_LONGEST, DX_CUT_DROP = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
@@ -259,6 +266,15 @@ SIGNATURES = {
                                 C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
     "dx_kmer_code": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
     "dx_kmer_letters": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p]),
+    "dx_sort_u64": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32]),
+    "dx_code_kmer_codes": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, _P, C.c_uint64,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_kmer_runs": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_uint32,
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_file_kmers_wide": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(Kmers64), _P,
+                                     C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "dx_kmer_code64": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
+    "dx_kmer_letters64": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_char_p]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

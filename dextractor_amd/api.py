@@ -881,6 +881,89 @@ class Context:
         finally:
             self.lib.dx_file_free(lst); self.lib.dx_file_free(tab)
 
+    # ---- k-mers up to k = 32: codes written out, sorted, counted off the runs ---------------------------
+    def sort_u64(self, keys, bits, tmp=None, n=None):
+        """dx_sort_u64: the n 64-bit keys of the device array `keys` (a torch tensor or a DevBuf; n defaults to what it holds) sorted
+        ascending in place, every key < 2^bits; tmp: n keys of room (None: made and freed here).  Returns keys."""
+        p, b = _dev(keys)
+        n = int(b // 8 if n is None else n)
+        own = self.alloc(8 * n + 8) if tmp is None and n else None
+        try:
+            self._chk(self.lib.dx_sort_u64(self.h, p, own.ptr if own else _dev(tmp)[0], n, int(bits)))
+        finally:
+            if own:
+                own.free()
+        return keys
+
+    def code_kmer_codes(self, d_in, boff, beg, length, k, canonical=False, cap=None, codes=None, in_bytes=None, n=None):
+        """dx_code_kmer_codes: unit j = symbols [beg[j], beg[j] + length[j]) of the packed read at d_in + boff[j] (beg None: whole
+        reads from symbol 0); window p of unit j -> codes[off[j] + p], off the exclusive sums of max(0, length[j] - k + 1); the code
+        is the window's symbols as a base-4 number (k 1 to 32), with canonical min(code, rc).  The arguments are device arrays as
+        code_kmers takes them.  codes: a device array of cap 64-bit words; None: a DevBuf of cap words made here (cap None: every
+        unit's windows, from a host copy of `length`), the caller's to free.  Returns (codes, windows).  Raises
+        DexGPUError: DX_E_NOMEM (.windows = what is needed) when cap is short, DX_E_FORMAT (.bad_unit) for a unit outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        k, n = int(k), int(b_len // 4 if n is None else n)
+        own = None
+        if codes is None:
+            if cap is None:
+                ln = (length.cpu().numpy()[:n] if hasattr(length, "cpu") else length.download(np.uint32, n)).astype(np.int64)
+                cap = int(np.maximum(ln - k + 1, 0).sum())
+            codes = own = self.alloc(8 * int(cap) + 8)
+        elif cap is None:
+            cap = _dev(codes)[1] // 8
+        win, bad = C.c_uint64(), C.c_uint64()
+        rc = self.lib.dx_code_kmer_codes(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _dev(boff)[0], _dev(beg)[0], p_len,
+                                         n, k, int(bool(canonical)), _dev(codes)[0], int(cap), C.byref(win), C.byref(bad))
+        if rc != 0:
+            if own:
+                own.free()
+            e = self._bad_unit(rc, bad)
+            e.windows = win.value
+            raise e
+        return codes, win.value
+
+    def kmer_runs(self, sorted_codes, n, min_count, cap, nspec=256):
+        """dx_kmer_runs of a sorted device array of n codes: (found: the runs of min_count keys at least, the first min(cap, found)
+        of them in ascending code order as a KMER64_DTYPE array, {"spectrum": uint64[nspec] -- [c] the runs of length c, the last bin
+        everything from nspec - 1 on --, "distinct", "max_count", "max_code"}); nspec None or 0: no spectrum."""
+        cap, found = int(cap), C.c_uint64()
+        spec = np.zeros(int(nspec), np.uint64) if nspec else None
+        d, m, mc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        d_out = self.alloc(16 * cap + 16) if cap else None
+        try:
+            self._chk(self.lib.dx_kmer_runs(self.h, _dev(sorted_codes)[0], int(n), int(min_count), d_out.ptr if d_out else None, cap,
+                                            C.byref(found), spec.ctypes.data if spec is not None else None, int(nspec or 0),
+                                            C.byref(d), C.byref(m), C.byref(mc)))
+            got = min(cap, found.value)
+            lst = d_out.download(np.uint8, 16 * got).view(KMER64_DTYPE) if got else np.zeros(0, KMER64_DTYPE)
+        finally:
+            if d_out:
+                d_out.free()
+        return found.value, lst, {"spectrum": spec, "distinct": d.value, "max_count": m.value, "max_code": mc.value}
+
+    def kmers_wide(self, kind, img: bytes, k, canonical=False, nspec=256, min_count=0, max_list=0):
+        """dx_file_kmers_wide: Context.kmers for 1 <= k <= 32, by sorting -- every window's code written out on the device, sorted,
+        the counts read off the runs; 16 bytes of device memory a window.  Returns (report, spectrum, list) as kmers does, the
+        report with the same keys; the list is a KMER64_LIST_DTYPE array (64-bit codes, `letters` 32 bytes wide)."""
+        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        km, lst, n = L.Kmers64(), C.c_void_p(), C.c_uint64()
+        spec = np.zeros(int(nspec), np.uint64)
+        self._chk(self.lib.dx_file_kmers_wide(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), int(max_list),
+                                              C.byref(km), spec.ctypes.data, int(nspec), C.byref(lst), C.byref(n)))
+        try:
+            rep = {f: getattr(km, f) for f, _ in L.Kmers._fields_}
+            rep["listed"] = n.value
+            out = np.zeros(n.value, KMER64_LIST_DTYPE)
+            if n.value:
+                raw = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * n.value,)).view(KMER64_DTYPE)
+                out["count"], out["code"] = raw["count"], raw["code"]
+                out["letters"] = [kmer_letters64(int(c), int(k), arrow=kind == "arrow") for c in raw["code"]]
+            return rep, spec, out
+        finally:
+            self.lib.dx_file_free(lst)
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -1110,6 +1193,10 @@ KMER_DTYPE = np.dtype([("count", "<u8"), ("code", "<u4"), ("reserved", "<u4")]) 
 KMER_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u4"), ("letters", "S14")])                              # Context.kmers' list
 
 
+KMER64_DTYPE = np.dtype([("code", "<u8"), ("count", "<u8")])                                                      # dx_kmer64
+KMER64_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u8"), ("letters", "S32")])                            # Context.kmers_wide's list
+
+
 def _dev(x):
     """a device array -> (its address, its bytes): a DevBuf, a DevView (bytes unknown: None), a torch tensor, or None"""
     if x is None:
@@ -1137,6 +1224,27 @@ def kmer_letters(code, k, arrow=False) -> bytes:
     rc = L.load().dx_kmer_letters(int(bool(arrow)), code, k, out) if 0 <= code < 2**32 and 0 <= k < 2**32 else -1
     if rc != 0:
         raise L.DexGPUError(rc, f"dx_kmer_letters: code {code} is not one of {k} symbols, or k is not 1 to 14")
+    return out.value
+
+
+def kmer_code64(letters, arrow=False, canonical=False) -> int:
+    """dx_kmer_code64: 1 to 32 letters (acgtACGT, or 1234 with arrow) -> the k-mer's 64-bit code, the first letter on top; canonical:
+    min(code, reverse complement's).  Host only."""
+    s = letters.encode() if isinstance(letters, str) else bytes(letters)
+    code = C.c_uint64()
+    rc = L.load().dx_kmer_code64(int(bool(arrow)), s, len(s), int(bool(canonical)), C.byref(code))
+    if rc != 0:
+        raise L.DexGPUError(rc, f"dx_kmer_code64: {letters!r} is not 1 to 32 letters of the kind's")
+    return code.value
+
+
+def kmer_letters64(code, k, arrow=False) -> bytes:
+    """dx_kmer_letters64: a code of k symbols (1 to 32) -> its letters, upper case or 1234.  Host only."""
+    out = C.create_string_buffer(40)
+    code, k = int(code), int(k)
+    rc = L.load().dx_kmer_letters64(int(bool(arrow)), code, k, out) if 0 <= code < 2**64 and 0 <= k < 2**32 else -1
+    if rc != 0:
+        raise L.DexGPUError(rc, f"dx_kmer_letters64: code {code} is not one of {k} symbols, or k is not 1 to 32")
     return out.value
 
 

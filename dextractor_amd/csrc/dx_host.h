@@ -43,6 +43,8 @@ __attribute__((visibility("hidden"))) int dx_find_edit_fail(dx_ctx *ctx, int cod
 __attribute__((visibility("hidden"))) int dx_cut_fail(dx_ctx *ctx, int code, const char *what);
 /* ... and "dx_file_kmers: <what>", defined in kmers/dx_kmers.hip, for dx_file_kmers.c */
 __attribute__((visibility("hidden"))) int dx_kmers_fail(dx_ctx *ctx, int code, const char *what);
+/* ... and "dx_file_kmers_wide: <what>", defined in kmers/dx_kmer_runs.hip, for dx_file_kmers_wide.c */
+__attribute__((visibility("hidden"))) int dx_kmers_wide_fail(dx_ctx *ctx, int code, const char *what);
 
 /* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
    arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their

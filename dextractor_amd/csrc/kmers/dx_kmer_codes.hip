@@ -1,0 +1,225 @@
+// dx_kmer_codes.hip -- the k-mers of packed reads written out, 1 <= k <= 32: every window's code as a 64-bit word, at a fixed place.
+//
+//   dx_code_kmer_codes   per unit of a .bps / .arw / .dexta / .dexar payload: window p of unit j -> codes[off[j] + p]   (k_kc_windows, k_kc_codes)
+//
+// The first step of the wide route: beyond k = 14 a table of 4^k cells is out of the question and a hashed one would put
+// every window on the path of the global atomic requests, which dx_kmers.hip measured as the slow one.  Here a window costs one plain
+// store; dx_sort_u64 (sort/dx_sort.hip) and dx_kmer_runs (dx_kmer_runs.hip) make counts of the codes.
+//
+// A unit is what it is for dx_code_kmers: symbols [beg, beg + len) of the packed read at in + boff, any byte offset, any phase.  A
+// window's code is its symbols as a base-4 number, the first on top, in the low 2 k bits of the word -- the top 2 k bits of the 64 bits
+// that dx_find.hip holds for a position, moved down.  With `canonical` it is min(code, rc), compared unsigned (at k = 32 the top bit is
+// in use).  Places: off = the exclusive sums of w_j = max(0, len_j - k + 1), a unit that does not lie inside the buffer counting 0:
+// k_kc_windows leaves the w_j, dx_scan_u32 the sums and the total, which the host holds against cap before anything is written.
+//
+// The walk is k_find's and k_kmers': tickets (k_ticket_units), 64 units a round, a lane reading one unit's parameters and checking its
+// bounds; a unit of up to KC_LANE chunks (16 packed bytes = 64 positions on 16-byte boundaries of the buffer) is its lane's, one of up
+// to 16 goes four a step by 16 lanes each, the others by the whole wave.  A lane holds its chunk and the 8 bytes behind it (a window of
+// up to 32 symbols that begins in the chunk ends there at the latest) as three 64-bit words in the read's bit order, moved up to the
+// first position that is the unit's and at which a window begins (kc_take, as fd_take); a position's code is one shift of the upper
+// word, and the words move up two bits a position.  The reverse strand rolls along in a second 64-bit register, as in k_kmers:
+// rc(p + 1) = rc(p) >> 2 | (3 - s) << (2 k - 2) with s the symbol that entered; the first form (bit reversal, kc_rc) starts it, once a
+// chunk.  Nothing outside [0, in_bytes) is read (last16_ask, units_begin's pad).
+//
+// Cost a window, counted from the source: the code 2 (v_lshrrev_b64), the words' move 3 shifts of 64 bits and 2 v_alignbit-like
+// funnel shifts (about 8), canonical + 6 (v_lshrrev_b64, v_not / v_and, v_lshlrev_b64, 2 v_or, v_cmp + 2 v_cndmask), the store's address
+// 2 and the global_store_dwordx2: about 15 to 20 vector instructions -- 10^9 windows in 0.5 ms on 39 T lane-instructions/s.  Bytes: 8
+// written a window, 0.25 read.  A lane writes its up to 64 windows one behind the other, 512 bytes, so a store instruction of the wave
+// touches 64 different 128-byte lines and a line is filled by 16 instructions of one lane; the lines are completed in the L2 before
+// they leave.  ESTIMATE: the 8 GB of 10^9 windows at half the rate of a copy's writes, about 4 to 5 ms.  MEASURED
+// (profiles/kmer_wide_rate.txt, 10^5 reads x 10 kb, the two small launches, the prefix sum and its read-back included): 4.65 ms
+// at k = 14, 16, 21 and 32 alike, 1.7 TB/s of codes written, 1.4 times a device-to-device copy of the same 8 GB (3.3 ms, which
+// moves 16 GB): bound by the stores, not by the walk (dx_code_counts reads the same units in 0.34 ms).  Stores of whole lines -- the
+// wave's 64 x 64 codes turned in LDS -- are what would lift it; not built.
+//
+// This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in the
+// profiler's name table and are timed with events on the context's stream (tools/kmer_wide_rate.py).
+#include "units/dx_units.hpp"
+
+#define KC_KMAX    32u
+#define KC_BATCH   1u                      // units a ticket at least
+#define KC_TARGET  (16u << 10)             // packed bytes a ticket
+#define KC_CHUNK   64u                     // positions a chunk (16 packed bytes)
+#define KC_LANE    4u                      // chunks: a unit of up to so many is its lane's
+#define KC_GROUP   UNITS_GROUP             // chunks: up to here 16 lanes take the unit, beyond the wave
+#define KC_EVEN64  0x5555555555555555ull
+
+int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
+
+// ---------------------------------------------------------------------------------------------
+//  k_kc_windows
+// ---------------------------------------------------------------------------------------------
+// w[j] = the windows of unit j: max(0, len - k + 1), 0 for a unit that does not lie inside `bound` bytes (k_kc_codes reports those)
+__global__ __launch_bounds__(DX_BLOCK)
+void k_kc_windows(const uint64_t *__restrict__ boff, const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n,
+                  uint64_t bound, uint32_t k, uint32_t *__restrict__ w)
+{ const uint64_t j = (uint64_t) blockIdx.x * DX_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t l = len[j];
+  w[j] = packed_unit_ok(boff[j], beg != NULL ? beg[j] : 0u, l, bound) && l >= k ? l - k + 1u : 0u;
+}
+
+// ---------------------------------------------------------------------------------------------
+//  k_kc_codes
+// ---------------------------------------------------------------------------------------------
+// the 8 bytes at byte o of the buffer as a word in the read's bit order (the first symbol on top); what lies behind the buffer's
+// end reads as zero, and the 8 bytes that would reach past it are its last 8, moved up (bytes >= 16)
+__device__ __forceinline__ uint64_t kc_be64(const uint8_t *in, uint64_t bytes, uint64_t o)
+{ if (o + 8u <= bytes) return __builtin_bswap64(*(const u64_u *) (in + o));
+  if (o >= bytes) return 0ull;
+  return __builtin_bswap64(*(const u64_u *) (in + (bytes - 8u))) << (8u * (uint32_t) (o + 8u - bytes));
+}
+
+// What a lane has of a unit in one chunk: n windows begin in it, the first at symbol `first` of the unit, and the three words are the
+// buffer from that window's first symbol on
+struct kc_part { uint64_t w0, w1, w2; uint32_t n, first; };
+
+// the chunk at byte a < bytes of the buffer against the unit that is symbols [S0, S1) of the buffer; n == 0: no window begins here
+__device__ __forceinline__ kc_part kc_take(const uint8_t *in, uint64_t bytes, uint64_t a, uint64_t S0, uint64_t S1, uint32_t k)
+{ kc_part p = { 0ull, 0ull, 0ull, 0u, 0u };
+  const uint64_t p0 = S0 > 4u * a ? S0 : 4u * a, p1 = S1 < 4u * a + KC_CHUNK ? S1 : 4u * a + KC_CHUNK;
+  if (p1 <= p0 || S1 - p0 < k) return p;
+  const uint32_t most = (uint32_t) (S1 - p0) - k + 1u;                        // windows from p0 on (a unit has fewer than 2^31 symbols)
+  p.n = most < (uint32_t) (p1 - p0) ? most : (uint32_t) (p1 - p0);
+  p.first = (uint32_t) (p0 - S0);
+  const u32x4    v    = last16_ask(in, bytes, a);
+  const uint32_t back = (uint32_t) (a - last16_from(a, bytes));              // 0, or how many bytes in front of a the 16 begin
+  const uint64_t h = __builtin_bswap64(v.x | ((uint64_t) v.y << 32)), l = __builtin_bswap64(v.z | ((uint64_t) v.w << 32));
+  uint64_t w0, w1, w2;
+  if (back == 0u)      { w0 = h; w1 = l; w2 = kc_be64(in, bytes, a + 16u); }
+  else if (back < 8u)  { w0 = (h << (8u * back)) | (l >> (64u - 8u * back)); w1 = l << (8u * back); w2 = 0ull; }
+  else                 { w0 = l << (8u * (back - 8u)); w1 = 0ull; w2 = 0ull; }
+  uint32_t s = (uint32_t) (p0 - 4u * a);                                       // the words move up to position p0
+  if (s >= 32u) { w0 = w1; w1 = w2; w2 = 0ull; s -= 32u; }
+  if (s)
+    { w0 = (w0 << (2u * s)) | (w1 >> (64u - 2u * s));
+      w1 = (w1 << (2u * s)) | (w2 >> (64u - 2u * s));
+      w2 <<= 2u * s;
+    }
+  p.w0 = w0; p.w1 = w1; p.w2 = w2;
+  return p;
+}
+
+// the reverse complement's code of the window that stands in the top 2 k bits of w: the bits reversed put symbol i at bits
+// 2 i + 1, 2 i with its two bits exchanged; they are exchanged back, complemented, and what stood below the window is masked off
+__device__ __forceinline__ uint64_t kc_rc(uint64_t w, uint32_t k)
+{ const uint64_t y = __builtin_bitreverse64(w);
+  return ~(((y >> 1) & KC_EVEN64) | ((y & KC_EVEN64) << 1)) & (k < 32u ? (1ull << (2u * k)) - 1u : ~0ull);
+}
+
+// the part's codes, one behind the other from out[0] on
+template <bool CANON>
+__device__ __forceinline__ void kc_write(const kc_part &p, uint32_t k, uint64_t *out)
+{ if (p.n == 0u) return;
+  uint64_t w0 = p.w0, w1 = p.w1, w2 = p.w2;
+  const uint32_t down = 64u - 2u * k, top = 2u * k - 2u;
+  uint64_t rcw = CANON ? kc_rc(w0, k) << 2 : 0ull;         // (the first step moves it down again and sets the top symbol it has already)
+  for (uint32_t i = 0; i < p.n; i++)
+    { uint64_t cur = w0 >> down;
+      if (CANON)
+        { rcw = (rcw >> 2) | ((~cur & 3ull) << top);
+          cur = cur < rcw ? cur : rcw;
+        }
+      out[i] = cur;
+      w0 = (w0 << 2) | (w1 >> 62); w1 = (w1 << 2) | (w2 >> 62); w2 <<= 2;
+    }
+}
+
+// in holds in_bytes bytes and 16 at least; the units are checked against `bound` (as in k_code_counts).  off: the exclusive sums of
+// k_kc_windows' counts; codes holds off[n] words at least.
+template <bool CANON>
+__global__ __launch_bounds__(DX_BLOCK)
+void k_kc_codes(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, const uint64_t *__restrict__ boff,
+                const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n, uint32_t k,
+                const uint64_t *__restrict__ off, uint64_t *__restrict__ codes, unsigned long long *__restrict__ bad,
+                uint32_t *__restrict__ ticket)
+{ const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP;
+  units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
+    { // unit u0 + lane is this lane's to read and to check
+      const uint64_t    i  = u0 + lane;
+      const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
+      uint64_t S0 = 0, S1 = 0, a0 = 0, to = 0;             // its symbols in the buffer; its first chunk's place; its first window's place
+      uint32_t nch = 0;                                    // its chunks
+      if (pu.ok && pu.len >= k)
+        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
+          a0 = (S0 >> 2) & ~15ull;
+          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
+          to = off[i];
+        }
+
+      // up to KC_LANE chunks: the lane's own, chunk after chunk
+      if (nch && nch <= KC_LANE)
+        for (uint32_t j = 0; j < nch; j++)
+          { const kc_part p = kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k);
+            kc_write<CANON>(p, k, codes + to + p.first);
+          }
+
+      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
+      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
+        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gto = __shfl(to, from);
+          const uint32_t gn  = __shfl(nch, from);
+          if (mine && sub < gn)
+            { const kc_part p = kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
+              kc_write<CANON>(p, k, codes + gto + p.first);
+            }
+        });
+
+      // the others: the whole wave, 64 chunks a step
+      units_each(__ballot(nch > KC_GROUP), [&](int from)
+        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
+          const uint64_t wto = uniform64(__shfl(to, from));
+          const uint32_t wn  = uniform(__shfl(nch, from));
+          for (uint32_t base = 0; base < wn; base += 64u)
+            { const uint32_t j = base + lane;
+              if (j < wn)
+                { const kc_part p = kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
+                  kc_write<CANON>(p, k, codes + wto + p.first);
+                }
+            }
+        });
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
+//  the entry point
+// ---------------------------------------------------------------------------------------------
+extern "C" int dx_code_kmer_codes(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                                  const uint64_t *d_boff, const uint32_t *d_beg, const uint32_t *d_len, uint64_t n,
+                                  uint32_t k, int canonical, uint64_t *d_codes, uint64_t cap, uint64_t *windows, uint64_t *bad_unit)
+{ if (ctx == NULL) return DX_E_ARG;
+  if (bad_unit) *bad_unit = UINT64_MAX;
+  if (windows) *windows = 0;
+  if (k < 1u || k > KC_KMAX) return dx_fail(ctx, DX_E_ARG, "dx_code_kmer_codes: k = %u (1 to %u)", k, KC_KMAX);
+  if (windows == NULL || (d_codes == NULL && cap)) return dx_fail(ctx, DX_E_ARG, "dx_code_kmer_codes: NULL pointer");
+  if (n >= (1ull << 31)) return dx_fail(ctx, DX_E_ARG, "dx_code_kmer_codes: more than 2^31 - 1 units in one batch");
+  if (n == 0) return DX_OK;
+
+  // one scratch block: the frame, then every unit's first place (n + 1) and its windows (n)
+  units_frame    f;
+  uint64_t       back[UF_OUT + 1], *d_w = NULL, total = 0;
+  const uint64_t bound = in_bytes;
+  const size_t   words = UF_OUT + 1;
+  DX_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = dx_scratch(ctx, (words + n + 1u + (n + 1u) / 2u) * 8u, (void **) &d_w);
+  if (rc != DX_OK) return rc;
+  uint64_t *d_off = d_w + words;
+  uint32_t *d_win = (uint32_t *) (d_off + n + 1u);
+  rc = units_begin(ctx, "dx_code_kmer_codes", n, d_boff && d_len && (d_in || !in_bytes), d_w, 1, 16, &d_in, &in_bytes, &f);
+  if (rc != DX_OK) return rc;
+  hipLaunchKernelGGL(k_kc_windows, dim3((unsigned) ((n + DX_BLOCK - 1u) / DX_BLOCK)), dim3(DX_BLOCK), 0, ctx->stream, d_boff, d_beg, d_len, n,
+                     bound, k, d_win);
+  DX_HIP(ctx, hipGetLastError());
+  if ((rc = dx_scan_u32(ctx, d_win, n, d_off, &total)) != DX_OK) return rc;
+  *windows = total;
+  if (total > cap)
+    return dx_fail(ctx, DX_E_NOMEM, "dx_code_kmer_codes: %llu windows, and room for %llu codes", (unsigned long long) total, (unsigned long long) cap);
+
+  const int grid = dx_grid_waves(ctx, n, 16);
+  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
+                     KC_TARGET, KC_BATCH, f.ticket);
+  if (canonical) hipLaunchKernelGGL(k_kc_codes<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len, n,
+                                    k, (const uint64_t *) d_off, d_codes, f.bad, f.ticket);
+  else           hipLaunchKernelGGL(k_kc_codes<false>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len, n,
+                                    k, (const uint64_t *) d_off, d_codes, f.bad, f.ticket);
+  return units_end(ctx, f, back, bad_unit, "%s: unit %llu does not lie inside the %llu packed bytes", bound);
+}

@@ -1059,6 +1059,64 @@ int dx_kmer_code(int arrow, const char *letters, uint32_t k, int canonical, uint
 int dx_kmer_letters(int arrow, uint32_t code, uint32_t k, char *out /* k + 1 */);
 
 /* ------------------------------------------------------------------------------------------
+ *  k-mers up to k = 32: every window's code written out, sorted on the device, counted off the runs  (csrc/sort/, csrc/kmers/)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { uint64_t code, count; } dx_kmer64;                                                      /* 16 bytes */
+typedef struct { uint64_t records, symbols, windows, distinct, max_count, max_code; uint32_t k, reserved; } dx_kmers64;   /* 56 bytes */
+
+/* d_keys[0 .. n) sorted ascending as unsigned numbers, on the device: a radix sort of 8 bits a pass from the lowest digit up
+ * (csrc/sort/dx_sort.hip; no device library).  The caller promises that every key is < 2^bits (bits < 64): only the ceil(bits / 8)
+ * digits that cover `bits` are passed over.  d_tmp: n keys of room, not d_keys; its contents are lost.  The sorted keys end in d_keys
+ * whatever the number of passes.  The cost does not depend on how the keys are distributed.  n == 0 or bits == 0 does nothing.
+ * DX_E_ARG for bits > 64, a NULL pointer with n > 0, n >= 2^36.                                                                    */
+int dx_sort_u64(dx_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp /* n keys of room */, uint64_t n, uint32_t bits /* 0..64 */);
+
+/* The codes of all windows of k symbols, 1 <= k <= 32, of n packed reads, written out (csrc/kmers/dx_kmer_codes.hip).  Unit j is what
+ * it is for dx_code_kmers: symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j], any byte offset, any phase;
+ * units may overlap or repeat; pad bits and foreign symbols are part of no window, and nothing outside [0, in_bytes) is read.  A
+ * window's code is its symbols as a base-4 number, the first on top, in the low 2 k bits of the word, zeros above; with canonical it
+ * is min(code, rc(code)), compared unsigned.  Window p of unit j goes to d_codes[off[j] + p], off = the exclusive sums of
+ * w_j = max(0, d_len[j] - k + 1), a unit that does not lie inside the in_bytes counting w_j = 0: the same array on every call.
+ * *windows = sum w_j.  If that exceeds cap nothing is written and the call is DX_E_NOMEM, *windows still set.  DX_E_FORMAT with
+ * *bad_unit = the smallest j that does not lie inside the in_bytes (UINT64_MAX otherwise; may be NULL): the good units' codes are
+ * written all the same.  DX_E_ARG for k outside 1..32, a NULL pointer that is needed (d_codes may be NULL when cap == 0), n >= 2^31.   */
+int dx_code_kmer_codes(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                       const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                       uint32_t k /* 1..32 */, int canonical,
+                       uint64_t *d_codes, uint64_t cap /* keys of room */, uint64_t *windows /* host */, uint64_t *bad_unit /* may be NULL */);
+
+/* What a SORTED array of n codes holds (csrc/kmers/dx_kmer_runs.hip): a run is a maximal stretch of equal keys, its length the code's
+ * count.  The meanings are dx_kmer_spectrum's and dx_kmer_list's, read off runs instead of cells: *distinct = the runs, *max_count the
+ * longest, *max_code the smallest code that has it (both 0 for n == 0); spectrum[c] (host, nspec >= 2 values; may be NULL) = the runs
+ * of length c, the last bin everything >= nspec - 1, spectrum[0] = 0; *found = the runs of min_count (>= 1) keys at least, listed or
+ * not; d_out gets the first min(cap, *found) of them in ascending code order, nothing at cap or beyond; cap == 0 counts only.  Places
+ * come from counts and a prefix sum, no atomic cursor; a run may be longer than any tile.  distinct, max_count, max_code may be NULL.
+ * Two waits for the stream: the prefix sum's total, then one read-back of everything else.  DX_E_ARG for a NULL pointer that is
+ * needed, min_count 0, nspec < 2 with a spectrum, n >= 2^36.                                                                      */
+int dx_kmer_runs(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count /* >= 1 */,
+                 dx_kmer64 *d_out /* cap; may be NULL when cap == 0 */, uint64_t cap, uint64_t *found,
+                 uint64_t *spectrum /* host, nspec; may be NULL */, uint32_t nspec,
+                 uint64_t *distinct, uint64_t *max_count, uint64_t *max_code);
+
+/* dx_file_kmers for 1 <= k <= 32, by another route: every window's code is written into ONE array on the device (dx_code_kmer_codes,
+ * slice behind slice), the array is sorted (dx_sort_u64 with bits = 2 k) and the counts are read off the runs (dx_kmer_runs).  The
+ * meaning of every argument and of *out is dx_file_kmers': the count is over what the archive HOLDS, a window never spans two records,
+ * the list (malloc'd, dx_file_free) has min(found, max_list) entries in ascending code order when min_count >= 1 and list != NULL.
+ * There is no table.  The codes and the sort's second array stand on the device together, 16 bytes a window: if dx_malloc cannot
+ * give them the call is DX_E_NOMEM and dx_last_error names the bytes asked for.  DX_E_ARG (dx_last_error says why) for DX_KIND_QUIVA,
+ * an unknown kind, canonical with arrow, k outside 1..32, nspec < 2 with a spectrum, a list without `listed`; else dx_file_unpack2's
+ * errors for the image.  *out and the caller's spectrum are untouched on any error.                                               */
+int dx_file_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k /* 1..32 */, int canonical,
+                       uint64_t min_count, uint64_t max_list, dx_kmers64 *out,
+                       uint64_t *spectrum /* host, nspec; may be NULL */, uint32_t nspec,
+                       dx_kmer64 **list /* may be NULL; malloc'd, dx_file_free */, uint64_t *listed);
+
+/* dx_kmer_code and dx_kmer_letters for 1 <= k <= 32.  Host only.  DX_E_ARG for k outside 1..32, a letter that is not the kind's (the
+ * text's end among them), a code of more than 2 k bits (k < 32), a NULL pointer.                                                  */
+int dx_kmer_code64(int arrow, const char *letters, uint32_t k, int canonical, uint64_t *code);
+int dx_kmer_letters64(int arrow, uint64_t code, uint32_t k, char *out /* k + 1 */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
