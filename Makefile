@@ -16,7 +16,7 @@ CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 # $(CSRC)/*.hip and *.hpp only); units/dx_units.hpp is what four of them share, find/dx_find_edit.hpp the queries of the two edit-distance files, dx_words.h the names of the words of ctx->d_u64
 HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads reads/dx_lines reads/dx_repack digest/dx_crc census/dx_census compare/dx_diff find/dx_find find/dx_find_edit find/dx_find_span kmers/dx_kmers kmers/dx_kmer_codes kmers/dx_kmer_runs sort/dx_sort
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
-C_SRC    = dx_host dx_walk_host dx_crew dx_files dx_file_pack2 dx_file_qv dx_file_qv_shard dx_file_check dx_file_subset dx_file_extract dx_file_compare dx_file_find dx_file_find_edit dx_file_cut dx_file_kmers dx_file_kmers_wide dx_select dx_compat
+C_SRC    = dx_host dx_walk_host dx_crew dx_files dx_file_pack2 dx_file_qv dx_file_qv_shard dx_file_check dx_file_u2 dx_file_subset dx_file_extract dx_file_compare dx_file_find dx_file_find_edit dx_file_cut dx_file_kmers dx_file_kmers_wide dx_select dx_compat
 C_OBJ    = $(C_SRC:%=$(BUILD)/%.o)
 TOOLS    = dexta undexta dexar undexar dexqv undexqv
 

@@ -396,8 +396,9 @@ done:
  *  census (dx_file_census): what an image holds -- records, symbols, the shortest and the longest read, N50, the composition of the
  *  2-bit kinds, the distribution of a .quiva's five lines -- for the day the text is gone.  dex2DB.c:587-595 / 793-797 count
  *  the same on one core as reads enter a database (DAZZ_DB.freq, totlen, maxlen: 896-913).  A .dexta / .dexar image is walked and
- *  uploaded, and its packed reads are counted where they lie (dx_code_counts): no text is made.  A .dexqv image is planned and decoded
- *  as the digest does it, and a slice hook counts every entry's five lines where they are made (dx_byte_hist_ranges).
+ *  uploaded slice by slice (dxf_u2_slices, dx_file_u2.c), and its packed reads are counted where they lie (dx_code_counts): no text
+ *  is made.  A .dexqv image is planned and decoded as the digest does it, and a slice hook counts every entry's five lines where they
+ *  are made (dx_byte_hist_ranges).
  * ========================================================================================== */
 /* Two counting passes, the first over the lengths' high halves (how many, and their sum), the second over the low halves of the
    lengths in the bucket in which the running sum, from the longest down, reaches half of the total. */
@@ -430,63 +431,19 @@ int dx_census_lengths(const uint32_t *len, uint64_t n, dx_census *out)
   return DX_OK;
 }
 
-/* how much of a 2-bit image of m bytes the device takes at once beside 48 bytes of arrays a record: 0 = all of it.  DEXGPU_TEXT_BUDGET
-   counts bytes of image here (there is no text) */
-size_t dxf_u2_cap(dx_ctx *ctx, size_t m, uint64_t units)
-{ uint64_t fr = 0, all = 0;
-  size_t   cap;
-  if (dxf_budget_env(m, 4096u, &cap)) return cap;
-  if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
-  if ((double) m + 48.0 * (double) units <= 0.9 * (double) fr) return 0;
-  { const double room = (0.9 * (double) fr) / 2.0;
-    return room > (double) ((size_t) 4 << 20) ? (size_t) room : (size_t) 4 << 20;
-  }
-}
+/* a slice of a walked image's packed reads (dxf_u2_slices, 16 bytes a record of its own): code[4] added to and, when wanted, every
+   record's four counts */
+typedef struct { dx_ctx *ctx; uint64_t *code; uint32_t *rec; } census2_job;
 
-static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
-
-/* a slice of whole records from i0 on: as many as span at most `cap` bytes of image, and one at least; cap 0: all that are left */
-uint64_t dxf_u2_slice_end(const u2_index *x, uint64_t i0, size_t cap)
-{ uint64_t i1 = i0 + 1;
-  if (cap == 0) return x->cnt;
-  while (i1 < x->cnt && u2_end(x, i1) - x->ioff[i0] <= cap) i1++;
-  return i1;
-}
-
-/* the packed reads of a walked image, slice by slice of whole records: code[4] and, when wanted, every record's four counts */
-static int census_pack2(dx_ctx *ctx, const uint8_t *img, const u2_index *x, size_t cap, uint64_t code[4], uint32_t *rec)
-{ const uint64_t cnt = x->cnt;
-  uint64_t *rel = NULL, i, i0, i1, most = 0, tot[4];
-  size_t    smax = 0, in_cap = 0, arr_cap = 0;
-  void     *d_in = NULL, *d_arr = NULL;
-  int       rc = DX_OK;
-  for (i0 = 0; i0 < cnt; i0 = i1)                         /* the largest slice: one allocation serves them all */
-    { i1 = dxf_u2_slice_end(x, i0, cap);
-      if (u2_end(x, i1 - 1) - x->ioff[i0] > smax) smax = (size_t) (u2_end(x, i1 - 1) - x->ioff[i0]);
-      if (i1 - i0 > most) most = i1 - i0;
-    }
-  if ((rel = malloc((most + 1) * sizeof(*rel))) == NULL) return DX_E_NOMEM;
-  TRY(dgrow(ctx, &d_in, &in_cap, smax + 64));
-  TRY(dgrow(ctx, &d_arr, &arr_cap, (size_t) most * 28 + 64));          /* offsets (8), symbols (4), counts (16) */
-  for (i0 = 0; i0 < cnt; i0 = i1)
-    { const uint64_t b0 = x->ioff[i0];
-      uint64_t *d_boff = d_arr;
-      uint32_t *d_cnt, *d_len;
-      i1 = dxf_u2_slice_end(x, i0, cap);
-      d_cnt = (uint32_t *) (d_boff + most); d_len = d_cnt + 4 * most;
-      for (i = i0; i < i1; i++) rel[i - i0] = x->ioff[i] - b0;
-      TRY(dx_h2d(ctx, d_in, img + b0, (size_t) (u2_end(x, i1 - 1) - b0)));
-      TRY(dx_h2d(ctx, d_boff, rel, (size_t) (i1 - i0) * 8));
-      TRY(dx_h2d(ctx, d_len, x->nsym + i0, (size_t) (i1 - i0) * 4));
-      TRY(dx_code_counts(ctx, d_in, u2_end(x, i1 - 1) - b0, d_boff, NULL, d_len, i1 - i0, rec ? d_cnt : NULL, tot, NULL));
-      if (rec != NULL) TRY(dx_d2h(ctx, rec + 4 * i0, d_cnt, (size_t) (i1 - i0) * 16));
-      for (i = 0; i < 4; i++) code[i] += tot[i];
-    }
-done:
-  if (d_in) (void) dx_free(ctx, d_in);
-  if (d_arr) (void) dx_free(ctx, d_arr);
-  free(rel);
-  return rc;
+static int census_pack2_slice(void *arg, const u2_slice *s)
+{ census2_job *c = arg;
+  uint32_t *d_cnt = s->d_extra;
+  uint64_t  tot[4];
+  int       rc, q;
+  if ((rc = dx_code_counts(c->ctx, s->d_in, s->bytes, s->d_boff, NULL, s->d_len, s->n, c->rec ? d_cnt : NULL, tot, NULL)) != DX_OK) return rc;
+  if (c->rec != NULL && (rc = dx_d2h(c->ctx, c->rec + 4 * s->i0, d_cnt, (size_t) s->n * 16)) != DX_OK) return rc;
+  for (q = 0; q < 4; q++) c->code[q] += tot[q];
+  return DX_OK;
 }
 
 typedef struct
@@ -553,7 +510,10 @@ int dx_file_census(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, dx_censu
     }
   if (kind != DX_KIND_QUIVA)
     { if (rec_code != NULL && (rcode = malloc((cnt + 1) * 4 * sizeof(*rcode))) == NULL) { rc = DX_E_NOMEM; goto done; }
-      if (cnt > 0) TRY(census_pack2(ctx, img, &im.ux, dxf_u2_cap(ctx, m, cnt), cs->code, rcode));
+      if (cnt > 0)
+        { census2_job c = { ctx, cs->code, rcode };
+          TRY(dxf_u2_slices(ctx, img, &im.ux, dxf_u2_cap(ctx, m, cnt), 16, census_pack2_slice, &c));
+        }
     }
   else
     { census_job c;

@@ -24,8 +24,6 @@
 /* ==========================================================================================
  *  the host part: two walks paired (tools/compare_host_check.c runs it alone, under the sanitizers)
  * ========================================================================================== */
-static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
-
 /* the prefix of a walked 2-bit image (the walk has seen to it that it is there): undexta.c:161-169 */
 static void u2_prefix(const uint8_t *img, const char **name, size_t *plen)
 { uint16_t key;
@@ -87,7 +85,7 @@ int dxf_compare_open(dx_ctx *ctx, int kind, const uint8_t *img_a, size_t m_a, co
   for (i = 0; i <= p->both; i++)
     if (kind == DX_KIND_QUIVA) { p->pa[i] = text_at(&p->a.h, i); p->pb[i] = text_at(&p->b.h, i); }
     else if (i < p->both)      { p->pa[i] = p->a.ux.ioff[i]; p->pb[i] = p->b.ux.ioff[i]; }
-    else                       { p->pa[i] = i ? u2_end(&p->a.ux, i - 1) : 0; p->pb[i] = i ? u2_end(&p->b.ux, i - 1) : 0; }
+    else                       { p->pa[i] = i ? dxf_u2_end(&p->a.ux, i - 1) : 0; p->pb[i] = i ? dxf_u2_end(&p->b.ux, i - 1) : 0; }
   return DX_OK;
 }
 
@@ -150,8 +148,8 @@ static int compare_pack2(cmp_job *j, size_t cap)
   int       rc = DX_OK;
   for (i0 = 0; i0 < p->both; i0 = i1)                     /* the largest slice: one allocation serves them all */
     { i1 = dxf_compare_slice_end(p, i0, cap);
-      if (u2_end(xa, i1 - 1) - xa->ioff[i0] > amax) amax = (size_t) (u2_end(xa, i1 - 1) - xa->ioff[i0]);
-      if (u2_end(xb, i1 - 1) - xb->ioff[i0] > bmax) bmax = (size_t) (u2_end(xb, i1 - 1) - xb->ioff[i0]);
+      if (dxf_u2_end(xa, i1 - 1) - xa->ioff[i0] > amax) amax = (size_t) (dxf_u2_end(xa, i1 - 1) - xa->ioff[i0]);
+      if (dxf_u2_end(xb, i1 - 1) - xb->ioff[i0] > bmax) bmax = (size_t) (dxf_u2_end(xb, i1 - 1) - xb->ioff[i0]);
       if (i1 - i0 > most) most = i1 - i0;
     }
   TRY(dgrow(j->ctx, &d_a, &a_cap, amax + 64));
@@ -167,13 +165,13 @@ static int compare_pack2(cmp_job *j, size_t cap)
         { aoff[i - i0] = xa->ioff[i] - a0; boff[i - i0] = xb->ioff[i] - b0;
           len[i - i0]  = xa->nsym[i] < xb->nsym[i] ? xa->nsym[i] : xb->nsym[i];
         }
-      TRY(dx_h2d(j->ctx, d_a, p->a.img + a0, (size_t) (u2_end(xa, i1 - 1) - a0)));
-      TRY(dx_h2d(j->ctx, d_b, p->b.img + b0, (size_t) (u2_end(xb, i1 - 1) - b0)));
+      TRY(dx_h2d(j->ctx, d_a, p->a.img + a0, (size_t) (dxf_u2_end(xa, i1 - 1) - a0)));
+      TRY(dx_h2d(j->ctx, d_b, p->b.img + b0, (size_t) (dxf_u2_end(xb, i1 - 1) - b0)));
       TRY(dx_h2d(j->ctx, j->d_arr, j->h_arr, (size_t) m * 20));
       { const uint64_t *da_off = j->d_arr, *db_off = da_off + m;
         const uint32_t *d_len = (const uint32_t *) (db_off + m);
         uint32_t *d_differ = (uint32_t *) d_len + m;
-        TRY(dx_code_diff(j->ctx, d_a, u2_end(xa, i1 - 1) - a0, da_off, d_b, u2_end(xb, i1 - 1) - b0, db_off, d_len, m, d_differ, NULL,
+        TRY(dx_code_diff(j->ctx, d_a, dxf_u2_end(xa, i1 - 1) - a0, da_off, d_b, dxf_u2_end(xb, i1 - 1) - b0, db_off, d_len, m, d_differ, NULL,
                          tot, &first, NULL));
         TRY(dx_d2h(j->ctx, j->rec + i0, d_differ, (size_t) m * 4));
       }
@@ -254,19 +252,6 @@ static size_t compare_qv_cap(dx_ctx *ctx, const cmp_pair *p, int *whole_in)
   return cap;
 }
 
-/* ... and of the two 2-bit images (there is no text: DEXGPU_TEXT_BUDGET counts bytes of image here, as for dx_file_census) */
-static size_t compare_pack2_cap(dx_ctx *ctx, const cmp_pair *p)
-{ const uint64_t whole = p->pa[p->both] + p->pb[p->both];
-  uint64_t fr = 0, all = 0;
-  size_t   cap;
-  if (dxf_budget_env((size_t) whole, 4096u, &cap)) return cap;
-  if (dx_mem_info(ctx, &fr, &all) != DX_OK || fr == 0) return 0;
-  if ((double) whole + 48.0 * (double) p->both <= 0.9 * (double) fr) return 0;
-  { const double room = (0.9 * (double) fr) / 2.0;
-    return room > (double) ((size_t) 4 << 20) ? (size_t) room : (size_t) 4 << 20;
-  }
-}
-
 int dx_file_compare(dx_ctx *ctx, int kind, const uint8_t *img_a, size_t m_a, const uint8_t *img_b, size_t m_b,
                     int lossy, dx_compare *out, uint32_t **rec_differ)
 { static const uint8_t lossy_and[5] = { 0xff, 0xff, 0xfe, 0xfc, 0xff };      /* QV.c:1406-1415: the insertion and the merge line */
@@ -287,7 +272,7 @@ int dx_file_compare(dx_ctx *ctx, int kind, const uint8_t *img_a, size_t m_a, con
   if ((j.rec = calloc((size_t) (p.both + 1) * (size_t) c.lines, sizeof(*j.rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
 
   if (p.both > 0 && kind != DX_KIND_QUIVA)
-    TRY(compare_pack2(&j, compare_pack2_cap(ctx, &p)));
+    TRY(compare_pack2(&j, dxf_u2_cap(ctx, (size_t) (p.pa[p.both] + p.pb[p.both]), p.both)));     /* (of the two images together) */
   else if (p.both > 0)
     { const size_t cap = compare_qv_cap(ctx, &p, &j.whole_in);
       uint64_t i0, i1;

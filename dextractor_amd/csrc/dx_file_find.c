@@ -12,7 +12,7 @@
  * A pattern becomes one query, or two with both_strands: the reverse complement is the codes 3 - c in reverse order, and a pattern
  * that equals its own is searched once.  The queries stand in the order (pattern, strand), so that the kernel's order (unit, pos,
  * query) is the file's (record, pos, pattern, strand); dxf_find_map then names every hit by its pattern and strand.
- * An image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET, goes in slices of whole records (dxf_u2_slice_end): a
+ * An image that does not fit the device, or exceeds DEXGPU_TEXT_BUDGET, goes in slices of whole records (dxf_u2_slices, dx_file_u2.c): a
  * slice's hits are listed into what max_hits has left, its record numbers moved by the slice's first record.
  *
  * Everything behind the plan is dxf_find_run, which dx_file_find_edit.c calls with its own plan and kernel (edit = 1) -- and, for
@@ -94,8 +94,6 @@ void dxf_find_map(const find_plan *fp, dx_hit *h, uint64_t cnt, uint64_t i0)
     }
 }
 
-static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
-
 int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char *const *pattern, uint32_t npat, uint32_t max_mis,
                  int both_strands, uint64_t max_hits, dx_find *out, dx_hit **hits, uint32_t **rec_hits)
 { find_plan fp;
@@ -107,106 +105,104 @@ int dx_file_find(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const char
   return dxf_find_run(ctx, kind, img, m, &fp, 0, max_hits, out, hits, rec_hits, NULL, NULL);
 }
 
+/* what dxf_find_run holds across the slices: the plan, the report so far, every record's count, the hits kept and (start wanted) their
+   starts, and the device arrays a slice's hits and starts are listed into */
+typedef struct
+  { dx_ctx *ctx; const find_plan *fp; int edit, starts;
+    dx_find  *fd;
+    uint32_t *rec, *st;
+    dx_hit   *list;
+    uint64_t  keep, kept, list_cap;
+    void     *d_hits, *d_st;
+    size_t    hit_cap, st_cap;
+  } find_job;
+
+/* a slice of the image's packed reads (dxf_u2_slices, 4 bytes a record of its own: the record's count) searched, its hits listed into
+   what `keep` has left */
+static int find_slice(void *arg, const u2_slice *s)
+{ find_job *j = arg;
+  dx_ctx   *ctx = j->ctx;
+  const find_plan *fp = j->fp;
+  uint32_t *d_cnt = s->d_extra;
+  uint64_t  i, found = 0, room, tot[64];
+  int       rc;
+  room = j->keep - j->kept < FIND_ROOM ? j->keep - j->kept : FIND_ROOM;
+  for (;;)                                                  /* (a second time only for a slice with more hits than FIND_ROOM that are wanted) */
+    { TRY(dgrow(ctx, &j->d_hits, &j->hit_cap, (size_t) room * sizeof(dx_hit) + 64));
+      if (j->edit) TRY(dx_code_find_edit(ctx, s->d_in, s->bytes, s->d_boff, NULL, s->d_len, s->n, fp->eq, fp->nq, d_cnt, j->d_hits, room, tot, &found, NULL));
+      else         TRY(dx_code_find(ctx, s->d_in, s->bytes, s->d_boff, NULL, s->d_len, s->n, fp->q, fp->nq, d_cnt, j->d_hits, room, tot, &found, NULL));
+      if (found <= room || room == j->keep - j->kept) break;
+      room = found < j->keep - j->kept ? found : j->keep - j->kept;
+      if (room > UINT32_MAX)
+        return (j->edit ? dx_find_edit_fail : dx_find_fail)(ctx, DX_E_NOMEM, "more than 2^32 - 1 hits of one slice to list: lower max_hits");
+    }
+  TRY(dx_d2h(ctx, j->rec + s->i0, d_cnt, (size_t) s->n * 4));
+  for (i = 0; i < fp->nq; i++) j->fd->per_pattern[fp->pat[i]][fp->strand[i]] += tot[i];
+  j->fd->hits += found;
+  { const uint64_t got = found < room ? found : room;
+    if (got)
+      { if (j->kept + got > j->list_cap)
+          { const uint64_t want = j->kept + got > 2 * j->list_cap ? j->kept + got : 2 * j->list_cap;
+            dx_hit *bigger = realloc(j->list, (size_t) want * sizeof(*j->list));
+            if (bigger == NULL) return DX_E_NOMEM;
+            j->list = bigger; j->list_cap = want;
+            if (j->starts)
+              { uint32_t *more = realloc(j->st, (size_t) want * sizeof(*j->st));
+                if (more == NULL) return DX_E_NOMEM;
+                j->st = more;
+              }
+          }
+        if (j->starts)                                      /* the slice's image and its unit-relative hits are still on the device */
+          { TRY(dgrow(ctx, &j->d_st, &j->st_cap, (size_t) got * sizeof(*j->st) + 64));
+            TRY(dx_code_hit_starts(ctx, s->d_in, s->bytes, s->d_boff, NULL, s->d_len, s->n, fp->eq, fp->nq, j->d_hits, got, j->d_st, NULL));
+            TRY(dx_d2h(ctx, j->st + j->kept, j->d_st, (size_t) got * sizeof(*j->st)));
+          }
+        TRY(dx_d2h(ctx, j->list + j->kept, j->d_hits, (size_t) got * sizeof(*j->list)));
+        dxf_find_map(fp, j->list + j->kept, got, s->i0);
+        j->kept += got;
+      }
+  }
+done:
+  return rc;
+}
+
 int dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const find_plan *fp, int edit, uint64_t max_hits, dx_find *out,
                  dx_hit **hits, uint32_t **rec_hits, uint32_t **start, uint32_t **rec_len)
 { image_text im;
-  dx_find   *fd = NULL;
-  dx_hit    *list = NULL;
-  uint32_t  *rec = NULL, *st = NULL, *rlen = NULL;
-  uint64_t  *rel = NULL, cnt, i, i0, i1, most = 0, list_cap = 0, kept = 0, tot[64];
-  const uint64_t keep = hits != NULL ? max_hits : 0;       /* hits the list is to hold (nobody takes it: none) */
-  size_t     cap, smax = 0, in_cap = 0, arr_cap = 0, hit_cap = 0, st_cap = 0;
-  void      *d_in = NULL, *d_arr = NULL, *d_hits = NULL, *d_st = NULL;
-  const u2_index *x;
+  find_job   j;
+  uint32_t  *rlen = NULL;
+  uint64_t   cnt, i;
   int        rc;
 
+  memset(&j, 0, sizeof(j));
+  j.ctx = ctx; j.fp = fp; j.edit = edit; j.starts = start != NULL;
+  j.keep = hits != NULL ? max_hits : 0;                    /* hits the list is to hold (nobody takes it: none) */
   TRY(dxf_image_open(ctx, kind, 0, 1, img, m, &im));       /* (the line width lays out a text nobody makes) */
-  x = &im.ux; cnt = x->cnt;
-  if ((fd = calloc(1, sizeof(*fd))) == NULL || (rec = malloc((cnt + 1) * sizeof(*rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
-  fd->records = cnt;
+  cnt = im.ux.cnt;
+  if ((j.fd = calloc(1, sizeof(*j.fd))) == NULL || (j.rec = malloc((cnt + 1) * sizeof(*j.rec))) == NULL) { rc = DX_E_NOMEM; goto done; }
+  j.fd->records = cnt;
   if (rec_len)
     { if ((rlen = malloc((cnt + 1) * sizeof(*rlen))) == NULL) { rc = DX_E_NOMEM; goto done; }
-      if (cnt) memcpy(rlen, x->nsym, (size_t) cnt * sizeof(*rlen));
+      if (cnt) memcpy(rlen, im.ux.nsym, (size_t) cnt * sizeof(*rlen));
     }
 
-  cap = cnt ? dxf_u2_cap(ctx, m, cnt) : 0;
-  for (i0 = 0; i0 < cnt; i0 = i1)                          /* the largest slice: one allocation serves them all */
-    { i1 = dxf_u2_slice_end(x, i0, cap);
-      if (u2_end(x, i1 - 1) - x->ioff[i0] > smax) smax = (size_t) (u2_end(x, i1 - 1) - x->ioff[i0]);
-      if (i1 - i0 > most) most = i1 - i0;
-    }
-  if (cnt)
-    { if ((rel = malloc((most + 1) * sizeof(*rel))) == NULL) { rc = DX_E_NOMEM; goto done; }
-      TRY(dgrow(ctx, &d_in, &in_cap, smax + 64));
-      TRY(dgrow(ctx, &d_arr, &arr_cap, (size_t) most * 16 + 64));            /* offsets (8), symbols (4), counts (4) */
-    }
-  for (i0 = 0; i0 < cnt; i0 = i1)
-    { const uint64_t b0 = x->ioff[i0];
-      uint64_t *d_boff = d_arr, n, found = 0, room, bytes;
-      uint32_t *d_len, *d_cnt;
-      i1 = dxf_u2_slice_end(x, i0, cap); n = i1 - i0; bytes = u2_end(x, i1 - 1) - b0;
-      d_len = (uint32_t *) (d_boff + most); d_cnt = d_len + most;
-      for (i = i0; i < i1; i++) rel[i - i0] = x->ioff[i] - b0;
-      TRY(dx_h2d(ctx, d_in, img + b0, (size_t) bytes));
-      TRY(dx_h2d(ctx, d_boff, rel, (size_t) n * 8));
-      TRY(dx_h2d(ctx, d_len, x->nsym + i0, (size_t) n * 4));
-      room = keep - kept < FIND_ROOM ? keep - kept : FIND_ROOM;
-      for (;;)                                              /* (a second time only for a slice with more hits than FIND_ROOM that are wanted) */
-        { TRY(dgrow(ctx, &d_hits, &hit_cap, (size_t) room * sizeof(dx_hit) + 64));
-          if (edit) TRY(dx_code_find_edit(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp->eq, fp->nq, d_cnt, d_hits, room, tot, &found, NULL));
-          else      TRY(dx_code_find(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp->q, fp->nq, d_cnt, d_hits, room, tot, &found, NULL));
-          if (found <= room || room == keep - kept) break;
-          room = found < keep - kept ? found : keep - kept;
-          if (room > UINT32_MAX)
-            { rc = (edit ? dx_find_edit_fail : dx_find_fail)(ctx, DX_E_NOMEM, "more than 2^32 - 1 hits of one slice to list: lower max_hits");
-              goto done;
-            }
-        }
-      TRY(dx_d2h(ctx, rec + i0, d_cnt, (size_t) n * 4));
-      for (i = 0; i < fp->nq; i++) fd->per_pattern[fp->pat[i]][fp->strand[i]] += tot[i];
-      fd->hits += found;
-      { const uint64_t got = found < room ? found : room;
-        if (got)
-          { if (kept + got > list_cap)
-              { const uint64_t want = kept + got > 2 * list_cap ? kept + got : 2 * list_cap;
-                dx_hit *bigger = realloc(list, (size_t) want * sizeof(*list));
-                if (bigger == NULL) { rc = DX_E_NOMEM; goto done; }
-                list = bigger; list_cap = want;
-                if (start)
-                  { uint32_t *more = realloc(st, (size_t) want * sizeof(*st));
-                    if (more == NULL) { rc = DX_E_NOMEM; goto done; }
-                    st = more;
-                  }
-              }
-            if (start)                                      /* the slice's image and its unit-relative hits are still on the device */
-              { TRY(dgrow(ctx, &d_st, &st_cap, (size_t) got * sizeof(*st) + 64));
-                TRY(dx_code_hit_starts(ctx, d_in, bytes, d_boff, NULL, d_len, n, fp->eq, fp->nq, d_hits, got, d_st, NULL));
-                TRY(dx_d2h(ctx, st + kept, d_st, (size_t) got * sizeof(*st)));
-              }
-            TRY(dx_d2h(ctx, list + kept, d_hits, (size_t) got * sizeof(*list)));
-            dxf_find_map(fp, list + kept, got, i0);
-            kept += got;
-          }
-      }
-    }
-  for (i = 0; i < cnt; i++) fd->records_hit += rec[i] != 0;
-  fd->listed = fd->hits < max_hits ? fd->hits : max_hits;
-  if (hits != NULL && list == NULL && (list = malloc(sizeof(*list))) == NULL) { rc = DX_E_NOMEM; goto done; }
-  if (start != NULL && st == NULL && (st = malloc(sizeof(*st))) == NULL) { rc = DX_E_NOMEM; goto done; }
+  TRY(dxf_u2_slices(ctx, img, &im.ux, cnt ? dxf_u2_cap(ctx, m, cnt) : 0, 4, find_slice, &j));
+  for (i = 0; i < cnt; i++) j.fd->records_hit += j.rec[i] != 0;
+  j.fd->listed = j.fd->hits < max_hits ? j.fd->hits : max_hits;
+  if (hits != NULL && j.list == NULL && (j.list = malloc(sizeof(*j.list))) == NULL) { rc = DX_E_NOMEM; goto done; }
+  if (start != NULL && j.st == NULL && (j.st = malloc(sizeof(*j.st))) == NULL) { rc = DX_E_NOMEM; goto done; }
 
-  *out = *fd;
-  if (hits) { *hits = list; list = NULL; }
-  if (rec_hits) { *rec_hits = rec; rec = NULL; }
-  if (start) { *start = st; st = NULL; }
+  *out = *j.fd;
+  if (hits) { *hits = j.list; j.list = NULL; }
+  if (rec_hits) { *rec_hits = j.rec; j.rec = NULL; }
+  if (start) { *start = j.st; j.st = NULL; }
   if (rec_len) { *rec_len = rlen; rlen = NULL; }
   rc = DX_OK;
 
 done:
-  if (d_in) (void) dx_free(ctx, d_in);
-  if (d_arr) (void) dx_free(ctx, d_arr);
-  if (d_hits) (void) dx_free(ctx, d_hits);
-  if (d_st) (void) dx_free(ctx, d_st);
+  if (j.d_hits) (void) dx_free(ctx, j.d_hits);
+  if (j.d_st) (void) dx_free(ctx, j.d_st);
   dxf_image_close(&im);
-  free(fd); free(list); free(rec); free(rel); free(st); free(rlen);
+  free(j.fd); free(j.list); free(j.rec); free(j.st); free(rlen);
   return rc;
 }

@@ -8,11 +8,11 @@
  * and the answer in ascending code order.  The meanings are dx_file_kmers': the count is over what the archive HOLDS, record by record.
  *
  * The image is opened and walked as dx_file_kmers_add walks it (dxf_image_open; slices of whole records under dxf_u2_cap /
- * DEXGPU_TEXT_BUDGET).  The windows are known from the lengths before anything is allocated; the codes and the sort's second array
- * stand on the device together, 16 bytes a window.  An image whose windows do not fit that way is DX_E_NOMEM: passes over ranges of
- * the codes are the next step, as is counting several files into one answer.
+ * DEXGPU_TEXT_BUDGET, handed over by dxf_u2_slices, dx_file_u2.c).  The windows are known from the lengths before anything is
+ * allocated; the codes and the sort's second array stand on the device together, 16 bytes a window.  An image whose windows do not
+ * fit that way is DX_E_NOMEM: passes over ranges of the codes are the next step, as is counting several files into one
+ * answer.
  */
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -53,21 +53,18 @@ static void wmark(const char *what)
   dx_mark("kmers_wide", &t0, what);
 }
 
-static int wide_args(dx_ctx *ctx, int kind, uint32_t k, int canonical)
-{ char why[96];
-  if (kind == DX_KIND_QUIVA)
-    return dx_kmers_wide_fail(ctx, DX_E_ARG, "a .dexqv image has no packed reads to count (DX_KIND_FASTA or DX_KIND_ARROW)");
-  if (kind != DX_KIND_FASTA && kind != DX_KIND_ARROW) return dx_kmers_wide_fail(ctx, DX_E_ARG, "unknown kind");
-  if (canonical && kind == DX_KIND_ARROW)
-    return dx_kmers_wide_fail(ctx, DX_E_ARG, "canonical: pulse widths have no complement (DX_KIND_FASTA only)");
-  if (k < 1 || k > KMER64_KMAX)
-    { snprintf(why, sizeof(why), "k = %u (1 to %u)", k, KMER64_KMAX);
-      return dx_kmers_wide_fail(ctx, DX_E_ARG, why);
-    }
+/* a slice of the image's packed reads (dxf_u2_slices): its windows' codes written behind those of the slices before it */
+typedef struct { dx_ctx *ctx; uint32_t k; int canonical; uint64_t *d_codes, windows, done; } wide_job;
+
+static int wide_slice(void *arg, const u2_slice *s)
+{ wide_job *j = arg;
+  uint64_t  w = 0;
+  int       rc;
+  if ((rc = dx_code_kmer_codes(j->ctx, s->d_in, s->bytes, s->d_boff, NULL, s->d_len, s->n, j->k, j->canonical, j->d_codes + j->done,
+                               j->windows - j->done, &w, NULL)) != DX_OK) return rc;
+  j->done += w;
   return DX_OK;
 }
-
-static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
 
 int dx_file_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical,
                        uint64_t min_count, uint64_t max_list, dx_kmers64 *out, uint64_t *spectrum, uint32_t nspec,
@@ -75,15 +72,16 @@ int dx_file_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint
 { image_text im;
   dx_kmers64 km;
   dx_kmer64 *lst = NULL;
-  uint64_t  *rel = NULL, *spec = NULL, cnt, i, i0, i1, most = 0, done = 0, found = 0, got = 0, room = 0;
-  size_t     cap, smax = 0, in_cap = 0, arr_cap = 0;
-  void      *d_in = NULL, *d_arr = NULL, *d_codes = NULL, *d_tmp = NULL, *d_list = NULL;
+  wide_job   j;
+  uint64_t  *spec = NULL, cnt, i, found = 0, got = 0, room = 0;
+  size_t     cap;
+  void      *d_codes = NULL, *d_tmp = NULL, *d_list = NULL;
   const u2_index *x;
   int        rc, want_list;
   if (ctx == NULL || out == NULL || (img == NULL && m)) return DX_E_ARG;
   if (list) *list = NULL;
   if (listed) *listed = 0;
-  if ((rc = wide_args(ctx, kind, k, canonical)) != DX_OK) return rc;
+  if ((rc = dxf_kmers_args(ctx, kind, k, KMER64_KMAX, canonical, dx_kmers_wide_fail)) != DX_OK) return rc;
   if (spectrum != NULL && nspec < 2) return dx_kmers_wide_fail(ctx, DX_E_ARG, "a spectrum of fewer than 2 bins");
   if (list != NULL && listed == NULL) return dx_kmers_wide_fail(ctx, DX_E_ARG, "a list without a place for its length");
   memset(&km, 0, sizeof(km));
@@ -99,35 +97,15 @@ int dx_file_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint
       if (x->nsym[i] >= k) km.windows += x->nsym[i] - k + 1;
     }
   cap = cnt ? dxf_u2_cap(ctx, m, cnt) : 0;
-  for (i0 = 0; i0 < cnt; i0 = i1)                          /* the largest slice: one allocation serves them all */
-    { i1 = dxf_u2_slice_end(x, i0, cap);
-      if (u2_end(x, i1 - 1) - x->ioff[i0] > smax) smax = (size_t) (u2_end(x, i1 - 1) - x->ioff[i0]);
-      if (i1 - i0 > most) most = i1 - i0;
-    }
   if (spectrum != NULL && (spec = calloc(nspec, sizeof(*spec))) == NULL) { rc = DX_E_NOMEM; goto done; }   /* (the caller's stays as it is on an error) */
   if (km.windows)
     { TRY(dx_malloc(ctx, (size_t) km.windows * 8 + 64, &d_codes));           /* the codes and the sort's second array: 16 bytes a window */
       TRY(dx_malloc(ctx, (size_t) km.windows * 8 + 64, &d_tmp));
-      if ((rel = malloc((most + 1) * sizeof(*rel))) == NULL) { rc = DX_E_NOMEM; goto done; }
-      TRY(dgrow(ctx, &d_in, &in_cap, smax + 64));
-      TRY(dgrow(ctx, &d_arr, &arr_cap, (size_t) most * 12 + 64));            /* offsets (8), symbols (4) */
     }
   wmark("the image walked, the device arrays made");
-  for (i0 = 0; i0 < cnt && km.windows; i0 = i1)
-    { const uint64_t b0 = x->ioff[i0];
-      uint64_t *d_boff = d_arr, n, bytes, w = 0;
-      uint32_t *d_len;
-      i1 = dxf_u2_slice_end(x, i0, cap); n = i1 - i0; bytes = u2_end(x, i1 - 1) - b0;
-      d_len = (uint32_t *) (d_boff + most);
-      for (i = i0; i < i1; i++) rel[i - i0] = x->ioff[i] - b0;
-      TRY(dx_h2d(ctx, d_in, img + b0, (size_t) bytes));
-      TRY(dx_h2d(ctx, d_boff, rel, (size_t) n * 8));
-      TRY(dx_h2d(ctx, d_len, x->nsym + i0, (size_t) n * 4));
-      TRY(dx_code_kmer_codes(ctx, d_in, bytes, d_boff, NULL, d_len, n, k, canonical, (uint64_t *) d_codes + done, km.windows - done, &w, NULL));
-      done += w;
-    }
-  if (done != km.windows) { rc = dx_kmers_wide_fail(ctx, DX_E_FORMAT, "the slices' windows are not the image's"); goto done; }
-  if (d_in) { (void) dx_free(ctx, d_in); d_in = NULL; }
+  j = (wide_job) { ctx, k, canonical, d_codes, km.windows, 0 };
+  if (km.windows) TRY(dxf_u2_slices(ctx, img, x, cap, 0, wide_slice, &j));   /* (the slices' arrays are gone when it returns: the sort has the room) */
+  if (j.done != km.windows) { rc = dx_kmers_wide_fail(ctx, DX_E_FORMAT, "the slices' windows are not the image's"); goto done; }
   wmark("the slices up, their codes written");
 
   TRY(dx_sort_u64(ctx, d_codes, d_tmp, km.windows, 2 * k));
@@ -153,13 +131,11 @@ int dx_file_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint
   rc = DX_OK;
 
 done:
-  if (d_in) (void) dx_free(ctx, d_in);
-  if (d_arr) (void) dx_free(ctx, d_arr);
   if (d_codes) (void) dx_free(ctx, d_codes);
   if (d_tmp) (void) dx_free(ctx, d_tmp);
   if (d_list) (void) dx_free(ctx, d_list);
   dxf_image_close(&im);
-  free(rel); free(lst); free(spec);
+  free(lst); free(spec);
   wmark("the device arrays freed");
   return rc;
 }

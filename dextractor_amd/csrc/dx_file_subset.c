@@ -160,7 +160,6 @@ static size_t subset2_cap(dx_ctx *ctx, size_t m, size_t total, uint64_t units)
   }
 }
 
-static uint64_t u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
 
 /* where unit j's framing begins in the new image (j == n: where the image ends; unit 0 takes the file's head along) */
 static size_t unit_at(const subset2 *p, uint64_t n, uint64_t j)
@@ -180,12 +179,12 @@ static int subset2_run(dx_ctx *ctx, const uint8_t *img, const selection *s, subs
     { const uint64_t i0 = sel_id(s, j0), b0 = p->x.ioff[i0];
       uint64_t i1 = i0 + 1, m, b1;
       size_t   o0, o1;
-      while (cap != 0 && i1 < p->x.cnt && u2_end(&p->x, i1) - b0 <= cap) i1++;
+      while (cap != 0 && i1 < p->x.cnt && dxf_u2_end(&p->x, i1) - b0 <= cap) i1++;
       if (cap == 0) i1 = p->x.cnt;
       o0 = unit_at(p, n, j0);                              /* ... and of at most `cap` bytes of the new image: an id may repeat without end */
       for (j1 = j0; j1 < n && sel_id(s, j1) < i1 && (cap == 0 || j1 == j0 || unit_at(p, n, j1 + 1) - o0 <= cap); j1++) ;
       m  = j1 - j0;
-      b1 = u2_end(&p->x, sel_id(s, j1 - 1));               /* (from the first selected record to the last: ids do not decrease) */
+      b1 = dxf_u2_end(&p->x, sel_id(s, j1 - 1));               /* (from the first selected record to the last: ids do not decrease) */
       o1 = unit_at(p, n, j1);
       { uint64_t *t = realloc(rel, (size_t) (2 * m + 1) * sizeof(*rel));
         if (t == NULL) { rc = DX_E_NOMEM; goto done; }

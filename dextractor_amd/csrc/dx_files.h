@@ -7,6 +7,7 @@
  *     dx_file_qv_shard.c  dexqv sharded: a table of phases that a crew of threads walks, one per context
  *     dx_crew.c        that crew (dx_crew.h; dx_file_pack2_sharded is a crew of one phase): the library's only barrier wait
  *     dx_file_check.c  an image of any kind and its text where it is made: dx_file_verify, dx_file_digest, dx_file_census
+ *     dx_file_u2.c     the packed reads of a walked 2-bit image on the device, slice by slice: dxf_u2_slices and what decides the slices
  *     dx_select.c      the .qvs entry API, the .bps / .arw read loader
  *     dx_file_subset.c a new image cut out of an old one: dx_file_subset_layout (host), dx_file_subset
  *     dx_file_extract.c chosen records as text: dx_file_extract
@@ -14,6 +15,7 @@
  *     dx_file_find.c   where given sequences occur in an image's reads: dx_file_find
  *     dx_file_find_edit.c  ... within an edit distance: dx_file_find_edit, dx_file_find_edit_spans
  *     dx_file_kmers.c  the k-mers of an image's reads, counted: dx_file_kmers_add, dx_file_kmers; dx_kmer_code, dx_kmer_letters (host)
+ *     dx_file_kmers_wide.c  ... for k up to 32, counted by sorting: dx_file_kmers_wide; dx_kmer_code64, dx_kmer_letters64 (host)
  *     dx_file_cut.c    what is kept of the records once the occurrences are cut out, and the image of it: dx_hits_cut_plan (host), dx_file_cut
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.
@@ -235,10 +237,22 @@ DXF_HIDDEN void dxf_image_close(image_text *im);
    range himself (the 2-bit kinds' reads are compared where they lie: nobody asks for a range of their text, and it is DX_E_ARG) */
 DXF_HIDDEN int  dxf_image_range(dx_ctx *ctx, const image_text *im, uint64_t r0, uint64_t r1, int whole_in, slice_fn fn, void *arg);
 
+/* ---- dx_file_u2.c ---------------------------------------------------------------------------------------------------- */
+/* where record i's packed read ends in the image */
+static inline uint64_t dxf_u2_end(const u2_index *x, uint64_t i) { return x->ioff[i] + (((uint64_t) x->nsym[i] + 3) >> 2); }
+
 /* how much of a 2-bit image of m bytes the device takes at once beside 48 bytes of arrays a record: 0 = all of it (DEXGPU_TEXT_BUDGET counts
    bytes of image here); and a slice of whole records from i0 on: as many as span at most `cap` bytes of image, and one at least */
 DXF_HIDDEN size_t   dxf_u2_cap(dx_ctx *ctx, size_t m, uint64_t units);
 DXF_HIDDEN uint64_t dxf_u2_slice_end(const u2_index *x, uint64_t i0, size_t cap);
+
+/* a slice of a walked 2-bit image on the device: records [i0, i0 + n), `bytes` of image at d_in, record i0 + k's packed read at
+   d_boff[k] of it with d_len[k] symbols; d_extra: `extra` bytes a record of the hook's own, 8-byte aligned, not initialised */
+typedef struct { const uint8_t *d_in; uint64_t bytes; const uint64_t *d_boff; const uint32_t *d_len; void *d_extra; uint64_t i0, n; } u2_slice;
+typedef int (*u2_slice_fn)(void *arg, const u2_slice *s);
+/* the image's packed reads in slices of whole records, at most `cap` bytes of image each (0: in one), each to `fn`; the first answer
+   that is not DX_OK ends the loop and is returned.  No records: nothing is allocated and `fn` is not called */
+DXF_HIDDEN int dxf_u2_slices(dx_ctx *ctx, const uint8_t *img, const u2_index *x, size_t cap, size_t extra, u2_slice_fn fn, void *arg);
 
 /* ---- dx_file_find.c -------------------------------------------------------------------------------------------------- */
 /* The host part of dx_file_find, apart so that it can run without a device (ctx == NULL: no error text is kept).  The patterns as the
@@ -266,6 +280,11 @@ DXF_HIDDEN int  dxf_find_run(dx_ctx *ctx, int kind, const uint8_t *img, size_t m
    the queries of dx_code_find_edit in fp->eq, with pat, strand and nq as dxf_find_plan leaves them (fp->q stays empty). */
 DXF_HIDDEN int  dxf_find_edit_plan(dx_ctx *ctx, int kind, const char *const *pattern, uint32_t npat, uint32_t max_err, int both_strands,
                                    find_plan *fp);
+
+/* ---- dx_file_kmers.c ------------------------------------------------------------------------------------------------- */
+/* what dx_file_kmers (kmax 14, dx_kmers_fail) and dx_file_kmers_wide (32, dx_kmers_wide_fail) ask of kind, k and canonical: DX_E_ARG in
+   `fail`'s words */
+DXF_HIDDEN int  dxf_kmers_args(dx_ctx *ctx, int kind, uint32_t k, uint32_t kmax, int canonical, int (*fail)(dx_ctx *, int, const char *));
 
 /* ---- dx_file_compare.c ----------------------------------------------------------------------------------------------- */
 /* Two images of one kind, walked and paired by index: the first `both` records of each are compared.  pa / pb (both + 1 each): what the

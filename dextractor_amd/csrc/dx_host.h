@@ -54,4 +54,10 @@ int dx_crc32_ranges_strided(dx_ctx *ctx, const uint8_t *d_buf, uint64_t buf_byte
                             uint64_t n, uint64_t stride, uint32_t *d_crc, uint64_t *bad_unit);
 int dx_crc32_pairs(dx_ctx *ctx, const uint32_t *d_crc, const uint64_t *d_len, uint64_t m, uint32_t *d_out_crc, uint64_t *d_out_len);
 
+#ifdef __cplusplus
+/* For the device files alone (dx_qv.hip defines it with C++ linkage, whatever block this header is included in): the exclusive sums
+   of n counts on the device, d_out[0 .. n] with the total last; the total also comes back (`total` may be NULL) */
+extern "C++" int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);
+#endif
+
 #endif

@@ -76,26 +76,6 @@ extern "C" {
 struct fd_query   { uint64_t code, mask; uint32_t len, mis; };       // code and mask in the top 2 len bits of the word
 struct fd_queries { fd_query q[FD_QMAX]; };
 
-int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
-
-// the 8 bytes at byte o of the buffer as a word in the read's bit order (the first symbol on top); what lies behind the buffer's
-// end reads as zero, and the 8 bytes that would reach past it are its last 8, moved up (bytes >= 16)
-__device__ __forceinline__ uint64_t fd_be64(const uint8_t *in, uint64_t bytes, uint64_t o)
-{ if (o + 8u <= bytes) return __builtin_bswap64(*(const u64_u *) (in + o));
-  if (o >= bytes) return 0ull;
-  return __builtin_bswap64(*(const u64_u *) (in + (bytes - 8u))) << (8u * (uint32_t) (o + 8u - bytes));
-}
-
-// the chunk whose place is byte a < bytes of the buffer and the 8 bytes behind it, as three such words
-__device__ __forceinline__ void fd_chunk(const uint8_t *in, uint64_t bytes, uint64_t a, uint64_t &w0, uint64_t &w1, uint64_t &w2)
-{ const u32x4    v    = last16_ask(in, bytes, a);
-  const uint32_t back = (uint32_t) (a - last16_from(a, bytes));              // 0, or how many bytes in front of a the 16 begin
-  const uint64_t h = __builtin_bswap64(v.x | ((uint64_t) v.y << 32)), l = __builtin_bswap64(v.z | ((uint64_t) v.w << 32));
-  if (back == 0u)      { w0 = h; w1 = l; w2 = fd_be64(in, bytes, a + 16u); }
-  else if (back < 8u)  { w0 = (h << (8u * back)) | (l >> (64u - 8u * back)); w1 = l << (8u * back); w2 = 0ull; }
-  else                 { w0 = l << (8u * (back - 8u)); w1 = 0ull; w2 = 0ull; }
-}
-
 // What a lane has of a unit in one chunk: the chunk's positions [t0, t1) and the three words moved up to t0; `left`: the symbols
 // from position t0 to the unit's end, so that query k may begin at t0 + d while d + len_k <= left.
 struct fd_part { uint64_t w0, w1, w2; uint32_t t0, t1, left; };
@@ -107,7 +87,7 @@ __device__ __forceinline__ fd_part fd_take(const uint8_t *in, uint64_t bytes, ui
   if (p1 <= p0) return p;
   p.t0 = (uint32_t) (p0 - 4u * a); p.t1 = (uint32_t) (p1 - 4u * a); p.left = (uint32_t) (S1 - p0);      // (a unit has fewer than 2^31 symbols)
   uint64_t w0, w1, w2;
-  fd_chunk(in, bytes, a, w0, w1, w2);
+  chunk_words(in, bytes, a, w0, w1, w2);
   uint32_t s = p.t0;
   if (s >= 32u) { w0 = w1; w1 = w2; w2 = 0ull; s -= 32u; }
   if (s)
@@ -197,13 +177,6 @@ __device__ __forceinline__ uint64_t fd_list(const fd_part &p, const fd_queries &
       w0 = (w0 << 2) | (w1 >> 62); w1 = (w1 << 2) | (w2 >> 62); w2 <<= 2;
     }
   return at;                                               // (the place behind the part's hits, or some place at cap or beyond)
-}
-
-__device__ __forceinline__ uint64_t fd_wave_sum64(uint64_t v)
-{
-  #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += (uint64_t) __shfl_xor((unsigned long long) v, d);
-  return v;
 }
 
 // in holds in_bytes bytes and 16 at least; the units are checked against `bound` (as in k_code_counts).
@@ -304,7 +277,7 @@ void k_find(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, c
               else mine += c;
             }
           if (!LIST)
-            { const uint64_t all = fd_wave_sum64(mine);
+            { const uint64_t all = wave_sum64(mine);
               if (lane == 0u)
                 { if (count != NULL) count[u0 + (uint64_t) from] = all < 0xffffffffull ? (uint32_t) all : 0xffffffffu;
                   if (room != NULL) room[u0 + (uint64_t) from] = (uint32_t) (all < cap ? all : cap);

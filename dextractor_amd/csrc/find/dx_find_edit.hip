@@ -76,23 +76,6 @@ extern "C" {
 #define FE_LANE    4u                      // stretches: a unit of up to so many is its lane's
 #define FE_GROUP   UNITS_GROUP             // stretches: up to here 16 lanes take the unit, beyond the wave
 
-int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
-
-// the 8 bytes at byte o of the buffer (bytes >= 8) as a word in the read's bit order (the first symbol on top); what lies behind the
-// buffer's end reads as zero, and the 8 bytes that would reach past it are its last 8, moved up
-__device__ __forceinline__ uint64_t fe_be64(const uint8_t *in, uint64_t bytes, uint64_t o)
-{ if (o + 8u <= bytes) return __builtin_bswap64(*(const u64_u *) (in + o));
-  if (o >= bytes) return 0ull;
-  return __builtin_bswap64(*(const u64_u *) (in + (bytes - 8u))) << (8u * (uint32_t) (o + 8u - bytes));
-}
-
-__device__ __forceinline__ uint64_t fe_wave_sum64(uint64_t v)
-{
-  #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += (uint64_t) __shfl_xor((unsigned long long) v, d);
-  return v;
-}
-
 // What a lane has of a unit: the ends [e0, e1) of the unit whose first symbol is symbol U0 of the buffer and which has L symbols
 // (1 <= e0, e1 <= L + 1; e1 <= e0: nothing of it)
 struct fe_part { uint64_t U0; uint32_t L, e0, e1; };
@@ -123,10 +106,10 @@ __device__ __forceinline__ uint32_t fe_scan(const uint8_t *in, uint64_t bytes, c
   uint32_t score = m, ca = over, cb = over, n = 0;                               // cb = c(i), ca = c(i - 1) in front of symbol i
 
   uint64_t A = p.U0 + s, o = A >> 2;                                             // symbol s of the unit in the buffer, its byte
-  uint64_t w = fe_be64(in, bytes, o) << (2u * (uint32_t) (A & 3u));
+  uint64_t w = be64_at(in, bytes, o) << (2u * (uint32_t) (A & 3u));
   uint32_t have = 32u - (uint32_t) (A & 3u);                                     // symbols left in w
   for (uint32_t i = s; i < t; i++)
-    { if (have == 0u) { o += 8u; w = fe_be64(in, bytes, o); have = 32u; }
+    { if (have == 0u) { o += 8u; w = be64_at(in, bytes, o); have = 32u; }
       const int32_t top = (int32_t) (w >> 32);                                   // the symbol: bits 31, 30
       const W B1 = (W) (int64_t) (top >> 31), B0 = (W) (int64_t) ((int32_t) ((uint32_t) top << 1) >> 31);      // its two bits, each all over a word
       w <<= 2; have--;
@@ -306,7 +289,7 @@ void k_find_edit(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bou
               else mine += fe_all<FE_COUNT>(in, in_bytes, p, Q, nq, s_tot, col, 0ull, NULL, 0ull, 0ull);
             }
           if (!LIST)
-            { const uint64_t all = fe_wave_sum64(mine);
+            { const uint64_t all = wave_sum64(mine);
               if (lane == 0u)
                 { if (count != NULL) count[u0 + (uint64_t) from] = all < 0xffffffffull ? (uint32_t) all : 0xffffffffu;
                   if (room != NULL) room[u0 + (uint64_t) from] = (uint32_t) (all < cap ? all : cap);

@@ -21,7 +21,7 @@
 // from lane to lane, so the planes are read from the kernel argument with a lane's index (vector loads from the constant segment, once
 // a hit), and a wave whose hits have queries of both sizes runs both instances.
 // The packed bytes are read backwards, 8 at a time, from any byte offset and phase: the 8 bytes that END at the symbol's byte, and when
-// those would begin in front of the buffer its first 8 moved down (hs_be64_back, the mirror of fe_be64): nothing outside [0, in_bytes)
+// those would begin in front of the buffer its first 8 moved down (hs_be64_back, the mirror of be64_at): nothing outside [0, in_bytes)
 // is read.  Hit i writes start[i] and nothing else; the smallest index of a bad hit is kept by an atomicMin as the units' kernels keep
 // their bad unit's (units/dx_units.hpp), read back once a call.
 //

@@ -36,6 +36,10 @@
 // profiler's name table and are timed with events on the context's stream (tools/kmer_wide_rate.py).
 #include "units/dx_units.hpp"
 
+extern "C" {
+#include "dx_host.h"
+}
+
 #define KC_KMAX    32u
 #define KC_BATCH   1u                      // units a ticket at least
 #define KC_TARGET  (16u << 10)             // packed bytes a ticket
@@ -43,8 +47,6 @@
 #define KC_LANE    4u                      // chunks: a unit of up to so many is its lane's
 #define KC_GROUP   UNITS_GROUP             // chunks: up to here 16 lanes take the unit, beyond the wave
 #define KC_EVEN64  0x5555555555555555ull
-
-int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
 
 // ---------------------------------------------------------------------------------------------
 //  k_kc_windows
@@ -62,14 +64,6 @@ void k_kc_windows(const uint64_t *__restrict__ boff, const uint32_t *__restrict_
 // ---------------------------------------------------------------------------------------------
 //  k_kc_codes
 // ---------------------------------------------------------------------------------------------
-// the 8 bytes at byte o of the buffer as a word in the read's bit order (the first symbol on top); what lies behind the buffer's
-// end reads as zero, and the 8 bytes that would reach past it are its last 8, moved up (bytes >= 16)
-__device__ __forceinline__ uint64_t kc_be64(const uint8_t *in, uint64_t bytes, uint64_t o)
-{ if (o + 8u <= bytes) return __builtin_bswap64(*(const u64_u *) (in + o));
-  if (o >= bytes) return 0ull;
-  return __builtin_bswap64(*(const u64_u *) (in + (bytes - 8u))) << (8u * (uint32_t) (o + 8u - bytes));
-}
-
 // What a lane has of a unit in one chunk: n windows begin in it, the first at symbol `first` of the unit, and the three words are the
 // buffer from that window's first symbol on
 struct kc_part { uint64_t w0, w1, w2; uint32_t n, first; };
@@ -82,13 +76,8 @@ __device__ __forceinline__ kc_part kc_take(const uint8_t *in, uint64_t bytes, ui
   const uint32_t most = (uint32_t) (S1 - p0) - k + 1u;                        // windows from p0 on (a unit has fewer than 2^31 symbols)
   p.n = most < (uint32_t) (p1 - p0) ? most : (uint32_t) (p1 - p0);
   p.first = (uint32_t) (p0 - S0);
-  const u32x4    v    = last16_ask(in, bytes, a);
-  const uint32_t back = (uint32_t) (a - last16_from(a, bytes));              // 0, or how many bytes in front of a the 16 begin
-  const uint64_t h = __builtin_bswap64(v.x | ((uint64_t) v.y << 32)), l = __builtin_bswap64(v.z | ((uint64_t) v.w << 32));
   uint64_t w0, w1, w2;
-  if (back == 0u)      { w0 = h; w1 = l; w2 = kc_be64(in, bytes, a + 16u); }
-  else if (back < 8u)  { w0 = (h << (8u * back)) | (l >> (64u - 8u * back)); w1 = l << (8u * back); w2 = 0ull; }
-  else                 { w0 = l << (8u * (back - 8u)); w1 = 0ull; w2 = 0ull; }
+  chunk_words(in, bytes, a, w0, w1, w2);
   uint32_t s = (uint32_t) (p0 - 4u * a);                                       // the words move up to position p0
   if (s >= 32u) { w0 = w1; w1 = w2; w2 = 0ull; s -= 32u; }
   if (s)

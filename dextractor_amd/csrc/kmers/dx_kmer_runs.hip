@@ -38,7 +38,6 @@ extern "C" {
 #define KR_NONE  0xffffffffu
 #define KR_NMAX  (1ull << 36)
 
-int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
 
 struct kr_block_out { unsigned long long distinct, max_count, max_code; };       // a workgroup's: its runs, the longest, its smallest code
 

@@ -88,7 +88,6 @@ extern "C" {
 #define KM_TILE    2048u                   // cells a workgroup lists: 8 a thread
 #define KM_EVEN    0x55555555u
 
-int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
 
 // ---------------------------------------------------------------------------------------------
 //  k_kmers

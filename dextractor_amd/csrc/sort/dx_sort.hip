@@ -52,6 +52,10 @@
 #include "dx_internal.hpp"
 #include "dx_device.hpp"
 
+extern "C" {
+#include "dx_host.h"
+}
+
 #define SORT_BITS   8u
 #define SORT_DIGITS (1u << SORT_BITS)
 #define SORT_ITEMS  16u                               // keys a thread
@@ -60,8 +64,6 @@
 #define SORT_NMAX   (1ull << 36)
 
 static_assert(SORT_DIGITS == DX_BLOCK, "thread d of a workgroup owns digit d");
-
-int dx_scan_u32(dx_ctx *ctx, const uint32_t *d_in, uint64_t n, uint64_t *d_out, uint64_t *total);      // dx_qv.hip
 
 __device__ __forceinline__ uint32_t sort_digit(uint64_t key, uint32_t shift) { return (uint32_t) (key >> shift) & (SORT_DIGITS - 1u); }
 

@@ -87,6 +87,32 @@ __device__ __forceinline__ uint64_t last16_from(uint64_t a, uint64_t bytes) { re
 __device__ __forceinline__ u32x4 last16_ask(const uint8_t *in, uint64_t bytes, uint64_t a)
 { return *(const u32x4_u *) (in + last16_from(a, bytes)); }
 
+// the 8 bytes at byte o of the buffer (bytes >= 8) as a word in the read's bit order (the first symbol on top); what lies behind the
+// buffer's end reads as zero, and the 8 bytes that would reach past it are its last 8, moved up
+__device__ __forceinline__ uint64_t be64_at(const uint8_t *in, uint64_t bytes, uint64_t o)
+{ if (o + 8u <= bytes) return __builtin_bswap64(*(const u64_u *) (in + o));
+  if (o >= bytes) return 0ull;
+  return __builtin_bswap64(*(const u64_u *) (in + (bytes - 8u))) << (8u * (uint32_t) (o + 8u - bytes));
+}
+
+// the chunk whose place is byte a < bytes of the buffer (bytes >= 16) and the 8 bytes behind it, as three such words
+__device__ __forceinline__ void chunk_words(const uint8_t *in, uint64_t bytes, uint64_t a, uint64_t &w0, uint64_t &w1, uint64_t &w2)
+{ const u32x4    v    = last16_ask(in, bytes, a);
+  const uint32_t back = (uint32_t) (a - last16_from(a, bytes));              // 0, or how many bytes in front of a the 16 begin
+  const uint64_t h = __builtin_bswap64(v.x | ((uint64_t) v.y << 32)), l = __builtin_bswap64(v.z | ((uint64_t) v.w << 32));
+  if (back == 0u)      { w0 = h; w1 = l; w2 = be64_at(in, bytes, a + 16u); }
+  else if (back < 8u)  { w0 = (h << (8u * back)) | (l >> (64u - 8u * back)); w1 = l << (8u * back); w2 = 0ull; }
+  else                 { w0 = l << (8u * (back - 8u)); w1 = 0ull; w2 = 0ull; }
+}
+
+// the sum of a 64-bit value over the wave, in every lane
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
+{
+  #pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += (uint64_t) __shfl_xor((unsigned long long) v, d);
+  return v;
+}
+
 // ---- the call frame ------------------------------------------------------------------------------------------------
 // A frame's 64-bit words on the device: the ticket (2 x 32 bits: the counter, k_ticket_units' units a ticket), the smallest
 // index of a refused unit, 16 bytes for an input shorter than the kernel's loads, and the call's answer words behind them.

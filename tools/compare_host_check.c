@@ -11,7 +11,7 @@
  * Build (the library's host C files compiled here with the sanitizers, the device files' entry points taken from the library, which this
  * program never calls into):
  *     clang -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Idextractor_amd/csrc \
- *           tools/compare_host_check.c $(for f in dx_file_compare dx_file_check dx_file_qv dx_file_pack2 dx_files dx_host dx_walk_host dx_crew; \
+ *           tools/compare_host_check.c $(for f in dx_file_compare dx_file_u2 dx_file_check dx_file_qv dx_file_pack2 dx_files dx_host dx_walk_host dx_crew; \
  *           do echo dextractor_amd/csrc/$f.c; done) -Ldextractor_amd -ldexgpu -Wl,-rpath,$PWD/dextractor_amd -lpthread -lm -o compare_host_check
  */
 #include <inttypes.h>

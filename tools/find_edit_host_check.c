@@ -1,6 +1,6 @@
 /*
  * find_edit_host_check.c -- the host part of dx_file_find_edit (csrc/dx_file_find_edit.c: dxf_find_edit_plan; csrc/dx_file_find.c:
- * dxf_find_map; csrc/dx_file_check.c: dxf_u2_slice_end) run alone, without a device, for a build under the sanitizers: pattern
+ * dxf_find_map; csrc/dx_file_u2.c: dxf_u2_slice_end) run alone, without a device, for a build under the sanitizers: pattern
  * parsing and its refusals, the reverse complement, the query table, the slice plan for a list of budgets, and the mapping of a
  * slice's hits to records, patterns and strands.  The walk is the host's (ctx == NULL); what the device would list for a slice is
  * made here by the plain DP column and the valley rule over the image's packed reads, in the kernel's order (unit, pos, query).
@@ -15,7 +15,7 @@
  * Build (the library's host C files compiled here with the sanitizers, the device files' entry points taken from the library, which
  * this program never calls into):
  *     clang -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Idextractor_amd/csrc \
- *           tools/find_edit_host_check.c $(for f in dx_file_find_edit dx_file_find dx_file_check dx_file_qv dx_file_pack2 dx_files dx_host \
+ *           tools/find_edit_host_check.c $(for f in dx_file_find_edit dx_file_find dx_file_u2 dx_file_check dx_file_qv dx_file_pack2 dx_files dx_host \
  *           dx_walk_host dx_crew; do echo dextractor_amd/csrc/$f.c; done) -Ldextractor_amd -ldexgpu -Wl,-rpath,$PWD/dextractor_amd \
  *           -lpthread -lm -o find_edit_host_check
  */
