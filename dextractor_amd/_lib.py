@@ -117,7 +117,19 @@ class Kmers64(C.Structure):                      # dx_kmers64
     _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("distinct", C.c_uint64),
                 ("max_count", C.c_uint64), ("max_code", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
 
+class KmerSetInfo(C.Structure):                  # dx_set_info (dx_kmer_set_info fills it)
+    _fields_ = [("codes", C.c_uint64), ("device_bytes", C.c_uint64), ("k", C.c_uint32), ("canonical", C.c_uint32),
+                ("arrow", C.c_uint32), ("index_bits", C.c_uint32)]
+
+class Screen(C.Structure):                       # dx_screen
+    _fields_ = [("hits", C.c_uint32), ("covered", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32)]
+
+class ScreenReport(C.Structure):                 # dx_screen_report
+    _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64),
+                ("covered", C.c_uint64), ("records_hit", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
+DX_SCREEN_KEEP, DX_SCREEN_DROP = 0, 1
 DX_CUT_SPLIT, DX_CUT_LONGEST, DX_CUT_DROP = 0, 1, 2
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
@@ -275,6 +287,16 @@ SIGNATURES = {
                                      C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "dx_kmer_code64": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     "dx_kmer_letters64": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_char_p]),
+    "dx_kmer_set_from_codes": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dx_kmer_set_from_sorted": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dx_file_kmer_set": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(_P), C.POINTER(Kmers64)]),
+    "dx_kmer_set_info": (C.c_int, [_P, C.POINTER(KmerSetInfo)]),
+    "dx_kmer_set_codes": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "dx_kmer_set_free": (C.c_int, [_P, _P]),
+    "dx_code_kmer_screen": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64 * 4),
+                                      C.POINTER(C.c_uint64)]),
+    "dx_file_screen": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(ScreenReport), C.POINTER(_P), C.POINTER(_P)]),
+    "dx_screen_select": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

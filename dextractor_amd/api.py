@@ -964,6 +964,66 @@ class Context:
         finally:
             self.lib.dx_file_free(lst)
 
+    # ---- screen: the reads that share k-mers with a set ---------------------------------------------------
+    def kmer_set(self, kind, img: bytes, k, canonical=False, min_count=1, report=False):
+        """dx_file_kmer_set: the distinct k-mers (1 <= k <= 32) of a .dexta / .dexar image that are counted min_count times at least,
+        as a KmerSet on the device -- kmers_wide's route up to the sorted codes.  report: (set, what kmers_wide reports for the image)."""
+        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        h, km = C.c_void_p(), L.Kmers64()
+        self._chk(self.lib.dx_file_kmer_set(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), C.byref(h), C.byref(km)))
+        s = KmerSet(self, h)
+        return (s, {f: getattr(km, f) for f, _ in L.Kmers._fields_}) if report else s
+
+    def kmer_set_from_codes(self, codes, k, canonical=False, arrow=False):
+        """dx_kmer_set_from_codes: the KmerSet of the given 64-bit codes (any order, repeats allowed, none at all: the empty set); with
+        canonical each is folded to min(code, rc(code)) first.  api.kmer_code64 makes a code of letters."""
+        a = np.ascontiguousarray(np.asarray(codes, np.uint64))
+        h = C.c_void_p()
+        self._chk(self.lib.dx_kmer_set_from_codes(self.h, a.ctypes.data if len(a) else None, len(a), int(k), int(bool(canonical)),
+                                                  int(bool(arrow)), C.byref(h)))
+        return KmerSet(self, h)
+
+    def kmer_set_from_sorted(self, sorted_codes, n, k, min_count=1, canonical=False, arrow=False):
+        """dx_kmer_set_from_sorted: the KmerSet of the codes whose run in the sorted device array of n keys has min_count keys at least"""
+        h = C.c_void_p()
+        self._chk(self.lib.dx_kmer_set_from_sorted(self.h, _dev(sorted_codes)[0], int(n), int(min_count), int(k), int(bool(canonical)),
+                                                   int(bool(arrow)), C.byref(h)))
+        return KmerSet(self, h)
+
+    def code_kmer_screen(self, d_in, boff, beg, length, kset, out=None, in_bytes=None, n=None):
+        """dx_code_kmer_screen: unit j = symbols [beg[j], beg[j] + length[j]) of the packed read at d_in + boff[j] (beg None: whole
+        reads from symbol 0), against the KmerSet kset: per unit the windows that are in the set (hits), the symbols they cover, the
+        first and the last such window (2^32 - 1: none).  The arguments are device arrays as code_kmer_codes takes them; out: a
+        device array of n 16-byte entries (SCREEN_DTYPE), or None for the totals alone.  Returns the totals as a uint64 array:
+        windows, hits, covered, units with a hit.  Raises DexGPUError: DX_E_FORMAT (.bad_unit, .totals) for a unit outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        n = int(b_len // 4 if n is None else n)
+        tot, bad = (C.c_uint64 * 4)(), C.c_uint64()
+        rc = self.lib.dx_code_kmer_screen(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _dev(boff)[0], _dev(beg)[0], p_len,
+                                          n, kset.h if kset is not None else None, _dev(out)[0], C.byref(tot), C.byref(bad))
+        totals = np.array(list(tot), np.uint64)
+        if rc != 0:
+            e = self._bad_unit(rc, bad)
+            e.totals = totals
+            raise e
+        return totals
+
+    def screen(self, kind, img: bytes, kset):
+        """dx_file_screen: the records of a .dexta / .dexar image screened against the KmerSet kset -> (report: records, symbols,
+        windows, hits, covered, records_hit, k; rec: a SCREEN_DTYPE array, one entry a record; rec_len: every record's symbols).
+        api.screen_select turns (rec, rec_len) into the ids that Context.subset takes."""
+        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        rp, rec, rl = L.ScreenReport(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.dx_file_screen(self.h, kd, img, len(img), kset.h if kset is not None else None, C.byref(rp), C.byref(rec), C.byref(rl)))
+        try:
+            n = int(rp.records)
+            r = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint8)), (16 * n,)).view(SCREEN_DTYPE).copy() if n else np.zeros(0, SCREEN_DTYPE)
+            ln = np.ctypeslib.as_array(C.cast(rl, C.POINTER(C.c_uint32)), (n,)).copy() if n else np.zeros(0, np.uint32)
+            return {f: getattr(rp, f) for f, _ in L.ScreenReport._fields_ if f != "reserved"}, r, ln
+        finally:
+            self.lib.dx_file_free(rec); self.lib.dx_file_free(rl)
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -1195,6 +1255,59 @@ KMER_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u4"), ("letters", "S14"
 
 KMER64_DTYPE = np.dtype([("code", "<u8"), ("count", "<u8")])                                                      # dx_kmer64
 KMER64_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u8"), ("letters", "S32")])                            # Context.kmers_wide's list
+
+
+SCREEN_DTYPE = np.dtype([("hits", "<u4"), ("covered", "<u4"), ("first", "<u4"), ("last", "<u4")])                 # dx_screen
+
+
+class KmerSet:
+    """A dx_kmer_set: a set of k-mers on a Context's device (Context.kmer_set, .kmer_set_from_codes).  free() it, or use it as a
+    context manager, before the Context is closed."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+
+    @property
+    def info(self) -> dict:
+        """{"codes", "device_bytes", "k", "canonical", "arrow", "index_bits"}"""
+        i = L.KmerSetInfo()
+        self.ctx._chk(self.ctx.lib.dx_kmer_set_info(self.h, C.byref(i)))
+        return {f: int(getattr(i, f)) for f, _ in L.KmerSetInfo._fields_}
+
+    def codes(self) -> np.ndarray:
+        """the set's codes, ascending, as a uint64 array"""
+        out = np.zeros(self.info["codes"], np.uint64)
+        self.ctx._chk(self.ctx.lib.dx_kmer_set_codes(self.ctx.h, self.h, out.ctypes.data if len(out) else None, len(out)))
+        return out
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.dx_kmer_set_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+def screen_select(rec, rec_len, min_hits=1, min_permille=0, drop=False) -> np.ndarray:
+    """dx_screen_select: the records of Context.screen's answer that match -- hits >= max(min_hits, 1) and covered * 1000 >=
+    min_permille * length --, or with drop the others, ascending, as the uint64 ids Context.subset takes.  Host only."""
+    r = np.ascontiguousarray(np.asarray(rec, SCREEN_DTYPE))
+    ln = np.ascontiguousarray(np.asarray(rec_len, np.uint32))
+    if len(r) != len(ln):
+        raise L.DexGPUError(-1, "dx_screen_select: an entry and a length a record")
+    ids, n = C.c_void_p(), C.c_uint64()
+    rc = L.load().dx_screen_select(r.ctypes.data if len(r) else None, ln.ctypes.data if len(ln) else None, len(r), int(min_hits),
+                                   int(min_permille), L.DX_SCREEN_DROP if drop else L.DX_SCREEN_KEEP, C.byref(ids), C.byref(n))
+    if rc != 0:
+        raise L.DexGPUError(rc, "dx_screen_select: min_permille is 0 to 1000")
+    try:
+        return np.ctypeslib.as_array(C.cast(ids, C.POINTER(C.c_uint64)), (n.value,)).copy() if n.value else np.zeros(0, np.uint64)
+    finally:
+        L.load().dx_file_free(ids)
 
 
 def _dev(x):

@@ -15,7 +15,9 @@
  *     dx_file_find.c   where given sequences occur in an image's reads: dx_file_find
  *     dx_file_find_edit.c  ... within an edit distance: dx_file_find_edit, dx_file_find_edit_spans
  *     dx_file_kmers.c  the k-mers of an image's reads, counted: dx_file_kmers_add, dx_file_kmers; dx_kmer_code, dx_kmer_letters (host)
- *     dx_file_kmers_wide.c  ... for k up to 32, counted by sorting: dx_file_kmers_wide; dx_kmer_code64, dx_kmer_letters64 (host)
+ *     dx_file_kmers_wide.c  ... for k up to 32, counted by sorting: dx_file_kmers_wide; the same k-mers as a set on the device: dx_file_kmer_set;
+ *                      dx_kmer_code64, dx_kmer_letters64 (host)
+ *     dx_file_screen.c the records that share k-mers with a set: dx_file_screen; dx_screen_select (host)
  *     dx_file_cut.c    what is kept of the records once the occurrences are cut out, and the image of it: dx_hits_cut_plan (host), dx_file_cut
  *
  * A function that one of these files has for another carries the prefix dxf_ and is hidden: the library exports none of them.

@@ -45,6 +45,10 @@ __attribute__((visibility("hidden"))) int dx_cut_fail(dx_ctx *ctx, int code, con
 __attribute__((visibility("hidden"))) int dx_kmers_fail(dx_ctx *ctx, int code, const char *what);
 /* ... and "dx_file_kmers_wide: <what>", defined in kmers/dx_kmer_runs.hip, for dx_file_kmers_wide.c */
 __attribute__((visibility("hidden"))) int dx_kmers_wide_fail(dx_ctx *ctx, int code, const char *what);
+/* ... and "dx_file_kmer_set: <what>", defined in screen/dx_kmer_set.hip, for dx_file_kmers_wide.c, and "dx_file_screen: <what>", in
+   screen/dx_screen.hip, for dx_file_screen.c */
+__attribute__((visibility("hidden"))) int dx_kmer_set_fail(dx_ctx *ctx, int code, const char *what);
+__attribute__((visibility("hidden"))) int dx_screen_fail(dx_ctx *ctx, int code, const char *what);
 
 /* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
    arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their

@@ -34,19 +34,11 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in the
 // profiler's name table and are timed with events on the context's stream (tools/kmer_wide_rate.py).
-#include "units/dx_units.hpp"
+#include "kmers/dx_kmer_windows.hpp"
 
 extern "C" {
 #include "dx_host.h"
 }
-
-#define KC_KMAX    32u
-#define KC_BATCH   1u                      // units a ticket at least
-#define KC_TARGET  (16u << 10)             // packed bytes a ticket
-#define KC_CHUNK   64u                     // positions a chunk (16 packed bytes)
-#define KC_LANE    4u                      // chunks: a unit of up to so many is its lane's
-#define KC_GROUP   UNITS_GROUP             // chunks: up to here 16 lanes take the unit, beyond the wave
-#define KC_EVEN64  0x5555555555555555ull
 
 // ---------------------------------------------------------------------------------------------
 //  k_kc_windows
@@ -64,38 +56,6 @@ void k_kc_windows(const uint64_t *__restrict__ boff, const uint32_t *__restrict_
 // ---------------------------------------------------------------------------------------------
 //  k_kc_codes
 // ---------------------------------------------------------------------------------------------
-// What a lane has of a unit in one chunk: n windows begin in it, the first at symbol `first` of the unit, and the three words are the
-// buffer from that window's first symbol on
-struct kc_part { uint64_t w0, w1, w2; uint32_t n, first; };
-
-// the chunk at byte a < bytes of the buffer against the unit that is symbols [S0, S1) of the buffer; n == 0: no window begins here
-__device__ __forceinline__ kc_part kc_take(const uint8_t *in, uint64_t bytes, uint64_t a, uint64_t S0, uint64_t S1, uint32_t k)
-{ kc_part p = { 0ull, 0ull, 0ull, 0u, 0u };
-  const uint64_t p0 = S0 > 4u * a ? S0 : 4u * a, p1 = S1 < 4u * a + KC_CHUNK ? S1 : 4u * a + KC_CHUNK;
-  if (p1 <= p0 || S1 - p0 < k) return p;
-  const uint32_t most = (uint32_t) (S1 - p0) - k + 1u;                        // windows from p0 on (a unit has fewer than 2^31 symbols)
-  p.n = most < (uint32_t) (p1 - p0) ? most : (uint32_t) (p1 - p0);
-  p.first = (uint32_t) (p0 - S0);
-  uint64_t w0, w1, w2;
-  chunk_words(in, bytes, a, w0, w1, w2);
-  uint32_t s = (uint32_t) (p0 - 4u * a);                                       // the words move up to position p0
-  if (s >= 32u) { w0 = w1; w1 = w2; w2 = 0ull; s -= 32u; }
-  if (s)
-    { w0 = (w0 << (2u * s)) | (w1 >> (64u - 2u * s));
-      w1 = (w1 << (2u * s)) | (w2 >> (64u - 2u * s));
-      w2 <<= 2u * s;
-    }
-  p.w0 = w0; p.w1 = w1; p.w2 = w2;
-  return p;
-}
-
-// the reverse complement's code of the window that stands in the top 2 k bits of w: the bits reversed put symbol i at bits
-// 2 i + 1, 2 i with its two bits exchanged; they are exchanged back, complemented, and what stood below the window is masked off
-__device__ __forceinline__ uint64_t kc_rc(uint64_t w, uint32_t k)
-{ const uint64_t y = __builtin_bitreverse64(w);
-  return ~(((y >> 1) & KC_EVEN64) | ((y & KC_EVEN64) << 1)) & (k < 32u ? (1ull << (2u * k)) - 1u : ~0ull);
-}
-
 // the part's codes, one behind the other from out[0] on
 template <bool CANON>
 __device__ __forceinline__ void kc_write(const kc_part &p, uint32_t k, uint64_t *out)

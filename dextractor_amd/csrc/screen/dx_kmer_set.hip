@@ -1,0 +1,248 @@
+// dx_kmer_set.hip -- a set of k-mers that stays on the device, 1 <= k <= 32, for dx_code_kmer_screen (dx_screen.hip) to ask.
+//
+//   dx_kmer_set_from_sorted   a SORTED device array (what dx_sort_u64 leaves) -> the codes whose run has min_count keys at least
+//   dx_kmer_set_from_codes    host codes, any order, repeats allowed: folded (canonical), uploaded, sorted, then the above
+//   dx_kmer_set_info / _codes / _free
+//
+//   k_set_take    tile t (KS_TILE = 2048 keys): the first key of every run of min_count keys at least -- counted (the tile's word),
+//                 then, the places known from dx_scan_u32 of the counts, written to its place
+//   k_set_index   one thread a bucket: first[b] = the lower bound of b << (2 k - p) in the codes
+//
+// The set is n distinct codes in ascending order and a bucket index over the top p bits of the 2 k-bit code: first[0 .. 2^p], 32-bit
+// places, first[2^p] = n.  p is the smallest value with 2^p >= 2 n, so that a bucket holds half a code on the average and the
+// screen's look-up is two dependent loads and one compare; it is clamped to [1, min(2 k, 26)] (26: 256 MiB of index), beyond which
+// the buckets grow and the look-up searches them.  DEXGPU_TEST=set_bits=<p> forces p (clamped the same way) for a test.
+//
+// In a sorted array key i begins a run if i == 0 or key[i] != key[i - 1], and the run has min_count keys at least exactly if
+// key[i + min_count - 1] is there and equal to key[i]: no run is measured, and a run may be longer than any tile.  Nothing is placed
+// by an atomic cursor: the places come from the tiles' counts and a prefix sum, as in k_run_list, so the array is the same on every
+// call.  k_set_index has a thread a bucket and a binary search each; nothing races.
+//
+// Cost: 8 bytes read a key twice (the count, the take), 8 written a code, 4 a bucket and log2 n dependent loads for it; all of it once a
+// set, beside a sort of the same keys.  MEASURED with the codes and the sort of the sequence (profiles/screen_rate.txt, first call):
+// 1.2 ms for 4.8 x 10^4 codes, 6.1 ms for 5 x 10^6, 116 ms for 10^8 (six sort passes and 2^26 binary searches).
+//
+// This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in the
+// profiler's name table and are timed with events on the context's stream (tools/screen_rate.py).
+#include "dx_internal.hpp"
+#include "dx_device.hpp"
+#include "screen/dx_kmer_set.hpp"
+
+extern "C" {
+#include "dx_host.h"
+}
+
+#include <new>
+
+#define KS_KMAX  32u
+#define KS_ITEMS 8u                           // keys a thread
+#define KS_TILE  (DX_BLOCK * KS_ITEMS)        // keys a workgroup
+#define KS_SORTED_MAX (1ull << 36)            // keys of a sorted array (dx_sort_u64's and dx_kmer_runs' bound)
+
+// ---------------------------------------------------------------------------------------------
+//  k_set_take
+// ---------------------------------------------------------------------------------------------
+// WRITE false: pass[t] = the runs of min_count keys at least that begin in tile t.  WRITE true: their first keys to out, from
+// start[t] on (the exclusive sums of the counts), in the order of the keys.  (need = min_count - 1 < n.)
+template <bool WRITE>
+__global__ __launch_bounds__(DX_BLOCK)
+void k_set_take(const uint64_t *__restrict__ key, uint64_t n, uint64_t need, uint32_t *__restrict__ pass,
+                const uint64_t *__restrict__ start, uint64_t *__restrict__ out)
+{ __shared__ uint32_t s_n[DX_WAVES_PER_BLK];
+  const uint64_t i0 = (uint64_t) blockIdx.x * KS_TILE + (uint64_t) KS_ITEMS * threadIdx.x;
+  uint64_t v[KS_ITEMS];
+  bool     take[KS_ITEMS];
+  uint32_t mine = 0;
+  uint64_t prev = i0 && i0 < n ? key[i0 - 1u] : 0ull;
+  #pragma unroll
+  for (uint32_t j = 0; j < KS_ITEMS; j++)
+    { const uint64_t i = i0 + j;
+      const bool have = i < n;
+      v[j] = have ? key[i] : 0ull;
+      take[j] = have && (i == 0u || v[j] != prev) && need < n - i && (need == 0u || key[i + need] == v[j]);
+      mine += take[j] ? 1u : 0u;
+      prev = v[j];
+    }
+  const uint32_t incl = wave_incl_scan(mine), wave = threadIdx.x / DX_WAVE;
+  if (lane_id() == 63) s_n[wave] = incl;
+  __syncthreads();
+  if (!WRITE)
+    { if (threadIdx.x == 0u) pass[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+      return;
+    }
+  uint64_t at = start[blockIdx.x] + (incl - mine);
+  for (uint32_t w = 0; w < wave; w++) at += s_n[w];
+  #pragma unroll
+  for (uint32_t j = 0; j < KS_ITEMS; j++)
+    if (take[j]) out[at++] = v[j];
+}
+
+// ---------------------------------------------------------------------------------------------
+//  k_set_index
+// ---------------------------------------------------------------------------------------------
+// first[b], b = 0 .. 2^p: the codes in front of the first one >= b << shift (shift = 2 k - p < 64); first[2^p] = n
+__global__ __launch_bounds__(DX_BLOCK)
+void k_set_index(const uint64_t *__restrict__ code, uint32_t n, uint32_t bits, uint32_t shift, uint32_t *__restrict__ first)
+{ const uint64_t b = (uint64_t) blockIdx.x * DX_BLOCK + threadIdx.x, buckets = 1ull << bits;
+  if (b > buckets) return;
+  uint32_t lo = 0, hi = n;
+  if (b == buckets) lo = n;
+  else
+    { const uint64_t target = b << shift;
+      while (lo < hi)
+        { const uint32_t mid = lo + (hi - lo) / 2u;
+          if (code[mid] < target) lo = mid + 1u; else hi = mid;
+        }
+    }
+  first[b] = lo;
+}
+
+// ---------------------------------------------------------------------------------------------
+//  the entry points
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(dx_set_info) == 32, "dx_set_info is 32 bytes");
+
+// what every maker asks of k, canonical and arrow: in dxf_kmers_args' words
+static int ks_args(dx_ctx *ctx, const char *who, uint32_t k, int canonical, int arrow)
+{ if (canonical && arrow) return dx_fail(ctx, DX_E_ARG, "%s: canonical: pulse widths have no complement (DX_KIND_FASTA only)", who);
+  if (k < 1u || k > KS_KMAX) return dx_fail(ctx, DX_E_ARG, "%s: k = %u (1 to %u)", who, k, KS_KMAX);
+  return DX_OK;
+}
+
+// p for a set of n codes of 2 k bits: the smallest with 2^p >= 2 n, or what DEXGPU_TEST=set_bits says, in [1, min(2 k, KS_BITS_MAX)]
+static uint32_t ks_bits(uint64_t n, uint32_t k)
+{ const uint32_t most = 2u * k < KS_BITS_MAX ? 2u * k : KS_BITS_MAX;
+  long long p = 1;
+  while (p < 40 && (1ull << p) < 2u * n) p++;
+  p = dx_test_num("set_bits", p);
+  return p < 1 ? 1u : (p > (long long) most ? most : (uint32_t) p);
+}
+
+extern "C" int dx_kmer_set_free(dx_ctx *ctx, dx_kmer_set *set)
+{ if (ctx == NULL) return DX_E_ARG;
+  if (set == NULL) return DX_OK;
+  DX_HIP(ctx, hipSetDevice(ctx->device));
+  if (set->d_codes) (void) hipFree(set->d_codes);
+  if (set->d_first) (void) hipFree(set->d_first);
+  delete set;
+  return DX_OK;
+}
+
+extern "C" int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count, uint32_t k, int canonical,
+                                       int arrow, dx_kmer_set **set)
+{ const char *who = "dx_kmer_set_from_sorted";
+  if (ctx == NULL) return DX_E_ARG;
+  if (set == NULL) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
+  *set = NULL;
+  int rc = ks_args(ctx, who, k, canonical, arrow);
+  if (rc != DX_OK) return rc;
+  if (d_sorted == NULL && n) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
+  if (min_count < 1u) return dx_fail(ctx, DX_E_ARG, "%s: min_count 0 (1 at least: the unseen codes are in no set)", who);
+  if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
+  DX_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = dx_after_pending(ctx)) != DX_OK) return rc;
+
+  // the runs that pass, a tile: counted, and summed to every tile's first place
+  const uint64_t tiles = (n + KS_TILE - 1u) / KS_TILE, need = min_count - 1u;
+  uint64_t      *d_start = NULL, found = 0;
+  uint32_t      *d_pass = NULL;
+  if (n && need < n)
+    { if ((rc = dx_scratch(ctx, (tiles + 1u + (tiles + 1u) / 2u) * 8u, (void **) &d_start)) != DX_OK) return rc;
+      d_pass = (uint32_t *) (d_start + tiles + 1u);
+      hipLaunchKernelGGL(k_set_take<false>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, d_pass,
+                         (const uint64_t *) NULL, (uint64_t *) NULL);
+      DX_HIP(ctx, hipGetLastError());
+      if ((rc = dx_scan_u32(ctx, d_pass, tiles, d_start, &found)) != DX_OK) return rc;
+    }
+  if (found >= KS_NMAX)
+    return dx_fail(ctx, DX_E_ARG, "%s: %llu codes in the set (fewer than 2^32 - 1)", who, (unsigned long long) found);
+
+  dx_kmer_set *s = new (std::nothrow) dx_kmer_set();
+  if (s == NULL) return dx_fail(ctx, DX_E_NOMEM, "%s: out of memory", who);
+  s->k = k; s->canonical = canonical ? 1u : 0u; s->arrow = arrow ? 1u : 0u; s->n = found;
+  s->bits = ks_bits(found, k);
+  const uint64_t buckets = 1ull << s->bits;
+  s->device_bytes = found * 8u + (buckets + 1u) * 4u;
+  if ((rc = dx_malloc(ctx, (size_t) found * 8u + 64u, (void **) &s->d_codes)) != DX_OK ||
+      (rc = dx_malloc(ctx, (size_t) (buckets + 1u) * 4u + 64u, (void **) &s->d_first)) != DX_OK)
+    { (void) dx_kmer_set_free(ctx, s);                   // (dx_malloc has left the words)
+      return rc;
+    }
+  if (found)
+    hipLaunchKernelGGL(k_set_take<true>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, (uint32_t *) NULL,
+                       (const uint64_t *) d_start, s->d_codes);
+  hipLaunchKernelGGL(k_set_index, dim3((unsigned) ((buckets + 1u + DX_BLOCK - 1u) / DX_BLOCK)), dim3(DX_BLOCK), 0, ctx->stream,
+                     (const uint64_t *) s->d_codes, (uint32_t) found, s->bits, 2u * k - s->bits, s->d_first);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (the caller may free d_sorted; the scratch is free again)
+  if (e != hipSuccess)
+    { (void) dx_kmer_set_free(ctx, s);
+      return dx_fail(ctx, DX_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+  *set = s;
+  return DX_OK;
+}
+
+// the code of the reverse complement of a code of k symbols (host)
+static uint64_t ks_rc(uint64_t code, uint32_t k)
+{ uint64_t out = 0;
+  for (uint32_t i = 0; i < k; i++)
+    out = (out << 2) | (3u - ((code >> (2u * i)) & 3u));
+  return out;
+}
+
+extern "C" int dx_kmer_set_from_codes(dx_ctx *ctx, const uint64_t *codes, uint64_t n, uint32_t k, int canonical, int arrow,
+                                      dx_kmer_set **set)
+{ const char *who = "dx_kmer_set_from_codes";
+  if (ctx == NULL) return DX_E_ARG;
+  if (set == NULL) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
+  *set = NULL;
+  int rc = ks_args(ctx, who, k, canonical, arrow);
+  if (rc != DX_OK) return rc;
+  if (codes == NULL && n) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
+  if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu codes (fewer than 2^36)", who, (unsigned long long) n);
+  if (n == 0) return dx_kmer_set_from_sorted(ctx, NULL, 0, 1, k, canonical, arrow, set);
+
+  std::vector<uint64_t> own;
+  if (k < KS_KMAX)
+    for (uint64_t i = 0; i < n; i++)
+      if (codes[i] >> (2u * k))
+        return dx_fail(ctx, DX_E_ARG, "%s: code %llu has bits above its %u symbols", who, (unsigned long long) i, k);
+  if (canonical)
+    { own.assign(codes, codes + n);
+      for (uint64_t i = 0; i < n; i++)
+        { const uint64_t r = ks_rc(own[i], k);
+          if (r < own[i]) own[i] = r;
+        }
+      codes = own.data();
+    }
+  void *d_keys = NULL, *d_tmp = NULL;
+  if ((rc = dx_malloc(ctx, (size_t) n * 8u + 64u, &d_keys)) == DX_OK && (rc = dx_malloc(ctx, (size_t) n * 8u + 64u, &d_tmp)) == DX_OK &&
+      (rc = dx_h2d(ctx, d_keys, codes, (size_t) n * 8u)) == DX_OK &&
+      (rc = dx_sort_u64(ctx, (uint64_t *) d_keys, (uint64_t *) d_tmp, n, 2u * k)) == DX_OK)
+    rc = dx_kmer_set_from_sorted(ctx, (const uint64_t *) d_keys, n, 1, k, canonical, arrow, set);
+  if (d_keys) (void) dx_free(ctx, d_keys);
+  if (d_tmp) (void) dx_free(ctx, d_tmp);
+  return rc;
+}
+
+extern "C" int dx_kmer_set_info(const dx_kmer_set *set, dx_set_info *info)
+{ if (set == NULL || info == NULL) return DX_E_ARG;
+  info->codes = set->n; info->device_bytes = set->device_bytes;
+  info->k = set->k; info->canonical = set->canonical; info->arrow = set->arrow; info->index_bits = set->bits;
+  return DX_OK;
+}
+
+extern "C" int dx_kmer_set_codes(dx_ctx *ctx, const dx_kmer_set *set, uint64_t *out, uint64_t cap)
+{ if (ctx == NULL) return DX_E_ARG;
+  if (set == NULL || (out == NULL && cap)) return dx_fail(ctx, DX_E_ARG, "dx_kmer_set_codes: NULL pointer");
+  if (cap < set->n)
+    return dx_fail(ctx, DX_E_NOMEM, "dx_kmer_set_codes: %llu codes, and room for %llu", (unsigned long long) set->n, (unsigned long long) cap);
+  return dx_d2h(ctx, out, set->d_codes, (size_t) set->n * 8u);
+}
+
+// dx_host.h: dx_file_screen.c's refusals of dx_file_kmer_set, worded there
+extern "C" int dx_kmer_set_fail(dx_ctx *ctx, int code, const char *what)
+{ if (ctx == NULL) return code;
+  return dx_fail(ctx, code, "dx_file_kmer_set: %s", what);
+}

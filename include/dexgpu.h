@@ -1117,6 +1117,80 @@ int dx_kmer_code64(int arrow, const char *letters, uint32_t k, int canonical, ui
 int dx_kmer_letters64(int arrow, uint64_t code, uint32_t k, char *out /* k + 1 */);
 
 /* ------------------------------------------------------------------------------------------
+ *  screen: which reads share k-mers with a given sequence set  (undexta -U, a k-mer index on one core, dexta again today)
+ *          (csrc/screen/, csrc/dx_file_screen.c)
+ * ------------------------------------------------------------------------------------------ */
+/* A set of k-mers, 1 <= k <= 32, that stays on the device: its distinct codes in ascending order (compared unsigned) as 64-bit words
+ * and a bucket index over the top p bits of the 2 k-bit code, first[0 .. 2^p] of 32-bit places.  p (index_bits) is the smallest value
+ * with 2^p >= 2 codes, clamped to [1, min(2 k, 26)].  A set remembers k, canonical and arrow; it belongs to the context's device and
+ * is freed with dx_kmer_set_free before the context is closed.                                                                    */
+typedef struct dx_kmer_set dx_kmer_set;
+typedef struct { uint64_t codes, device_bytes; uint32_t k, canonical, arrow, index_bits; } dx_set_info;   /* 32 bytes; (dx_kmer_set_info is the call, as dx_qv_onepass_info is dx_onepass_info's) */
+
+/* The set of the n host codes, in any order, repeats allowed; n == 0 is the empty set.  With canonical every code is replaced by
+ * min(code, rc(code)) first, so the letters of either strand may be given (dx_kmer_code64 makes a code of letters).  The codes are
+ * uploaded, sorted (dx_sort_u64, bits = 2 k) and the distinct ones taken.  DX_E_ARG (dx_last_error says why) for k outside 1..32,
+ * canonical with arrow, a code with bits above 2 k (k < 32; the index is named), a NULL pointer that is needed, a set of 2^32 - 1 or
+ * more distinct codes (the count is named).  *set is NULL on any error.                                                          */
+int dx_kmer_set_from_codes(dx_ctx *ctx, const uint64_t *codes, uint64_t n, uint32_t k, int canonical, int arrow, dx_kmer_set **set);
+
+/* The set of the codes whose run in a SORTED device array of n keys (what dx_sort_u64 leaves) has min_count (>= 1) keys at least.
+ * The array is only read; places come from counts and a prefix sum, the same array on every call.  The refusals are the above and
+ * min_count 0, n >= 2^36.                                                                                                         */
+int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count, uint32_t k, int canonical, int arrow,
+                            dx_kmer_set **set);
+
+/* The set of the distinct k-mers of a .dexta / .dexar image that are counted min_count (>= 1) times at least: dx_file_kmers_wide's
+ * route up to the sorted array, then dx_kmer_set_from_sorted (arrow = the image's kind).  *out (may be NULL) is what
+ * dx_file_kmers_wide reports for the image.  The refusals and errors are dx_file_kmers_wide's, and min_count 0.                   */
+int dx_file_kmer_set(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count,
+                     dx_kmer_set **set, dx_kmers64 *out /* may be NULL */);
+
+int dx_kmer_set_info(const dx_kmer_set *set, dx_set_info *info);
+/* the codes back, ascending: out (host) has room for cap of them; DX_E_NOMEM when that is fewer than the set holds */
+int dx_kmer_set_codes(dx_ctx *ctx, const dx_kmer_set *set, uint64_t *out /* host */, uint64_t cap);
+int dx_kmer_set_free(dx_ctx *ctx, dx_kmer_set *set /* may be NULL */);
+
+/* Per unit: how many of its windows are in the set, and how much of it they cover.  16 bytes a unit.                              */
+typedef struct { uint32_t hits, covered, first, last; } dx_screen;
+
+/* Units are dx_code_kmer_codes' own: symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j], any byte offset,
+ * any phase; they may overlap or repeat; pad bits and foreign symbols are part of no window, and nothing outside [0, in_bytes) is
+ * read.  A window's code is made as dx_code_kmer_codes makes it, with the set's k and canonical.  For unit j: hits = the windows
+ * whose code is in the set; covered = the symbols of the unit that lie in one such window at least (the size of the union of the
+ * [p, p + k)); first and last = the smallest and the largest such p, UINT32_MAX when there is none.  d_out (n entries, 4-byte aligned;
+ * may be NULL) gets them; total[0 .. 4) (host) = the windows, the hits, the covered symbols and the units with a hit, over the good
+ * units.  A unit that does not lie inside the in_bytes gets {0, 0, UINT32_MAX, UINT32_MAX} and adds nothing; the smallest such j
+ * goes back in *bad_unit (UINT64_MAX otherwise; may be NULL) with DX_E_FORMAT, the others' entries and the totals are made all the
+ * same.  One read-back a call; the same bytes on every call.  DX_E_ARG for a NULL set or another pointer that is needed, n >= 2^31.  */
+int dx_code_kmer_screen(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                        const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                        const dx_kmer_set *set,
+                        dx_screen *d_out /* n entries; may be NULL */,
+                        uint64_t total[4] /* host: windows, hits, covered, units with a hit */,
+                        uint64_t *bad_unit /* may be NULL */);
+
+typedef struct { uint64_t records, symbols, windows, hits, covered, records_hit; uint32_t k, reserved; } dx_screen_report;   /* 56 bytes */
+
+/* The records of a .dexta / .dexar image (kind DX_KIND_FASTA or DX_KIND_ARROW; any key, legacy layout or byte order) screened against
+ * the set, where they lie: the image is walked on the host and goes up whole or, when it does not fit the device or exceeds
+ * DEXGPU_TEXT_BUDGET (bytes of image), in slices of whole records; the answer does not depend on the slicing.  *out = the sums;
+ * *rec (may be NULL; malloc'd, dx_file_free) one dx_screen a record, *rec_len (may be NULL; malloc'd) every record's symbols.
+ * DX_E_ARG (dx_last_error says why) for DX_KIND_QUIVA, an unknown kind, a set whose arrow is not the image's kind, a NULL pointer
+ * that is needed; else dx_file_unpack2's errors for the image.  *out is untouched on any error.                                   */
+int dx_file_screen(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const dx_kmer_set *set, dx_screen_report *out,
+                   dx_screen **rec /* may be NULL; malloc'd, dx_file_free; one a record */, uint32_t **rec_len /* may be NULL */);
+
+#define DX_SCREEN_KEEP 0   /* ids = the records that match */
+#define DX_SCREEN_DROP 1   /* ids = the others */
+/* Host only, no GPU: the records that dx_file_screen's answer selects.  A record matches when hits >= max(min_hits, 1) and
+ * covered * 1000 >= min_permille * len (64-bit products; a record of length 0 has no hit and never matches).  *ids (malloc'd,
+ * dx_file_free; *n_ids of them, ascending) goes to dx_file_subset unchanged -- for the .dexta, the .dexar and the .dexqv of the same
+ * records.  *n_ids == 0 is DX_OK here (dx_file_subset refuses it).  DX_E_ARG for min_permille > 1000, another mode, a NULL pointer.  */
+int dx_screen_select(const dx_screen *rec, const uint32_t *rec_len, uint64_t records, uint32_t min_hits, uint32_t min_permille,
+                     int mode, uint64_t **ids, uint64_t *n_ids);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
