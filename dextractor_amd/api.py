@@ -12,6 +12,121 @@ import numpy as np
 
 from . import _lib as L
 
+_NONE64 = 2**64 - 1                                           # the C-ABI's "no such unit / record / position"
+_KINDS = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}
+
+
+# ---- one definition for each idiom of the calls below ------------------------------------------
+def _kind(kind):
+    """"fasta", "arrow" or "quiva" -> DX_KIND_* (anything else: KeyError)"""
+    return _KINDS[kind]
+
+
+def _addr(x):
+    """a device array -> its address: a DevBuf, a DevView, a DeviceIndex._View or anything else with .ptr, or a torch tensor
+    (data_ptr()); None -> None, the C-ABI's NULL, which the library answers with DX_E_ARG where the array is not optional"""
+    if x is None:
+        return None
+    try:
+        return x.ptr
+    except AttributeError:
+        return x.data_ptr()
+
+
+def _need(x, name):
+    """_addr for an array whose entry point launches without a NULL check of its own: None is refused here"""
+    if x is None:
+        raise TypeError(f"{name}: a device array, not None")
+    return _addr(x)
+
+
+def _dev(x):
+    """a device array -> (its address, its bytes): a DevBuf, a DevView (bytes unknown: None), a torch tensor, or None"""
+    if x is None:
+        return None, 0
+    return _addr(x), x.numel() * x.element_size() if hasattr(x, "data_ptr") else getattr(x, "nbytes", None)
+
+
+def _words(lib, h):
+    """the library's words for the last failure of context h (None: of a call without a context)"""
+    return (lib.dx_last_error(h) or b"").decode()
+
+
+def _error(rc, text, **attrs):
+    """the DexGPUError of return code rc with `text` behind the code's name and attrs (bad_unit, line, ...) set on it"""
+    e = L.DexGPUError(rc, text)
+    e.__dict__.update(attrs)
+    return e
+
+
+def _index(word):
+    """a c_uint64 the library left an index in -> that index, or None when the word is all ones"""
+    return None if word.value == _NONE64 else word.value
+
+
+def _unit_pos(word):
+    """a c_uint64 of (unit << 32 | position) -> the pair, or None when the word is all ones"""
+    return None if word.value == _NONE64 else (word.value >> 32, word.value & 0xffffffff)
+
+
+class _Outs:
+    """k pointers for a call to leave malloc'd results in (C.byref of each), given back to the library (dx_file_free) on the way out,
+    whatever happened in between.  The library hands results over as its last step: after a call that failed they are all NULL."""
+
+    def __init__(self, lib, k):
+        self.lib, self.p = lib, [C.c_void_p() for _ in range(k)]
+
+    def __enter__(self):
+        return self.p
+
+    def __exit__(self, *a):
+        for p in self.p:
+            self.lib.dx_file_free(p)
+
+
+def _take(p, dtype, count, shape=None):
+    """a copy of the `count` dtype values at the library's pointer p, as `shape` (None: flat).  Not a byte behind them is read, and
+    with count 0 p is not read at all (it may be NULL): the result is empty, of that dtype and shape."""
+    dt = np.dtype(dtype)
+    if count:
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (count * dt.itemsize,)).view(dt).copy()
+    else:
+        a = np.zeros(0, dt)
+    return a if shape is None else a.reshape(shape)
+
+
+def _text(p, n):
+    """a copy of the n.value bytes at the library's pointer p"""
+    return C.string_at(p.value, n.value)
+
+
+def _fields(s, skip=("reserved",)):
+    """a C struct's fields as a dict, its padding word left out"""
+    return {f: getattr(s, f) for f, _ in s._fields_ if f not in skip}
+
+
+def _hist(hist=None):
+    """an L.HIST (uint64 [6][256]) holding `hist`, or zeros"""
+    h = L.HIST()
+    if hist is not None:
+        np.ctypeslib.as_array(h)[:] = np.asarray(hist, dtype=np.uint64).reshape(6, 256)
+    return h
+
+
+def _host_bytes(b):
+    """bytes, or a numpy array (a big image: no copy into a bytes object) -> (what ctypes passes as its const uint8_t *, its size);
+    the pointer made of an array keeps the array alive"""
+    if isinstance(b, np.ndarray):
+        b = np.ascontiguousarray(b, dtype=np.uint8)
+        return b.ctypes.data_as(C.c_void_p), b.size
+    return b, len(b)
+
+
+def _patterns(patterns):
+    """str or bytes patterns -> (the const char * array the file drivers take, how many)"""
+    pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
+    return (C.c_char_p * max(len(pats), 1))(*pats), len(pats)
+
 
 class DevView:
     """A pointer into a DevBuf (which stays the owner)."""
@@ -75,8 +190,7 @@ class DeviceIndex:
     def use(self, d_in):
         """dx_qv_use_dindex: the run-coded lines' groups this walk has noted go to the decoder (d_in: the stream's device
         address, as dx_qv_decode will get it); use(None) takes them back."""
-        self.ctx._chk(self.ctx.lib.dx_qv_use_dindex(self.ctx.h, d_in.ptr if d_in is not None else None,
-                                                    C.byref(self.x) if d_in is not None else None))
+        self.ctx._chk(self.ctx.lib.dx_qv_use_dindex(self.ctx.h, _addr(d_in), C.byref(self.x) if d_in is not None else None))
 
     def download(self):
         """-> dict of numpy arrays, as qv_walk returns them"""
@@ -102,7 +216,7 @@ class Context:
         h = C.c_void_p()
         rc = self.lib.dx_open(device, C.byref(h))
         if rc != 0:
-            raise L.DexGPUError(rc, (self.lib.dx_last_error(None) or b"").decode())
+            raise _error(rc, _words(self.lib, None))
         self.h = h
         self.device = device
 
@@ -117,9 +231,17 @@ class Context:
     def __exit__(self, *a):
         self.close()
 
+    def _err(self, rc, text="{}", **attrs):
+        """the DexGPUError of a call of this context that returned rc: `text` with the library's words for it in place of its {},
+        and attrs set on it"""
+        return _error(rc, text.format(_words(self.lib, self.h)), **attrs)
+
     def _chk(self, rc):
         if rc != 0:
-            raise L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
+            raise self._err(rc)
+
+    def _bad_unit(self, rc, bad):
+        return self._err(rc, bad_unit=_index(bad))
 
     # ---- memory ------------------------------------------------------------------------------
     def alloc(self, nbytes) -> DevBuf:
@@ -128,6 +250,13 @@ class Context:
     def to_device(self, arr) -> DevBuf:
         a = np.ascontiguousarray(arr)
         return DevBuf(self, a.nbytes).upload(a)
+
+    def _download(self, at, dtype, count):
+        """`count` dtype values from the device address `at`, as a numpy array"""
+        a = np.empty(count, dtype)
+        if a.nbytes:
+            self._chk(self.lib.dx_d2h(self.h, a.ctypes.data, at, a.nbytes))
+        return a
 
     def sync(self):
         self._chk(self.lib.dx_sync(self.h))
@@ -150,18 +279,18 @@ class Context:
 
     # ---- 2-bit packers -----------------------------------------------------------------------
     def pack2_encode(self, alphabet, d_text, d_off, d_tlen, d_nsym, n, d_hdr, d_hdr_off, d_out, d_out_off):
-        self._chk(self.lib.dx_pack2_encode(self.h, alphabet, d_text.ptr, d_off.ptr, d_tlen.ptr, d_nsym.ptr, n,
-                                           d_hdr.ptr if d_hdr else None, d_hdr_off.ptr if d_hdr_off else None,
-                                           d_out.ptr, d_out_off.ptr))
+        self._chk(self.lib.dx_pack2_encode(self.h, alphabet, _need(d_text, "d_text"), _need(d_off, "d_off"), _need(d_tlen, "d_tlen"),
+                                           _need(d_nsym, "d_nsym"), n, _addr(d_hdr), _addr(d_hdr_off), _need(d_out, "d_out"),
+                                           _need(d_out_off, "d_out_off")))
 
     def pack2_decode(self, letters, d_in, d_in_off, d_nsym, n, width, d_out, d_out_off):
-        self._chk(self.lib.dx_pack2_decode(self.h, letters, d_in.ptr, d_in_off.ptr, d_nsym.ptr, n, width,
-                                           d_out.ptr, d_out_off.ptr))
+        self._chk(self.lib.dx_pack2_decode(self.h, letters, _need(d_in, "d_in"), _need(d_in_off, "d_in_off"), _need(d_nsym, "d_nsym"),
+                                           n, width, _need(d_out, "d_out"), _need(d_out_off, "d_out_off")))
 
     # ---- QV coder ----------------------------------------------------------------------------
     @staticmethod
     def qv_batch(d_text, d_off, d_len, n, line_pad=1, text_bytes=0) -> L.QVBatch:
-        return L.QVBatch(d_text.ptr, d_off.ptr, d_len.ptr, n, text_bytes, line_pad)
+        return L.QVBatch(_need(d_text, "d_text"), _need(d_off, "d_off"), _need(d_len, "d_len"), n, text_bytes, line_pad)
 
     def qv_lossy_text(self, batch):
         """QV.c:1355-1372's rounding of the insertion / merge QVs, in place on the batch's device text."""
@@ -174,20 +303,14 @@ class Context:
 
     def qv_hist(self, batch, params, entry0=0, hist=None, tot=0):
         """Returns (hist uint64 [6,256], totChar); adds into `hist`/`tot` when given (shards)."""
-        h = L.HIST()
-        if hist is not None:
-            np.ctypeslib.as_array(h)[:] = hist
-        t = C.c_uint64(tot)
+        h, t = _hist(hist), C.c_uint64(tot)
         self._chk(self.lib.dx_qv_hist(self.h, C.byref(batch), entry0, C.byref(params), C.byref(h), C.byref(t)))
         return np.ctypeslib.as_array(h).reshape(6, 256).copy(), t.value
 
     def qv_scan(self, batch, entry0=0, params=None, hist=None, tot=0):
         """dx_qv_scan: qv_prescan + qv_hist with one wait on the device.  Returns (params, hist uint64 [6,256], totChar)."""
         p = params or L.QVParams(-1, -1, -1, -1)
-        h = L.HIST()
-        if hist is not None:
-            np.ctypeslib.as_array(h)[:] = hist
-        t = C.c_uint64(tot)
+        h, t = _hist(hist), C.c_uint64(tot)
         self._chk(self.lib.dx_qv_scan(self.h, C.byref(batch), entry0, C.byref(p), C.byref(h), C.byref(t)))
         return p, np.ctypeslib.as_array(h).reshape(6, 256).copy(), t.value
 
@@ -196,28 +319,25 @@ class Context:
 
     def qv_sizes(self, batch, d_hdr_off, d_seg, d_rec_off) -> int:
         tot = C.c_uint64()
-        self._chk(self.lib.dx_qv_sizes(self.h, C.byref(batch), d_hdr_off.ptr if d_hdr_off else None,
-                                       d_seg.ptr, d_rec_off.ptr, C.byref(tot)))
+        self._chk(self.lib.dx_qv_sizes(self.h, C.byref(batch), _addr(d_hdr_off), _need(d_seg, "d_seg"), _need(d_rec_off, "d_rec_off"),
+                                       C.byref(tot)))
         return tot.value
 
     def qv_encode(self, batch, d_hdr, d_hdr_off, d_rec_off, d_seg, d_out):
-        self._chk(self.lib.dx_qv_encode(self.h, C.byref(batch), d_hdr.ptr if d_hdr else None,
-                                        d_hdr_off.ptr if d_hdr_off else None, d_rec_off.ptr, d_seg.ptr,
-                                        d_out.ptr))
+        self._chk(self.lib.dx_qv_encode(self.h, C.byref(batch), _addr(d_hdr), _addr(d_hdr_off), _need(d_rec_off, "d_rec_off"),
+                                        _need(d_seg, "d_seg"), _need(d_out, "d_out")))
 
     def qv_encode_onepass(self, batch, d_hdr, d_hdr_off, d_seg, d_rec_off, d_out, out_cap) -> int:
         """dx_qv_encode_onepass: sizes, offsets and the record stream without a size pass; returns the total."""
         tot = C.c_uint64()
-        self._chk(self.lib.dx_qv_encode_onepass(self.h, C.byref(batch), d_hdr.ptr if d_hdr else None,
-                                                d_hdr_off.ptr if d_hdr_off else None, d_seg.ptr, d_rec_off.ptr,
-                                                d_out.ptr, out_cap, C.byref(tot)))
+        self._chk(self.lib.dx_qv_encode_onepass(self.h, C.byref(batch), _addr(d_hdr), _addr(d_hdr_off), _need(d_seg, "d_seg"),
+                                                _need(d_rec_off, "d_rec_off"), _need(d_out, "d_out"), out_cap, C.byref(tot)))
         return tot.value
 
     def qv_encode_onepass_begin(self, batch, d_hdr, d_hdr_off, d_seg, d_rec_off, d_out, out_cap):
         """dx_qv_encode_onepass_begin: queue the encode; the next batch's prescan / hist / build / set_coding may follow."""
-        self._chk(self.lib.dx_qv_encode_onepass_begin(self.h, C.byref(batch), d_hdr.ptr if d_hdr else None,
-                                                      d_hdr_off.ptr if d_hdr_off else None, d_seg.ptr, d_rec_off.ptr,
-                                                      d_out.ptr, out_cap))
+        self._chk(self.lib.dx_qv_encode_onepass_begin(self.h, C.byref(batch), _addr(d_hdr), _addr(d_hdr_off), _need(d_seg, "d_seg"),
+                                                      _need(d_rec_off, "d_rec_off"), _need(d_out, "d_out"), out_cap))
 
     def qv_encode_onepass_end(self) -> int:
         """dx_qv_encode_onepass_end: wait for the encode that has begun; returns the stream's size."""
@@ -227,15 +347,16 @@ class Context:
 
     def qv_decode(self, d_in, d_rec_off, d_hdr_off, d_seg, d_len, n, upper, d_out, d_out_off, flip=False):
         flags = (1 if upper else 0) | (2 if flip else 0)          # DX_DECODE_UPPER | DX_DECODE_FLIP
-        self._chk(self.lib.dx_qv_decode(self.h, d_in.ptr, d_rec_off.ptr, d_hdr_off.ptr if d_hdr_off else None,
-                                        d_seg.ptr, d_len.ptr, n, flags, d_out.ptr, d_out_off.ptr))
+        self._chk(self.lib.dx_qv_decode(self.h, _need(d_in, "d_in"), _need(d_rec_off, "d_rec_off"), _addr(d_hdr_off),
+                                        _need(d_seg, "d_seg"), _need(d_len, "d_len"), n, flags, _need(d_out, "d_out"),
+                                        _need(d_out_off, "d_out_off")))
 
     def qv_walk_device(self, d_img, nbytes, first, coding, newv=1, flip=0):
         """dx_qv_walk_device: the record walk of the bare stream at d_img on the device -> DeviceIndex (device arrays
         rec_off, hdr_off, seg, len, hdr4 as views that dx_qv_decode takes; .free() when done).  Raises DexGPUError
         (DX_E_MISMATCH) when the stream has to be walked on the host."""
         x = L.QVDIndex()
-        self._chk(self.lib.dx_qv_walk_device(self.h, d_img.ptr, nbytes, first, C.byref(coding), newv, flip, C.byref(x)))
+        self._chk(self.lib.dx_qv_walk_device(self.h, _need(d_img, "d_img"), nbytes, first, C.byref(coding), newv, flip, C.byref(x)))
         return DeviceIndex(self, x)
 
     def qv_walk_records_device(self, d_buf, nbytes, d_start, d_len, n, coding, d_seg, flip=False):
@@ -243,12 +364,11 @@ class Context:
         bytes, d_len[i] symbols a line) into d_seg (n x 5 uint32) -- with d_start as d_rec_off what qv_decode takes.  Raises
         DexGPUError (DX_E_FORMAT, .bad_entry = the first such i) when a record does not end inside the nbytes."""
         bad = C.c_uint64()
-        rc = self.lib.dx_qv_walk_records_device(self.h, d_buf.ptr, int(nbytes), d_start.ptr, d_len.ptr, int(n), C.byref(coding),
-                                                int(bool(flip)), d_seg.ptr, C.byref(bad))
+        rc = self.lib.dx_qv_walk_records_device(self.h, _need(d_buf, "d_buf"), int(nbytes), _need(d_start, "d_start"),
+                                                _need(d_len, "d_len"), int(n), C.byref(coding), int(bool(flip)),
+                                                _need(d_seg, "d_seg"), C.byref(bad))
         if rc != 0:
-            e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
-            e.bad_entry = bad.value if bad.value != 2**64 - 1 else None
-            raise e
+            raise self._err(rc, bad_entry=_index(bad))
 
     def entries_compress(self, lines_per_entry, lossy=False):
         """dx_entries_new / _add / _compress (QVcoding_Scan1 + Compress_Next_QVentry1 as a batch, what dex2DB writes into a
@@ -266,14 +386,10 @@ class Context:
                 if rc != 0:
                     raise L.DexGPUError(rc, "dx_entries_add")
             n = len(lines_per_entry)
-            coding, rec, nb, coff = L.QVCoding(), C.c_void_p(), C.c_size_t(), C.c_void_p()
-            self._chk(self.lib.dx_entries_compress(self.h, e, int(bool(lossy)), C.byref(coding), C.byref(rec), C.byref(nb), C.byref(coff)))
-            try:
-                records = C.string_at(rec.value, nb.value)
-                offs = np.ctypeslib.as_array(C.cast(coff, C.POINTER(C.c_uint64)), (n + 1,)).copy()
-            finally:
-                self.lib.dx_file_free(rec); self.lib.dx_file_free(coff)
-            return coding, records, offs
+            coding, nb = L.QVCoding(), C.c_size_t()
+            with _Outs(self.lib, 2) as (rec, coff):
+                self._chk(self.lib.dx_entries_compress(self.h, e, int(bool(lossy)), C.byref(coding), C.byref(rec), C.byref(nb), C.byref(coff)))
+                return coding, _text(rec, nb), _take(coff, np.uint64, n + 1)
         finally:
             self.lib.dx_entries_free(e)
 
@@ -291,32 +407,25 @@ class Context:
             if len(ids) and int(ids.max()) >= min(len(rlen), len(coff)):
                 raise IndexError("an id beyond the entries of coff / rlen")
             n_ids, idp = len(ids), ids.ctypes.data
-        if isinstance(records, np.ndarray):
-            records = np.ascontiguousarray(records, dtype=np.uint8)
-            rp, nb = records.ctypes.data_as(C.c_void_p), records.size
-        else:
-            rp, nb = records, len(records)
+        rp, nb = _host_bytes(records)
         if ids is None and len(coff) < n_ids:
             raise IndexError("fewer offsets than lengths")
-        out, n, toff = C.c_void_p(), C.c_size_t(), C.c_void_p()
-        self._chk(self.lib.dx_entries_uncompress(self.h, C.byref(coding), int(bool(flip)), rp, nb, coff.ctypes.data, rlen.ctypes.data,
-                                                 idp, n_ids, int(ascii), C.byref(out), C.byref(n), C.byref(toff)))
-        try:
-            return C.string_at(out.value, n.value), np.ctypeslib.as_array(C.cast(toff, C.POINTER(C.c_uint64)), (n_ids + 1,)).copy()
-        finally:
-            self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
+        n = C.c_size_t()
+        with _Outs(self.lib, 2) as (out, toff):
+            self._chk(self.lib.dx_entries_uncompress(self.h, C.byref(coding), int(bool(flip)), rp, nb, coff.ctypes.data, rlen.ctypes.data,
+                                                     idp, n_ids, int(ascii), C.byref(out), C.byref(n), C.byref(toff)))
+            return _text(out, n), _take(toff, np.uint64, n_ids + 1)
 
     def reads_unpack(self, letters, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_unpack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
         whole reads from symbol 0) as d_len[j] bytes of `letters` and one delimiter behind them at d_out + d_out_off[j].  Raises
         DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie inside the in_bytes."""
         bad = C.c_uint64()
-        rc = self.lib.dx_reads_unpack(self.h, int(letters), d_in.ptr, int(in_bytes), d_boff.ptr, d_beg.ptr if d_beg else None,
-                                      d_len.ptr, int(n), d_out.ptr, d_out_off.ptr, C.byref(bad))
+        rc = self.lib.dx_reads_unpack(self.h, int(letters), _need(d_in, "d_in"), int(in_bytes), _need(d_boff, "d_boff"), _addr(d_beg),
+                                      _need(d_len, "d_len"), int(n), _need(d_out, "d_out"), _need(d_out_off, "d_out_off"),
+                                      C.byref(bad))
         if rc != 0:
-            e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
-            e.bad_unit = bad.value if bad.value != 2**64 - 1 else None
-            raise e
+            raise self._bad_unit(rc, bad)
 
     @staticmethod
     def _reads_selection(boff, rlen, ids, beg, end):
@@ -355,132 +464,100 @@ class Context:
         boff, rlen, ids, beg, end, n_ids = self._reads_selection(boff, rlen, ids, beg, end)
         if not (L.DX_LETTERS_LOWER <= int(letters) <= L.DX_LETTERS_NUMBERS):
             raise ValueError("unknown letter set")
-        if isinstance(payload, np.ndarray):
-            payload = np.ascontiguousarray(payload, dtype=np.uint8)
-            pp, nb = payload.ctypes.data_as(C.c_void_p), payload.size
-        else:
-            pp, nb = payload, len(payload)
-        out, n, toff = C.c_void_p(), C.c_size_t(), C.c_void_p()
-        self._chk(self.lib.dx_reads_uncompress(self.h, int(letters), pp, nb, boff.ctypes.data, rlen.ctypes.data,
-                                               ids.ctypes.data if ids is not None else None,
-                                               beg.ctypes.data if beg is not None else None,
-                                               end.ctypes.data if end is not None else None, n_ids,
-                                               C.byref(out), C.byref(n), C.byref(toff)))
+        pp, nb = _host_bytes(payload)
+        n = C.c_size_t()
+        with _Outs(self.lib, 2) as (out, toff):
+            self._chk(self.lib.dx_reads_uncompress(self.h, int(letters), pp, nb, boff.ctypes.data, rlen.ctypes.data, _ptr(ids), _ptr(beg),
+                                                   _ptr(end), n_ids, C.byref(out), C.byref(n), C.byref(toff)))
+            return _text(out, n), _take(toff, np.uint64, n_ids + 1)
+
+    def _index_device(self, fn, args, dev, host):
+        """the two device indexers: fn(ctx, *args, the device arrays, &n, the header arrays, &prefix_len, &line, &code) ->
+        [the n values of each device array (its dtype in `dev`), the n x 4 of each malloc'd header array (`host`), prefix_len].  The
+        arrays are the caller's, so they are released here on every path once the call has succeeded."""
+        d, hd = [C.c_void_p() for _ in dev], [C.c_void_p() for _ in host]
+        cnt, pl, line, code = C.c_uint64(), C.c_size_t(), C.c_uint64(), C.c_int()
+        rc = fn(self.h, *args, *[C.byref(p) for p in d], C.byref(cnt), *[C.byref(p) for p in hd], C.byref(pl), C.byref(line),
+                C.byref(code))
+        if rc != 0:
+            raise _error(rc, f"line {line.value}: DX_IDX code {code.value}", line=line.value, idx_code=code.value)
         try:
-            return C.string_at(out.value, n.value), np.ctypeslib.as_array(C.cast(toff, C.POINTER(C.c_uint64)), (n_ids + 1,)).copy()
+            out = [self._download(p, dt, cnt.value) for p, dt in zip(d, dev)]
+            return out + [_take(p, dt, 4 * cnt.value, (cnt.value, 4)) for p, dt in zip(hd, host)] + [pl.value]
         finally:
-            self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
+            for p in d:
+                self.lib.dx_free(self.h, p)
+            for p in hd:
+                C.CDLL(None).free(p)
 
     def index_quiva_device(self, d_text, nbytes):
         """GPU text front end -> (off uint64, len uint32, hdr4 int32 [n,4], prefix_len); raises
         DexGPUError(DX_E_FORMAT) with .line / .idx_code on a malformed image."""
-        d_off, d_len, hdr = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        cnt, pl, line, code = C.c_uint64(), C.c_size_t(), C.c_uint64(), C.c_int()
-        rc = self.lib.dx_index_quiva_device(self.h, d_text.ptr, nbytes, C.byref(d_off), C.byref(d_len), C.byref(cnt),
-                                            C.byref(hdr), C.byref(pl), C.byref(line), C.byref(code))
-        if rc != 0:
-            e = L.DexGPUError(rc, f"line {line.value}: DX_IDX code {code.value}")
-            e.line, e.idx_code = line.value, code.value
-            raise e
-        n = cnt.value
-        off, ln = np.empty(n, np.uint64), np.empty(n, np.uint32)
-        if n:
-            self._chk(self.lib.dx_d2h(self.h, off.ctypes.data, d_off, n * 8))
-            self._chk(self.lib.dx_d2h(self.h, ln.ctypes.data, d_len, n * 4))
-            h4 = np.ctypeslib.as_array(C.cast(hdr, C.POINTER(C.c_int32)), (n, 4)).copy()
-            self.lib.dx_free(self.h, d_off); self.lib.dx_free(self.h, d_len)
-            C.CDLL(None).free(hdr)
-        else:
-            h4 = np.empty((0, 4), np.int32)
-        return off, ln, h4, pl.value
+        return tuple(self._index_device(self.lib.dx_index_quiva_device, (_need(d_text, "d_text"), nbytes), (np.uint64, np.uint32),
+                                        (np.int32,)))
 
     def index_seq_device(self, d_text, nbytes, arrow=False):
         """GPU text front end for .fasta/.arrow -> (off, tlen, nsym, hdr4, cnr4, prefix_len)."""
-        d_off, d_tl, d_ns, hdr, cnr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        cnt, pl, line, code = C.c_uint64(), C.c_size_t(), C.c_uint64(), C.c_int()
-        rc = self.lib.dx_index_seq_device(self.h, int(arrow), d_text.ptr, nbytes, C.byref(d_off), C.byref(d_tl),
-                                          C.byref(d_ns), C.byref(cnt), C.byref(hdr), C.byref(cnr), C.byref(pl),
-                                          C.byref(line), C.byref(code))
-        if rc != 0:
-            e = L.DexGPUError(rc, f"line {line.value}: DX_IDX code {code.value}")
-            e.line, e.idx_code = line.value, code.value
-            raise e
-        n = cnt.value
-        off, tl, ns = np.empty(n, np.uint64), np.empty(n, np.uint32), np.empty(n, np.uint32)
-        self._chk(self.lib.dx_d2h(self.h, off.ctypes.data, d_off, n * 8))
-        self._chk(self.lib.dx_d2h(self.h, tl.ctypes.data, d_tl, n * 4))
-        self._chk(self.lib.dx_d2h(self.h, ns.ctypes.data, d_ns, n * 4))
-        h4 = np.ctypeslib.as_array(C.cast(hdr, C.POINTER(C.c_int32)), (n, 4)).copy()
-        c4 = np.ctypeslib.as_array(C.cast(cnr, C.POINTER(C.c_uint16)), (n, 4)).copy()
-        for p_ in (d_off, d_tl, d_ns):
-            self.lib.dx_free(self.h, p_)
-        C.CDLL(None).free(hdr); C.CDLL(None).free(cnr)
-        return off, tl, ns, h4, c4, pl.value
+        return tuple(self._index_device(self.lib.dx_index_seq_device, (int(arrow), _need(d_text, "d_text"), nbytes),
+                                        (np.uint64, np.uint32, np.uint32), (np.int32, np.uint16)))
 
     def synth_quiva(self, seed, entry0, n, d_off, d_len, d_hdr4, d_lut, del_run, movie, d_text):
-        self._chk(self.lib.dx_synth_quiva(self.h, seed & 0xFFFFFFFF, entry0, n, d_off.ptr, d_len.ptr, d_hdr4.ptr,
-                                          d_lut.ptr, del_run, movie.encode(), d_text.ptr))
+        self._chk(self.lib.dx_synth_quiva(self.h, seed & 0xFFFFFFFF, entry0, n, _need(d_off, "d_off"), _need(d_len, "d_len"),
+                                          _need(d_hdr4, "d_hdr4"), _need(d_lut, "d_lut"), del_run, movie.encode(),
+                                          _need(d_text, "d_text")))
 
     # ---- whole-file drivers (what the CLI tools call) -------------------------------------------
-    def _file_call(self, fn, *args):
-        out, n = C.c_void_p(), C.c_size_t()
-        line, code = C.c_uint64(), C.c_int()
-        extra = () if fn in (self.lib.dx_file_unpack2, self.lib.dx_file_undexqv) else (C.byref(line), C.byref(code))
-        rc = fn(self.h, *args, C.byref(out), C.byref(n), *extra)
-        if rc != 0:
-            msg = (self.lib.dx_last_error(self.h) or b"").decode()
-            if rc == -3 and extra:
-                msg = f"line {line.value}: input rejected (DX_IDX code {code.value}) {msg}"
-            raise L.DexGPUError(rc, msg)
-        try:
-            return C.string_at(out.value, n.value)
-        finally:
-            self.lib.dx_file_free(out)
+    def _file_call(self, fn, *args, idx):
+        """fn(ctx, *args, &out, &n) -> the bytes it made; idx: the entry point indexes text, and reports (&line, &code) behind them"""
+        n, line, code = C.c_size_t(), C.c_uint64(), C.c_int()
+        with _Outs(self.lib, 1) as (out,):
+            rc = fn(self.h, *args, C.byref(out), C.byref(n), *((C.byref(line), C.byref(code)) if idx else ()))
+            if rc != 0:
+                raise self._err(rc, f"line {line.value}: input rejected (DX_IDX code {code.value}) {{}}" if rc == -3 and idx else "{}")
+            return _text(out, n)
 
     def dexta(self, fasta: bytes) -> bytes:
-        return self._file_call(self.lib.dx_file_pack2, 0, fasta, len(fasta))
+        return self._file_call(self.lib.dx_file_pack2, 0, fasta, len(fasta), idx=True)
 
     def dexar(self, arrow: bytes) -> bytes:
-        return self._file_call(self.lib.dx_file_pack2, 1, arrow, len(arrow))
+        return self._file_call(self.lib.dx_file_pack2, 1, arrow, len(arrow), idx=True)
 
     def undexta(self, img: bytes, upper=False, width=80) -> bytes:
         return self._file_call(self.lib.dx_file_unpack2, L.DX_LETTERS_UPPER if upper else L.DX_LETTERS_LOWER,
-                               img, len(img), width)
+                               img, len(img), width, idx=False)
 
     def undexar(self, img: bytes, width=80) -> bytes:
-        return self._file_call(self.lib.dx_file_unpack2, L.DX_LETTERS_ARROW, img, len(img), width)
+        return self._file_call(self.lib.dx_file_unpack2, L.DX_LETTERS_ARROW, img, len(img), width, idx=False)
 
     def dexqv(self, quiva: bytes, lossy=False) -> bytes:
-        return self._file_call(self.lib.dx_file_dexqv, quiva, len(quiva), int(lossy))
+        return self._file_call(self.lib.dx_file_dexqv, quiva, len(quiva), int(lossy), idx=True)
 
     def qv_use_index(self, d_in, d_seg, n, d_gidx, d_gidx_off, none=0):
         """dx_qv_use_index: a group index made elsewhere (qv_walk(index=True)) for the stream at d_in / d_seg; d_gidx None: take it back"""
-        self._chk(self.lib.dx_qv_use_index(self.h, d_in.ptr if d_in else None, d_seg.ptr if d_seg else None, n,
-                                           d_gidx.ptr if d_gidx else None, d_gidx_off.ptr if d_gidx_off else None, none))
+        self._chk(self.lib.dx_qv_use_index(self.h, _addr(d_in), _addr(d_seg), n, _addr(d_gidx), _addr(d_gidx_off), none))
 
     def undexqv(self, img: bytes, upper=False) -> bytes:
-        return self._file_call(self.lib.dx_file_undexqv, img, len(img), int(upper))
+        return self._file_call(self.lib.dx_file_undexqv, img, len(img), int(upper), idx=False)
 
     # ---- round-trip check --------------------------------------------------------------------------
     def verify_ranges(self, d_a, d_a_off, d_a_len, d_b, d_b_off, d_b_len, n, count=True):
         """dx_verify_ranges: (first differing unit or None, first differing byte in it, differing units -- None when count=False,
         which also lets the kernel skip what lies behind a difference already found)"""
         unit, pos, differ = C.c_uint64(), C.c_uint32(), C.c_uint64()
-        self._chk(self.lib.dx_verify_ranges(self.h, d_a.ptr, d_a_off.ptr, d_a_len.ptr, d_b.ptr, d_b_off.ptr, d_b_len.ptr, n,
+        self._chk(self.lib.dx_verify_ranges(self.h, _need(d_a, "d_a"), _need(d_a_off, "d_a_off"), _need(d_a_len, "d_a_len"),
+                                            _need(d_b, "d_b"), _need(d_b_off, "d_b_off"), _need(d_b_len, "d_b_len"), n,
                                             C.byref(unit), C.byref(pos), C.byref(differ) if count else None))
-        none = unit.value == 2**64 - 1
-        return (None if none else unit.value), pos.value, (differ.value if count else None)
+        return _index(unit), pos.value, (differ.value if count else None)
 
     def verify(self, kind, text: bytes, img: bytes, lossy=False) -> dict:
         """dx_file_verify: does img (a .dexta / .dexar / .dexqv image) give text back?  kind: "fasta", "arrow" or "quiva".  The
         report as a dict; `where` is one of _lib.VERIFY_WHERE, `error` the library's words when it is "IMAGE"."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
         rep = L.VerifyReport()
-        self._chk(self.lib.dx_file_verify(self.h, k, text, len(text), img, len(img), int(lossy), C.byref(rep)))
-        out = {f: getattr(rep, f) for f, _ in L.VerifyReport._fields_}
+        self._chk(self.lib.dx_file_verify(self.h, _kind(kind), text, len(text), img, len(img), int(lossy), C.byref(rep)))
+        out = _fields(rep)
         out["ok"], out["upper"], out["where"] = bool(rep.ok), bool(rep.upper), L.VERIFY_WHERE[rep.where]
         if out["where"] == "IMAGE":
-            out["error"] = (self.lib.dx_last_error(self.h) or b"").decode()
+            out["error"] = _words(self.lib, self.h)
         return out
 
     # ---- digest ------------------------------------------------------------------------------------
@@ -488,51 +565,39 @@ class Context:
         """dx_crc32_ranges: d_crc[j] = zlib's CRC-32 of d_buf[d_off[j] .. d_off[j] + d_len[j]) (offsets and lengths: uint64 on the
         device).  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie inside the buf_bytes."""
         bad = C.c_uint64()
-        rc = self.lib.dx_crc32_ranges(self.h, d_buf.ptr if d_buf else None, int(buf_bytes), d_off.ptr if d_off else None,
-                                      d_len.ptr if d_len else None, int(n), d_crc.ptr if d_crc else None, C.byref(bad))
+        rc = self.lib.dx_crc32_ranges(self.h, _addr(d_buf), int(buf_bytes), _addr(d_off), _addr(d_len), int(n), _addr(d_crc),
+                                      C.byref(bad))
         if rc != 0:
-            e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
-            e.bad_unit = bad.value if bad.value != 2**64 - 1 else None
-            raise e
+            raise self._bad_unit(rc, bad)
 
     def crc32_fold(self, d_crc, d_len, n):
         """dx_crc32_fold: (CRC-32, length) of the units' concatenation in index order, from their CRCs (uint32) and lengths (uint64)"""
         crc, nbytes = C.c_uint32(), C.c_uint64()
-        self._chk(self.lib.dx_crc32_fold(self.h, d_crc.ptr if d_crc else None, d_len.ptr if d_len else None, int(n),
-                                         C.byref(crc), C.byref(nbytes)))
+        self._chk(self.lib.dx_crc32_fold(self.h, _addr(d_crc), _addr(d_len), int(n), C.byref(crc), C.byref(nbytes)))
         return crc.value, nbytes.value
 
     def digest(self, kind, img: bytes, upper=False, width=80, per_record=False) -> dict:
         """dx_file_digest: the CRC-32 (zlib's) and size of the text undexta / undexar / undexqv writes for img with these options,
         decoded and hashed on the device.  kind: "fasta", "arrow" or "quiva".  {"crc32", "bytes", "records"}, and with per_record
         "rec_crc": every record's own CRC-32 (its header line included) as a uint32 array."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        dg, rec = L.Digest(), C.c_void_p()
-        self._chk(self.lib.dx_file_digest(self.h, k, img, len(img), int(bool(upper)), int(width), C.byref(dg),
-                                          C.byref(rec) if per_record else None))
-        out = {"crc32": dg.crc32, "bytes": dg.bytes, "records": dg.records}
-        if per_record:
-            try:
-                out["rec_crc"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), (dg.records + 1,))[:dg.records].copy()
-            finally:
-                self.lib.dx_file_free(rec)
+        dg = L.Digest()
+        with _Outs(self.lib, 1) as (rec,):
+            self._chk(self.lib.dx_file_digest(self.h, _kind(kind), img, len(img), int(bool(upper)), int(width), C.byref(dg),
+                                              C.byref(rec) if per_record else None))
+            out = {"crc32": dg.crc32, "bytes": dg.bytes, "records": dg.records}
+            if per_record:
+                out["rec_crc"] = _take(rec, np.uint32, dg.records)
         return out
 
     # ---- census ------------------------------------------------------------------------------------
-    def _bad_unit(self, rc, bad):
-        e = L.DexGPUError(rc, (self.lib.dx_last_error(self.h) or b"").decode())
-        e.bad_unit = bad.value if bad.value != 2**64 - 1 else None
-        return e
-
     def code_counts(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_counts=None):
         """dx_code_counts: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None: whole
         reads from symbol 0); d_counts (uint32, n x 4, or None) gets every unit's symbols code by code, the four totals over the
         call's units come back as a uint64 array.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does
         not lie inside the in_bytes."""
         tot, bad = (C.c_uint64 * 4)(), C.c_uint64()
-        rc = self.lib.dx_code_counts(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
-                                     d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n),
-                                     d_counts.ptr if d_counts else None, C.byref(tot), C.byref(bad))
+        rc = self.lib.dx_code_counts(self.h, _addr(d_in), int(in_bytes), _addr(d_boff), _addr(d_beg), _addr(d_len), int(n),
+                                     _addr(d_counts), C.byref(tot), C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
         return np.array(list(tot), dtype=np.uint64)
@@ -544,9 +609,8 @@ class Context:
         the buf_bytes or a kind that is not below nkinds."""
         nk = int(nkinds)
         hist, bad = np.zeros((max(nk, 1), 256), dtype=np.uint64), C.c_uint64()
-        rc = self.lib.dx_byte_hist_ranges(self.h, d_buf.ptr if d_buf else None, int(buf_bytes), d_off.ptr if d_off else None,
-                                          d_len.ptr if d_len else None, d_kind.ptr if d_kind else None, nk, int(n),
-                                          d_sum.ptr if d_sum else None, hist.ctypes.data, C.byref(bad))
+        rc = self.lib.dx_byte_hist_ranges(self.h, _addr(d_buf), int(buf_bytes), _addr(d_off), _addr(d_len), _addr(d_kind), nk, int(n),
+                                          _addr(d_sum), hist.ctypes.data, C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
         return hist
@@ -555,21 +619,17 @@ class Context:
         """dx_file_census: what the image holds, counted on the device (no text is made or downloaded).  kind: "fasta", "arrow" or
         "quiva".  {"records", "symbols", "min_len", "max_len", "n50", "code" (uint64[4]), "hist" (uint64[5, 256])}, and with
         per_record "rec_len" (uint32) and "rec_code" (uint32 [n, 4]; fasta, arrow) or "rec_sum" (uint64 [n, 5]; quiva)."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        cs, rl, rc_, rs = L.Census(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._chk(self.lib.dx_file_census(self.h, k, img, len(img), C.byref(cs), C.byref(rl) if per_record else None,
-                                          C.byref(rc_) if per_record else None, C.byref(rs) if per_record else None))
-        out = census_dict(cs)
-        if per_record:
-            n = cs.records
-            try:
-                out["rec_len"] = np.ctypeslib.as_array(C.cast(rl, C.POINTER(C.c_uint32)), (n + 1,))[:n].copy()
+        cs = L.Census()
+        with _Outs(self.lib, 3) as (rl, rc_, rs):
+            self._chk(self.lib.dx_file_census(self.h, _kind(kind), img, len(img), C.byref(cs), C.byref(rl) if per_record else None,
+                                              C.byref(rc_) if per_record else None, C.byref(rs) if per_record else None))
+            out, n = census_dict(cs), cs.records
+            if per_record:
+                out["rec_len"] = _take(rl, np.uint32, n)
                 if rc_.value:
-                    out["rec_code"] = np.ctypeslib.as_array(C.cast(rc_, C.POINTER(C.c_uint32)), (4 * n + 4,))[:4 * n].reshape(n, 4).copy()
+                    out["rec_code"] = _take(rc_, np.uint32, 4 * n, (n, 4))
                 if rs.value:
-                    out["rec_sum"] = np.ctypeslib.as_array(C.cast(rs, C.POINTER(C.c_uint64)), (5 * n + 5,))[:5 * n].reshape(n, 5).copy()
-            finally:
-                self.lib.dx_file_free(rl); self.lib.dx_file_free(rc_); self.lib.dx_file_free(rs)
+                    out["rec_sum"] = _take(rs, np.uint64, 5 * n, (n, 5))
         return out
 
     # ---- compare -----------------------------------------------------------------------------------
@@ -584,15 +644,13 @@ class Context:
         nk = int(nkinds)
         tally, first, bad = (L.DiffTally * max(nk, 1))(), C.c_uint64(), C.c_uint64()
         masks = None if a_and is None else (C.c_uint8 * max(nk, 1))(*[int(v) for v in a_and])
-        rc = self.lib.dx_diff_ranges(self.h, d_a.ptr if d_a else None, int(a_bytes), d_a_off.ptr if d_a_off else None,
-                                     d_b.ptr if d_b else None, int(b_bytes), d_b_off.ptr if d_b_off else None,
-                                     d_len.ptr if d_len else None, d_kind.ptr if d_kind else None, nk, masks, int(n),
-                                     d_differ.ptr if d_differ else None, d_first.ptr if d_first else None, tally,
+        rc = self.lib.dx_diff_ranges(self.h, _addr(d_a), int(a_bytes), _addr(d_a_off), _addr(d_b), int(b_bytes), _addr(d_b_off),
+                                     _addr(d_len), _addr(d_kind), nk, masks, int(n), _addr(d_differ), _addr(d_first), tally,
                                      C.byref(first), C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
         out = {f: np.array([getattr(t, f) for t in tally][:nk], dtype=np.uint64) for f, _ in L.DiffTally._fields_}
-        out["first"] = None if first.value == 2**64 - 1 else (first.value >> 32, first.value & 0xffffffff)
+        out["first"] = _unit_pos(first)
         return out
 
     def code_diff(self, d_a, a_bytes, d_a_boff, d_b, b_bytes, d_b_boff, d_len, n, d_differ=None, d_first=None) -> dict:
@@ -601,34 +659,52 @@ class Context:
         symbols.  {"symbols", "units", "first": (unit, symbol) or None}.  Raises DexGPUError (DX_E_FORMAT, .bad_unit) when a unit
         does not lie inside its side's bytes."""
         tot, first, bad = (C.c_uint64 * 2)(), C.c_uint64(), C.c_uint64()
-        rc = self.lib.dx_code_diff(self.h, d_a.ptr if d_a else None, int(a_bytes), d_a_boff.ptr if d_a_boff else None,
-                                   d_b.ptr if d_b else None, int(b_bytes), d_b_boff.ptr if d_b_boff else None,
-                                   d_len.ptr if d_len else None, int(n), d_differ.ptr if d_differ else None,
-                                   d_first.ptr if d_first else None, C.byref(tot), C.byref(first), C.byref(bad))
+        rc = self.lib.dx_code_diff(self.h, _addr(d_a), int(a_bytes), _addr(d_a_boff), _addr(d_b), int(b_bytes), _addr(d_b_boff),
+                                   _addr(d_len), int(n), _addr(d_differ), _addr(d_first), C.byref(tot), C.byref(first), C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
-        return {"symbols": tot[0], "units": tot[1],
-                "first": None if first.value == 2**64 - 1 else (first.value >> 32, first.value & 0xffffffff)}
+        return {"symbols": tot[0], "units": tot[1], "first": _unit_pos(first)}
 
     def compare(self, kind, a: bytes, b: bytes, lossy=False, per_record=False) -> dict:
         """dx_file_compare: how two images of one kind ("fasta", "arrow" or "quiva") differ, records paired by index, compared on the
         device without either text.  The fields of dx_compare as a dict -- `same` a bool, the first_* None when there is none, the
         per-line fields uint64 arrays of `lines` values -- and with per_record "rec_differ": uint32 [records compared, lines].
         lossy (quiva): side a's insertion and merge lines are masked as dexqv -l rounds them."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        cm, rec = L.Compare(), C.c_void_p()
-        self._chk(self.lib.dx_file_compare(self.h, k, a, len(a), b, len(b), int(bool(lossy)), C.byref(cm),
-                                           C.byref(rec) if per_record else None))
-        out = compare_dict(cm)
-        if per_record:
-            n, ln = min(cm.records_a, cm.records_b), cm.lines
-            try:
-                out["rec_differ"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), ((n + 1) * ln,))[:n * ln].reshape(n, ln).copy()
-            finally:
-                self.lib.dx_file_free(rec)
+        cm = L.Compare()
+        with _Outs(self.lib, 1) as (rec,):
+            self._chk(self.lib.dx_file_compare(self.h, _kind(kind), a, len(a), b, len(b), int(bool(lossy)), C.byref(cm),
+                                               C.byref(rec) if per_record else None))
+            out = compare_dict(cm)
+            if per_record:
+                n, ln = min(cm.records_a, cm.records_b), cm.lines
+                out["rec_differ"] = _take(rec, np.uint32, n * ln, (n, ln))
         return out
 
     # ---- find --------------------------------------------------------------------------------------
+    def _listed(self, call, cap, dtype, d_list=None):
+        """the scheme of the listing calls: call(address of a device list of `cap` 16-byte entries) -> how many there were to list;
+        the list is d_list, or with None made and freed here (cap 0: none, NULL).  Returns the first min(cap, found) entries."""
+        own = self.alloc(16 * cap + 16) if d_list is None and cap > 0 else None
+        try:
+            at = _addr(own if own is not None else d_list)
+            return self._download(at, dtype, min(cap, call(at)))
+        finally:
+            if own is not None:
+                own.free()
+
+    def _code_find(self, fn, q, nq, d_in, in_bytes, d_boff, d_beg, d_len, n, d_count, cap, d_hits):
+        """dx_code_find / dx_code_find_edit: one argument list, one answer; q: the nq queries as the entry point's array"""
+        cap, tot, hits, bad = int(cap), (C.c_uint64 * max(nq, 1))(), C.c_uint64(), C.c_uint64()
+
+        def call(p_hits):
+            rc = fn(self.h, _addr(d_in), int(in_bytes), _addr(d_boff), _addr(d_beg), _addr(d_len), int(n), q, nq, _addr(d_count),
+                    p_hits, cap, tot, C.byref(hits), C.byref(bad))
+            if rc != 0:
+                raise self._bad_unit(rc, bad)
+            return hits.value
+        lst = self._listed(call, cap, HIT_DTYPE, d_hits)
+        return {"hits": hits.value, "total": np.array(list(tot)[:nq], dtype=np.uint64)}, lst
+
     def code_find(self, d_in, in_bytes, d_boff, d_beg, d_len, n, queries, d_count=None, cap=0, d_hits=None):
         """dx_code_find: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None: whole
         reads from symbol 0); queries: (code, len, max_mis) triples, symbol i of a query in bits 2 (len - 1 - i) + 1, 2 (len - 1 - i)
@@ -636,25 +712,9 @@ class Context:
         ({"hits": all of them, "total": uint64 a query}, the first min(cap, hits) hits in the order (unit, pos, query) as a
         HIT_DTYPE array).  Raises DexGPUError (DX_E_FORMAT,
         .bad_unit = the first such j) when a unit does not lie inside the in_bytes."""
-        nq, cap = len(queries), int(cap)
+        nq = len(queries)
         q = (L.Query * max(nq, 1))(*[L.Query(int(c), int(m), int(x)) for c, m, x in queries])
-        tot, hits, bad = (C.c_uint64 * max(nq, 1))(), C.c_uint64(), C.c_uint64()
-        own = d_hits is None and cap > 0
-        if own:
-            d_hits = self.alloc(16 * cap + 16)
-        try:
-            rc = self.lib.dx_code_find(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
-                                       d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), q, nq,
-                                       d_count.ptr if d_count else None, d_hits.ptr if d_hits else None, cap, tot,
-                                       C.byref(hits), C.byref(bad))
-            if rc != 0:
-                raise self._bad_unit(rc, bad)
-            k = min(cap, hits.value)
-            lst = d_hits.download(np.uint8, 16 * k).view(HIT_DTYPE) if k else np.zeros(0, HIT_DTYPE)
-        finally:
-            if own:
-                d_hits.free()
-        return {"hits": hits.value, "total": np.array(list(tot)[:nq], dtype=np.uint64)}, lst
+        return self._code_find(self.lib.dx_code_find, q, nq, d_in, in_bytes, d_boff, d_beg, d_len, n, d_count, cap, d_hits)
 
     def find(self, kind, img: bytes, patterns, max_mismatches=0, both_strands=False, max_hits=1 << 20, per_record=False):
         """dx_file_find: where the patterns (str, 1 to 32 letters: acgtACGT for "fasta", 1234 for "arrow") occur in the reads of the
@@ -664,25 +724,20 @@ class Context:
         strand) as a HIT_DTYPE array, `query` being the pattern's index)."""
         return self._file_find(self.lib.dx_file_find, kind, img, patterns, max_mismatches, both_strands, max_hits, per_record)
 
-    def _file_find(self, fn, kind, img, patterns, bound, both_strands, max_hits, per_record):
-        """dx_file_find / dx_file_find_edit: one argument list, one report"""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
-        arr = (C.c_char_p * max(len(pats), 1))(*pats)
-        fd, lst, rec = L.Find(), C.c_void_p(), C.c_void_p()
-        self._chk(fn(self.h, k, img, len(img), arr, len(pats), int(bound), int(bool(both_strands)),
-                     int(max_hits), C.byref(fd), C.byref(lst), C.byref(rec) if per_record else None))
-        try:
+    def _file_find(self, fn, kind, img, patterns, bound, both_strands, max_hits, per_record, spans=False):
+        """dx_file_find / dx_file_find_edit / (spans) dx_file_find_edit_spans: one argument list, one report"""
+        k, (arr, npat), fd = _kind(kind), _patterns(patterns), L.Find()
+        with _Outs(self.lib, 4) as (lst, rec, st, rl):
+            self._chk(fn(self.h, k, img, len(img), arr, npat, int(bound), int(bool(both_strands)), int(max_hits), C.byref(fd),
+                         C.byref(lst), C.byref(rec) if per_record else None, *((C.byref(st), C.byref(rl)) if spans else ())))
             out = {"records": fd.records, "records_hit": fd.records_hit, "hits": fd.hits, "listed": fd.listed,
-                   "per_pattern": np.array([[fd.per_pattern[p][0], fd.per_pattern[p][1]] for p in range(len(pats))],
-                                           dtype=np.uint64).reshape(len(pats), 2)}
-            hits = np.zeros(0, HIT_DTYPE)
-            if fd.listed:
-                hits = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * fd.listed,)).view(HIT_DTYPE).copy()
+                   "per_pattern": np.array([[fd.per_pattern[p][0], fd.per_pattern[p][1]] for p in range(npat)],
+                                           dtype=np.uint64).reshape(npat, 2)}
+            hits = _take(lst, HIT_DTYPE, fd.listed)
+            if spans:
+                out["start"], out["rec_len"] = _take(st, np.uint32, fd.listed), _take(rl, np.uint32, fd.records)
             if per_record:
-                out["rec_hits"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), (fd.records + 1,))[:fd.records].copy()
-        finally:
-            self.lib.dx_file_free(lst); self.lib.dx_file_free(rec)
+                out["rec_hits"] = _take(rec, np.uint32, fd.records)
         return out, hits
 
     # ---- find with indels ----------------------------------------------------------------------------
@@ -692,25 +747,9 @@ class Context:
         end e with c(e) <= k, c(e) < c(e - 1) and c(e) <= c(e + 1), c being the semi-global edit distance capped at k + 1: one hit for
         each valley of the distance, at the leftmost end of its floor; pos = e, the exclusive end of the occurrence, mis = the
         distance.  Returns what code_find returns, in the same order (unit, pos, query)."""
-        nq, cap = len(queries), int(cap)
+        nq = len(queries)
         q = (L.EQuery * max(nq, 1))(*[equery(*x) for x in queries])
-        tot, hits, bad = (C.c_uint64 * max(nq, 1))(), C.c_uint64(), C.c_uint64()
-        own = d_hits is None and cap > 0
-        if own:
-            d_hits = self.alloc(16 * cap + 16)
-        try:
-            rc = self.lib.dx_code_find_edit(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
-                                            d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), q, nq,
-                                            d_count.ptr if d_count else None, d_hits.ptr if d_hits else None, cap, tot,
-                                            C.byref(hits), C.byref(bad))
-            if rc != 0:
-                raise self._bad_unit(rc, bad)
-            k = min(cap, hits.value)
-            lst = d_hits.download(np.uint8, 16 * k).view(HIT_DTYPE) if k else np.zeros(0, HIT_DTYPE)
-        finally:
-            if own:
-                d_hits.free()
-        return {"hits": hits.value, "total": np.array(list(tot)[:nq], dtype=np.uint64)}, lst
+        return self._code_find(self.lib.dx_code_find_edit, q, nq, d_in, in_bytes, d_boff, d_beg, d_len, n, d_count, cap, d_hits)
 
     def find_edit(self, kind, img: bytes, patterns, max_errors=0, both_strands=False, max_hits=1 << 20, per_record=False):
         """dx_file_find_edit: where the patterns (str, 1 to 64 letters) END in the reads of the image within max_errors edits
@@ -729,51 +768,27 @@ class Context:
         nq, n_hits = len(queries), int(n_hits)
         q = (L.EQuery * max(nq, 1))(*[equery(*x) for x in queries])
         bad = C.c_uint64()
-        own = d_start is None and n_hits > 0
-        if own:
-            d_start = self.alloc(4 * n_hits + 16)
+        own = self.alloc(4 * n_hits + 16) if d_start is None and n_hits > 0 else None
         try:
-            rc = self.lib.dx_code_hit_starts(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
-                                             d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), q, nq,
-                                             d_hits.ptr if d_hits else None, n_hits, d_start.ptr if d_start else None, C.byref(bad))
+            at = _addr(own if own is not None else d_start)
+            rc = self.lib.dx_code_hit_starts(self.h, _addr(d_in), int(in_bytes), _addr(d_boff), _addr(d_beg), _addr(d_len), int(n), q, nq,
+                                             _addr(d_hits), n_hits, at, C.byref(bad))
             starts = None
-            if rc in (0, -3) and n_hits and d_start is not None and n_hits < 2**32:
-                starts = d_start.download(np.uint32, n_hits)
+            if rc in (0, -3) and n_hits and at is not None and n_hits < 2**32:
+                starts = self._download(at, np.uint32, n_hits)
             if rc != 0:
-                e = self._bad_unit(rc, bad)
-                e.starts = starts
-                raise e
+                raise self._err(rc, bad_unit=_index(bad), starts=starts)
         finally:
-            if own:
-                d_start.free()
+            if own is not None:
+                own.free()
         return starts if starts is not None else np.zeros(0, np.uint32)
 
     def find_spans(self, kind, img: bytes, patterns, max_errors=0, both_strands=False, max_hits=1 << 20, per_record=False):
         """dx_file_find_edit_spans: find_edit's return -- the same report, the same hits -- and in the report "start": uint32, one a
         listed hit, the first symbol of its occurrence on the read as stored (the occurrence is the record's symbols [start, pos)),
         and "rec_len": uint32 a record, its symbols."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
-        arr = (C.c_char_p * max(len(pats), 1))(*pats)
-        fd, lst, rec, st, rl = L.Find(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._chk(self.lib.dx_file_find_edit_spans(self.h, k, img, len(img), arr, len(pats), int(max_errors), int(bool(both_strands)),
-                                                   int(max_hits), C.byref(fd), C.byref(lst), C.byref(rec) if per_record else None,
-                                                   C.byref(st), C.byref(rl)))
-        try:
-            out = {"records": fd.records, "records_hit": fd.records_hit, "hits": fd.hits, "listed": fd.listed,
-                   "per_pattern": np.array([[fd.per_pattern[p][0], fd.per_pattern[p][1]] for p in range(len(pats))],
-                                           dtype=np.uint64).reshape(len(pats), 2)}
-            hits, out["start"] = np.zeros(0, HIT_DTYPE), np.zeros(0, np.uint32)
-            if fd.listed:
-                hits = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * fd.listed,)).view(HIT_DTYPE).copy()
-                out["start"] = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint32)), (fd.listed,)).copy()
-            out["rec_len"] = np.ctypeslib.as_array(C.cast(rl, C.POINTER(C.c_uint32)), (fd.records + 1,))[:fd.records].copy()
-            if per_record:
-                out["rec_hits"] = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint32)), (fd.records + 1,))[:fd.records].copy()
-        finally:
-            for p in (lst, rec, st, rl):
-                self.lib.dx_file_free(p)
-        return out, hits
+        return self._file_find(self.lib.dx_file_find_edit_spans, kind, img, patterns, max_errors, both_strands, max_hits, per_record,
+                               spans=True)
 
     def cut(self, kind, img: bytes, patterns, max_errors=0, both_strands=False, min_len=0, mode="split"):
         """dx_file_cut: the image ("fasta" or "arrow") with the occurrences of the patterns within max_errors edits cut out of its
@@ -782,18 +797,13 @@ class Context:
         such piece of a record, on a tie the first) or "drop" (only the records without an occurrence, whole).  Returns (image,
         report, selection): the report is cut_plan's, and the selection {"ids", "beg", "end"} is what Context.subset takes to cut the
         .dexar and the .dexqv of the same records in the same places."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
-        arr = (C.c_char_p * max(len(pats), 1))(*pats)
-        out, ln, cut, n = C.c_void_p(), C.c_size_t(), L.Cut(), C.c_uint64()
-        sel = [C.c_void_p() for _ in range(3)]
-        self._chk(self.lib.dx_file_cut(self.h, k, img, len(img), arr, len(pats), int(max_errors), int(bool(both_strands)), int(min_len),
-                                       _cut_mode(mode), C.byref(out), C.byref(ln), C.byref(cut), *[C.byref(a) for a in sel], C.byref(n)))
-        try:
-            return C.string_at(out.value, ln.value), cut_dict(cut), _cut_selection(sel, n.value)
-        finally:
-            for p in [out] + sel:
-                self.lib.dx_file_free(p)
+        k, (arr, npat) = _kind(kind), _patterns(patterns)
+        ln, cut, n = C.c_size_t(), L.Cut(), C.c_uint64()
+        with _Outs(self.lib, 4) as (out, *sel):
+            self._chk(self.lib.dx_file_cut(self.h, k, img, len(img), arr, npat, int(max_errors), int(bool(both_strands)),
+                                           int(min_len), _cut_mode(mode), C.byref(out), C.byref(ln), C.byref(cut),
+                                           *[C.byref(a) for a in sel], C.byref(n)))
+            return _text(out, ln), cut_dict(cut), _cut_selection(sel, n.value)
 
     # ---- k-mers ------------------------------------------------------------------------------------
     def code_kmers(self, d_in, boff, beg, length, k, canonical=False, table=None, in_bytes=None, n=None):
@@ -812,8 +822,8 @@ class Context:
             table = torch.zeros(4 ** k, dtype=torch.int64, device=f"cuda:{self.device}")
             torch.cuda.synchronize(self.device)                   # (zeroed on torch's stream, counted into on the context's)
         win, bad = C.c_uint64(), C.c_uint64()
-        rc = self.lib.dx_code_kmers(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _dev(boff)[0], _dev(beg)[0], p_len,
-                                    int(b_len // 4 if n is None else n), k, int(bool(canonical)), _dev(table)[0], C.byref(win),
+        rc = self.lib.dx_code_kmers(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                    int(b_len // 4 if n is None else n), k, int(bool(canonical)), _addr(table), C.byref(win),
                                     C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
@@ -825,7 +835,7 @@ class Context:
         count}; nspec None or 0: no spectrum."""
         spec = np.zeros(int(nspec), np.uint64) if nspec else None
         d, m, mc = C.c_uint64(), C.c_uint64(), C.c_uint32()
-        self._chk(self.lib.dx_kmer_spectrum(self.h, _dev(table)[0], int(k), spec.ctypes.data if spec is not None else None,
+        self._chk(self.lib.dx_kmer_spectrum(self.h, _addr(table), int(k), spec.ctypes.data if spec is not None else None,
                                             int(nspec or 0), C.byref(d), C.byref(m), C.byref(mc)))
         return {"spectrum": spec, "distinct": d.value, "max_count": m.value, "max_code": mc.value}
 
@@ -833,25 +843,37 @@ class Context:
         """dx_kmer_list of a device table: (found: the codes counted min_count times at least, the first min(cap, found) of them in
         ascending code order as a KMER_DTYPE array)."""
         cap, found = int(cap), C.c_uint64()
-        d_out = self.alloc(16 * cap + 16) if cap else None
-        try:
-            self._chk(self.lib.dx_kmer_list(self.h, _dev(table)[0], int(k), int(min_count), d_out.ptr if d_out else None, cap,
-                                            C.byref(found)))
-            got = min(cap, found.value)
-            lst = d_out.download(np.uint8, 16 * got).view(KMER_DTYPE) if got else np.zeros(0, KMER_DTYPE)
-        finally:
-            if d_out:
-                d_out.free()
+
+        def call(p_out):
+            self._chk(self.lib.dx_kmer_list(self.h, _addr(table), int(k), int(min_count), p_out, cap, C.byref(found)))
+            return found.value
+        lst = self._listed(call, cap, KMER_DTYPE)
         return found.value, lst
 
     def kmers_add(self, kind, img: bytes, k, canonical, table) -> dict:
         """dx_file_kmers_add: the k-mers of the reads of the image ("fasta" or "arrow") added to the device table of 4^k counters,
         so that several files are counted into one.  {"records", "symbols", "windows"} of this image."""
-        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
         r, s, w = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._chk(self.lib.dx_file_kmers_add(self.h, kd, img, len(img), int(k), int(bool(canonical)), _dev(table)[0], C.byref(r),
+        self._chk(self.lib.dx_file_kmers_add(self.h, _kind(kind), img, len(img), int(k), int(bool(canonical)), _addr(table), C.byref(r),
                                              C.byref(s), C.byref(w)))
         return {"records": r.value, "symbols": s.value, "windows": w.value}
+
+    def _file_kmers(self, fn, km, raw, listed, letters, kind, img, k, canonical, nspec, min_count, max_list, table=None):
+        """dx_file_kmers / dx_file_kmers_wide: one argument list, one answer.  km: the entry point's report struct, raw: the dtype of
+        its list, listed: of the list returned, whose `letters` letters(code, k, arrow=) makes; table: whether the counters are wanted
+        too, None for the entry point that has none to give."""
+        kd, spec, n = _kind(kind), np.zeros(int(nspec), np.uint64), C.c_uint64()
+        with _Outs(self.lib, 2) as (lst, tab):
+            self._chk(fn(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), int(max_list), C.byref(km),
+                         spec.ctypes.data, int(nspec), C.byref(lst), C.byref(n),
+                         *(() if table is None else (C.byref(tab) if table else None,))))
+            rep = _fields(km)
+            rep["listed"] = n.value
+            got, out = _take(lst, raw, n.value), np.zeros(n.value, listed)
+            if n.value:
+                out["count"], out["code"] = got["count"], got["code"]
+                out["letters"] = [letters(int(c), int(k), arrow=kind == "arrow") for c in got["code"]]
+            return (rep, spec, out, _take(tab, np.uint64, 4 ** int(k))) if table else (rep, spec, out)
 
     def kmers(self, kind, img: bytes, k, canonical=False, nspec=256, min_count=0, max_list=0, table=False):
         """dx_file_kmers: the exact counts of all k-mers (1 <= k <= 14) of the reads of the image ("fasta" or "arrow"), counted on
@@ -860,26 +882,8 @@ class Context:
         "windows", "distinct", "max_count", "max_code", "k", "listed"}; spectrum: uint64[nspec] as kmer_spectrum's; list: the first
         max_list codes counted min_count times at least (min_count 0: none), ascending, as a KMER_LIST_DTYPE array whose `letters`
         are what Context.find takes as a pattern."""
-        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        km, lst, n, tab = L.Kmers(), C.c_void_p(), C.c_uint64(), C.c_void_p()
-        spec = np.zeros(int(nspec), np.uint64)
-        self._chk(self.lib.dx_file_kmers(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), int(max_list),
-                                         C.byref(km), spec.ctypes.data, int(nspec), C.byref(lst), C.byref(n),
-                                         C.byref(tab) if table else None))
-        try:
-            rep = {f: getattr(km, f) for f, _ in L.Kmers._fields_}
-            rep["listed"] = n.value
-            out = np.zeros(n.value, KMER_LIST_DTYPE)
-            if n.value:
-                raw = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * n.value,)).view(KMER_DTYPE)
-                out["count"], out["code"] = raw["count"], raw["code"]
-                out["letters"] = [kmer_letters(int(c), int(k), arrow=kind == "arrow") for c in raw["code"]]
-            res = (rep, spec, out)
-            if table:
-                res += (np.ctypeslib.as_array(C.cast(tab, C.POINTER(C.c_uint64)), (4 ** int(k),)).copy(),)
-            return res
-        finally:
-            self.lib.dx_file_free(lst); self.lib.dx_file_free(tab)
+        return self._file_kmers(self.lib.dx_file_kmers, L.Kmers(), KMER_DTYPE, KMER_LIST_DTYPE, kmer_letters, kind, img, k, canonical,
+                                nspec, min_count, max_list, bool(table))
 
     # ---- k-mers up to k = 32: codes written out, sorted, counted off the runs ---------------------------
     def sort_u64(self, keys, bits, tmp=None, n=None):
@@ -889,7 +893,7 @@ class Context:
         n = int(b // 8 if n is None else n)
         own = self.alloc(8 * n + 8) if tmp is None and n else None
         try:
-            self._chk(self.lib.dx_sort_u64(self.h, p, own.ptr if own else _dev(tmp)[0], n, int(bits)))
+            self._chk(self.lib.dx_sort_u64(self.h, p, _addr(own if own is not None else tmp), n, int(bits)))
         finally:
             if own:
                 own.free()
@@ -914,14 +918,12 @@ class Context:
         elif cap is None:
             cap = _dev(codes)[1] // 8
         win, bad = C.c_uint64(), C.c_uint64()
-        rc = self.lib.dx_code_kmer_codes(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _dev(boff)[0], _dev(beg)[0], p_len,
-                                         n, k, int(bool(canonical)), _dev(codes)[0], int(cap), C.byref(win), C.byref(bad))
+        rc = self.lib.dx_code_kmer_codes(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                         n, k, int(bool(canonical)), _addr(codes), int(cap), C.byref(win), C.byref(bad))
         if rc != 0:
             if own:
                 own.free()
-            e = self._bad_unit(rc, bad)
-            e.windows = win.value
-            raise e
+            raise self._err(rc, bad_unit=_index(bad), windows=win.value)
         return codes, win.value
 
     def kmer_runs(self, sorted_codes, n, min_count, cap, nspec=256):
@@ -931,48 +933,31 @@ class Context:
         cap, found = int(cap), C.c_uint64()
         spec = np.zeros(int(nspec), np.uint64) if nspec else None
         d, m, mc = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        d_out = self.alloc(16 * cap + 16) if cap else None
-        try:
-            self._chk(self.lib.dx_kmer_runs(self.h, _dev(sorted_codes)[0], int(n), int(min_count), d_out.ptr if d_out else None, cap,
-                                            C.byref(found), spec.ctypes.data if spec is not None else None, int(nspec or 0),
-                                            C.byref(d), C.byref(m), C.byref(mc)))
-            got = min(cap, found.value)
-            lst = d_out.download(np.uint8, 16 * got).view(KMER64_DTYPE) if got else np.zeros(0, KMER64_DTYPE)
-        finally:
-            if d_out:
-                d_out.free()
+
+        def call(p_out):
+            self._chk(self.lib.dx_kmer_runs(self.h, _addr(sorted_codes), int(n), int(min_count), p_out, cap, C.byref(found),
+                                            spec.ctypes.data if spec is not None else None, int(nspec or 0), C.byref(d), C.byref(m),
+                                            C.byref(mc)))
+            return found.value
+        lst = self._listed(call, cap, KMER64_DTYPE)
         return found.value, lst, {"spectrum": spec, "distinct": d.value, "max_count": m.value, "max_code": mc.value}
 
     def kmers_wide(self, kind, img: bytes, k, canonical=False, nspec=256, min_count=0, max_list=0):
         """dx_file_kmers_wide: Context.kmers for 1 <= k <= 32, by sorting -- every window's code written out on the device, sorted,
         the counts read off the runs; 16 bytes of device memory a window.  Returns (report, spectrum, list) as kmers does, the
         report with the same keys; the list is a KMER64_LIST_DTYPE array (64-bit codes, `letters` 32 bytes wide)."""
-        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        km, lst, n = L.Kmers64(), C.c_void_p(), C.c_uint64()
-        spec = np.zeros(int(nspec), np.uint64)
-        self._chk(self.lib.dx_file_kmers_wide(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), int(max_list),
-                                              C.byref(km), spec.ctypes.data, int(nspec), C.byref(lst), C.byref(n)))
-        try:
-            rep = {f: getattr(km, f) for f, _ in L.Kmers._fields_}
-            rep["listed"] = n.value
-            out = np.zeros(n.value, KMER64_LIST_DTYPE)
-            if n.value:
-                raw = np.ctypeslib.as_array(C.cast(lst, C.POINTER(C.c_uint8)), (16 * n.value,)).view(KMER64_DTYPE)
-                out["count"], out["code"] = raw["count"], raw["code"]
-                out["letters"] = [kmer_letters64(int(c), int(k), arrow=kind == "arrow") for c in raw["code"]]
-            return rep, spec, out
-        finally:
-            self.lib.dx_file_free(lst)
+        return self._file_kmers(self.lib.dx_file_kmers_wide, L.Kmers64(), KMER64_DTYPE, KMER64_LIST_DTYPE, kmer_letters64, kind, img, k,
+                                canonical, nspec, min_count, max_list)
 
     # ---- screen: the reads that share k-mers with a set ---------------------------------------------------
     def kmer_set(self, kind, img: bytes, k, canonical=False, min_count=1, report=False):
         """dx_file_kmer_set: the distinct k-mers (1 <= k <= 32) of a .dexta / .dexar image that are counted min_count times at least,
         as a KmerSet on the device -- kmers_wide's route up to the sorted codes.  report: (set, what kmers_wide reports for the image)."""
-        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
         h, km = C.c_void_p(), L.Kmers64()
-        self._chk(self.lib.dx_file_kmer_set(self.h, kd, img, len(img), int(k), int(bool(canonical)), int(min_count), C.byref(h), C.byref(km)))
+        self._chk(self.lib.dx_file_kmer_set(self.h, _kind(kind), img, len(img), int(k), int(bool(canonical)), int(min_count), C.byref(h),
+                                            C.byref(km)))
         s = KmerSet(self, h)
-        return (s, {f: getattr(km, f) for f, _ in L.Kmers._fields_}) if report else s
+        return (s, _fields(km)) if report else s
 
     def kmer_set_from_codes(self, codes, k, canonical=False, arrow=False):
         """dx_kmer_set_from_codes: the KmerSet of the given 64-bit codes (any order, repeats allowed, none at all: the empty set); with
@@ -986,7 +971,7 @@ class Context:
     def kmer_set_from_sorted(self, sorted_codes, n, k, min_count=1, canonical=False, arrow=False):
         """dx_kmer_set_from_sorted: the KmerSet of the codes whose run in the sorted device array of n keys has min_count keys at least"""
         h = C.c_void_p()
-        self._chk(self.lib.dx_kmer_set_from_sorted(self.h, _dev(sorted_codes)[0], int(n), int(min_count), int(k), int(bool(canonical)),
+        self._chk(self.lib.dx_kmer_set_from_sorted(self.h, _addr(sorted_codes), int(n), int(min_count), int(k), int(bool(canonical)),
                                                    int(bool(arrow)), C.byref(h)))
         return KmerSet(self, h)
 
@@ -1000,29 +985,22 @@ class Context:
         p_len, b_len = _dev(length)
         n = int(b_len // 4 if n is None else n)
         tot, bad = (C.c_uint64 * 4)(), C.c_uint64()
-        rc = self.lib.dx_code_kmer_screen(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _dev(boff)[0], _dev(beg)[0], p_len,
-                                          n, kset.h if kset is not None else None, _dev(out)[0], C.byref(tot), C.byref(bad))
+        rc = self.lib.dx_code_kmer_screen(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                          n, kset.h if kset is not None else None, _addr(out), C.byref(tot), C.byref(bad))
         totals = np.array(list(tot), np.uint64)
         if rc != 0:
-            e = self._bad_unit(rc, bad)
-            e.totals = totals
-            raise e
+            raise self._err(rc, bad_unit=_index(bad), totals=totals)
         return totals
 
     def screen(self, kind, img: bytes, kset):
         """dx_file_screen: the records of a .dexta / .dexar image screened against the KmerSet kset -> (report: records, symbols,
         windows, hits, covered, records_hit, k; rec: a SCREEN_DTYPE array, one entry a record; rec_len: every record's symbols).
         api.screen_select turns (rec, rec_len) into the ids that Context.subset takes."""
-        kd = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-        rp, rec, rl = L.ScreenReport(), C.c_void_p(), C.c_void_p()
-        self._chk(self.lib.dx_file_screen(self.h, kd, img, len(img), kset.h if kset is not None else None, C.byref(rp), C.byref(rec), C.byref(rl)))
-        try:
-            n = int(rp.records)
-            r = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint8)), (16 * n,)).view(SCREEN_DTYPE).copy() if n else np.zeros(0, SCREEN_DTYPE)
-            ln = np.ctypeslib.as_array(C.cast(rl, C.POINTER(C.c_uint32)), (n,)).copy() if n else np.zeros(0, np.uint32)
-            return {f: getattr(rp, f) for f, _ in L.ScreenReport._fields_ if f != "reserved"}, r, ln
-        finally:
-            self.lib.dx_file_free(rec); self.lib.dx_file_free(rl)
+        rp = L.ScreenReport()
+        with _Outs(self.lib, 2) as (rec, rl):
+            self._chk(self.lib.dx_file_screen(self.h, _kind(kind), img, len(img), kset.h if kset is not None else None, C.byref(rp),
+                                              C.byref(rec), C.byref(rl)))
+            return _fields(rp), _take(rec, SCREEN_DTYPE, rp.records), _take(rl, np.uint32, rp.records)
 
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
@@ -1030,9 +1008,8 @@ class Context:
         whole reads from symbol 0) as (d_len[j] + 3) >> 2 packed bytes at d_out + d_out_off[j], not a byte outside them.  Raises
         DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie inside the in_bytes."""
         bad = C.c_uint64()
-        rc = self.lib.dx_reads_repack(self.h, d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
-                                      d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n),
-                                      d_out.ptr if d_out else None, d_out_off.ptr if d_out_off else None, C.byref(bad))
+        rc = self.lib.dx_reads_repack(self.h, _addr(d_in), int(in_bytes), _addr(d_boff), _addr(d_beg), _addr(d_len), int(n),
+                                      _addr(d_out), _addr(d_out_off), C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
 
@@ -1041,9 +1018,8 @@ class Context:
         device), nothing written outside them.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a source range
         does not lie inside the src_bytes."""
         bad = C.c_uint64()
-        rc = self.lib.dx_copy_ranges(self.h, d_src.ptr if d_src else None, int(src_bytes), d_src_off.ptr if d_src_off else None,
-                                     d_len.ptr if d_len else None, int(n), d_dst.ptr if d_dst else None,
-                                     d_dst_off.ptr if d_dst_off else None, C.byref(bad))
+        rc = self.lib.dx_copy_ranges(self.h, _addr(d_src), int(src_bytes), _addr(d_src_off), _addr(d_len), int(n), _addr(d_dst),
+                                     _addr(d_dst_off), C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
 
@@ -1051,17 +1027,15 @@ class Context:
         """dx_file_subset: the image dexta / dexar / dexqv [-l] writes for the text of img's records ids (None: all of them; they
         must not decrease, and may repeat; with beg and end too: records 0 .. len(beg) - 1), whole or cut to [beg[j], end[j]) -- made on the device, no text on the way.  kind:
         "fasta", "arrow" or "quiva"."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        k = _kind(kind)
         ids, beg, end, n = _subset_selection(ids, beg, end)
         if n is None:
-            n = 2 ** 64 - 1                                  # (ids == beg == end == NULL with UINT64_MAX: every record whole)
-        out, ln = C.c_void_p(), C.c_size_t()
-        self._chk(self.lib.dx_file_subset(self.h, k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), n, int(bool(lossy)),
-                                          C.byref(out), C.byref(ln)))
-        try:
-            return C.string_at(out.value, ln.value)
-        finally:
-            self.lib.dx_file_free(out)
+            n = _NONE64                                      # (ids == beg == end == NULL with UINT64_MAX: every record whole)
+        ln = C.c_size_t()
+        with _Outs(self.lib, 1) as (out,):
+            self._chk(self.lib.dx_file_subset(self.h, k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), n, int(bool(lossy)),
+                                              C.byref(out), C.byref(ln)))
+            return _text(out, ln)
 
     # ---- extract -----------------------------------------------------------------------------------
     def reads_unpack_lines(self, letters, d_in, in_bytes, d_boff, d_beg, d_len, n, width, d_out, d_out_off):
@@ -1070,9 +1044,8 @@ class Context:
         d_out_off[j], not a byte outside them.  Raises DexGPUError (DX_E_FORMAT, .bad_unit = the first such j) when a unit does not lie
         inside the in_bytes."""
         bad = C.c_uint64()
-        rc = self.lib.dx_reads_unpack_lines(self.h, int(letters), d_in.ptr if d_in else None, int(in_bytes), d_boff.ptr if d_boff else None,
-                                            d_beg.ptr if d_beg else None, d_len.ptr if d_len else None, int(n), int(width),
-                                            d_out.ptr if d_out else None, d_out_off.ptr if d_out_off else None, C.byref(bad))
+        rc = self.lib.dx_reads_unpack_lines(self.h, int(letters), _addr(d_in), int(in_bytes), _addr(d_boff), _addr(d_beg), _addr(d_len),
+                                            int(n), int(width), _addr(d_out), _addr(d_out_off), C.byref(bad))
         if rc != 0:
             raise self._bad_unit(rc, bad)
 
@@ -1081,23 +1054,20 @@ class Context:
         (None: all of them; with beg and end too: records 0 .. len(beg) - 1), in that order -- any order, and an id may repeat --, whole
         or cut to [beg[j], end[j]).  kind: "fasta", "arrow" or "quiva" (which ignores width).  offsets: (text, toff) with toff[j] where
         unit j's header line begins and toff[n] = len(text)."""
-        k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
+        k = _kind(kind)
         ids, beg, end, n = _subset_selection(ids, beg, end)
-        every = n is None
-        out, ln, toff = C.c_void_p(), C.c_size_t(), C.c_void_p()
-        self._chk(self.lib.dx_file_extract(self.h, k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), 2 ** 64 - 1 if every else n,
-                                           int(bool(upper)), int(width), C.byref(out), C.byref(ln), C.byref(toff) if offsets else None))
-        try:
-            text = C.string_at(out.value, ln.value)
+        every, ln = n is None, C.c_size_t()
+        with _Outs(self.lib, 2) as (out, toff):
+            self._chk(self.lib.dx_file_extract(self.h, k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), _NONE64 if every else n,
+                                               int(bool(upper)), int(width), C.byref(out), C.byref(ln), C.byref(toff) if offsets else None))
+            text = _text(out, ln)
             if not offsets:
                 return text
             if every:                                        # (the count is the library's; every unit has a header line, so the
                 n, at = 0, C.cast(toff, C.POINTER(C.c_uint64))   #  offsets rise, and the first that is the text's length is the last)
                 while at[n] != ln.value:
                     n += 1
-            return text, np.ctypeslib.as_array(C.cast(toff, C.POINTER(C.c_uint64)), (n + 1,)).copy()
-        finally:
-            self.lib.dx_file_free(out); self.lib.dx_file_free(toff)
+            return text, _take(toff, np.uint64, n + 1)
 
     def qv_subindex(self, on=True):
         self._chk(self.lib.dx_qv_subindex(self.h, int(bool(on))))
@@ -1106,7 +1076,7 @@ class Context:
         """dx_qv_onepass_info: the route the last one-pass encode took (groups / direct, scratch, budget)."""
         o = L.OnepassInfo()
         self._chk(self.lib.dx_qv_onepass_info(self.h, C.byref(o)))
-        d = {k: int(getattr(o, k)) for k, _ in L.OnepassInfo._fields_ if k not in ("reserved", "chain_waits")}
+        d = _fields(o, skip=("reserved", "chain_waits"))
         d["chain_waits"] = [int(x) for x in o.chain_waits]
         return d
 
@@ -1132,57 +1102,52 @@ class Context:
                 return 1
         return L.SINK_FN(cb), box
 
+    @staticmethod
+    def _source(read, box):
+        """ctypes callback around a Python read(want) -> bytes; what it raises goes into the sink's `box`, and the library is told
+        that reading failed"""
+        def rd(user, buf, want):
+            try:
+                data = read(want)
+                C.memmove(buf, data, len(data))
+                return len(data)
+            except BaseException as e:                       # noqa: BLE001 -- re-raised by the caller
+                box.append(e)
+                return -1
+        return L.READ_FN(rd)
+
+    def _streamed(self, box, rc, total, where=None):
+        """the end of a streaming call: what a callback raised goes on from here; else rc is checked -- where: the (line, code) of
+        an entry point that indexes text, which go in front of the library's words -- and the stream's size returned"""
+        if box:
+            raise box[0]
+        if rc != 0:
+            raise self._err(rc, f"line {where[0].value} (DX_IDX code {where[1].value}): {{}}" if where else "{}")
+        return total.value
+
     def unpack2_stream(self, img: bytes, sink, mode=L.DX_LETTERS_LOWER, width=80) -> int:
         """dx_file_unpack2_to: sink(data: bytes, at: int) -> falsy to go on; returns the text's size."""
         total = C.c_size_t()
         cb, box = self._sink(sink)
         rc = self.lib.dx_file_unpack2_to(self.h, int(mode), img, len(img), int(width), cb, None, C.byref(total))
-        if box:
-            raise box[0]
-        self._chk(rc)
-        return total.value
+        return self._streamed(box, rc, total)
 
     def pack2_stream(self, read, sink, arrow=False, chunk=0) -> int:
         """dx_file_pack2_stream: read(want: int) -> bytes (fewer than want only at the end); sink(data: bytes, at: int) -> falsy
         to go on; returns the image's size."""
         total, line, code = C.c_size_t(), C.c_uint64(), C.c_int()
         cb, box = self._sink(sink)
-
-        def rd(user, buf, want):
-            try:
-                data = read(want)
-                C.memmove(buf, data, len(data))
-                return len(data)
-            except BaseException as e:                       # noqa: BLE001 -- re-raised by the caller
-                box.append(e)
-                return -1
-        rcb = L.READ_FN(rd)
+        rcb = self._source(read, box)
         rc = self.lib.dx_file_pack2_stream(self.h, int(arrow), rcb, None, int(chunk), cb, None, C.byref(total), C.byref(line), C.byref(code))
-        if box:
-            raise box[0]
-        if rc != 0:
-            raise L.DexGPUError(rc, f"line {line.value} (DX_IDX code {code.value}): " + (self.lib.dx_last_error(self.h) or b"").decode())
-        return total.value
+        return self._streamed(box, rc, total, (line, code))
 
     def unpack2_pieces(self, read, sink, mode=L.DX_LETTERS_LOWER, width=80, chunk=0) -> int:
         """dx_file_unpack2_stream: read(want: int) -> bytes of the image; sink(data: bytes, at: int); returns the text's size."""
         total = C.c_size_t()
         cb, box = self._sink(sink)
-
-        def rd(user, buf, want):
-            try:
-                data = read(want)
-                C.memmove(buf, data, len(data))
-                return len(data)
-            except BaseException as e:                       # noqa: BLE001 -- re-raised by the caller
-                box.append(e)
-                return -1
-        rcb = L.READ_FN(rd)
+        rcb = self._source(read, box)
         rc = self.lib.dx_file_unpack2_stream(self.h, int(mode), rcb, None, int(chunk), int(width), cb, None, C.byref(total))
-        if box:
-            raise box[0]
-        self._chk(rc)
-        return total.value
+        return self._streamed(box, rc, total)
 
     def dexqv_stream(self, quiva: bytes, sink, lossy=False) -> int:
         """dx_file_dexqv_to: sink(data: bytes, at: int) -> falsy to go on; returns the image's size."""
@@ -1190,11 +1155,7 @@ class Context:
         cb, box = self._sink(sink)
         rc = self.lib.dx_file_dexqv_to(self.h, quiva, len(quiva), int(lossy), cb, None, C.byref(total),
                                        C.byref(line), C.byref(code))
-        if box:
-            raise box[0]
-        if rc != 0:
-            raise L.DexGPUError(rc, f"line {line.value} (DX_IDX code {code.value}): " + (self.lib.dx_last_error(self.h) or b"").decode())
-        return total.value
+        return self._streamed(box, rc, total, (line, code))
 
     def undexqv_stream(self, img: bytes, sink, upper=False) -> int:
         """dx_file_undexqv_plan + dx_file_undexqv_run: sink(data: bytes, at: int) -> falsy to go on; returns the
@@ -1207,42 +1168,31 @@ class Context:
         try:
             cb, box = self._sink(sink)
             rc = self.lib.dx_file_undexqv_run(self.h, plan, int(upper), cb, None)
-            if box:
-                raise box[0]
-            self._chk(rc)
+            return self._streamed(box, rc, total)
         finally:
             self.lib.dx_file_undexqv_plan_free(plan)
-        return total.value
+
+
+def _sharded(contexts, name, *args):
+    """the sharded file drivers: lib.<name>(the contexts' handles, how many, *args, &out, &n, &line, &code) -> the bytes it made"""
+    lib = contexts[0].lib
+    arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
+    n, line, code = C.c_size_t(), C.c_uint64(), C.c_int()
+    with _Outs(lib, 1) as (out,):
+        rc = getattr(lib, name)(arr, len(contexts), *args, C.byref(out), C.byref(n), C.byref(line), C.byref(code))
+        if rc != 0:
+            raise _error(rc, f"line {line.value} (DX_IDX code {code.value})")
+        return _text(out, n)
 
 
 def dexqv_sharded(contexts, quiva: bytes, lossy=False) -> bytes:
     """One .quiva file over several contexts/GPUs (dx_file_dexqv_sharded)."""
-    lib = contexts[0].lib
-    arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
-    out, n, line, code = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_int()
-    rc = lib.dx_file_dexqv_sharded(arr, len(contexts), quiva, len(quiva), int(lossy), C.byref(out), C.byref(n),
-                                   C.byref(line), C.byref(code))
-    if rc != 0:
-        raise L.DexGPUError(rc, f"line {line.value} (DX_IDX code {code.value})")
-    try:
-        return C.string_at(out.value, n.value)
-    finally:
-        lib.dx_file_free(out)
+    return _sharded(contexts, "dx_file_dexqv_sharded", quiva, len(quiva), int(lossy))
 
 
 def pack2_sharded(contexts, text: bytes, arrow=False) -> bytes:
     """One .fasta/.arrow file over several contexts/GPUs (dx_file_pack2_sharded)."""
-    lib = contexts[0].lib
-    arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
-    out, n, line, code = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_int()
-    rc = lib.dx_file_pack2_sharded(arr, len(contexts), int(arrow), text, len(text), C.byref(out), C.byref(n),
-                                   C.byref(line), C.byref(code))
-    if rc != 0:
-        raise L.DexGPUError(rc, f"line {line.value} (DX_IDX code {code.value})")
-    try:
-        return C.string_at(out.value, n.value)
-    finally:
-        lib.dx_file_free(out)
+    return _sharded(contexts, "dx_file_pack2_sharded", int(arrow), text, len(text))
 
 
 # ---- host-only helpers (no GPU needed) ---------------------------------------------------------
@@ -1272,7 +1222,7 @@ class KmerSet:
         """{"codes", "device_bytes", "k", "canonical", "arrow", "index_bits"}"""
         i = L.KmerSetInfo()
         self.ctx._chk(self.ctx.lib.dx_kmer_set_info(self.h, C.byref(i)))
-        return {f: int(getattr(i, f)) for f, _ in L.KmerSetInfo._fields_}
+        return _fields(i)
 
     def codes(self) -> np.ndarray:
         """the set's codes, ascending, as a uint64 array"""
@@ -1299,24 +1249,13 @@ def screen_select(rec, rec_len, min_hits=1, min_permille=0, drop=False) -> np.nd
     ln = np.ascontiguousarray(np.asarray(rec_len, np.uint32))
     if len(r) != len(ln):
         raise L.DexGPUError(-1, "dx_screen_select: an entry and a length a record")
-    ids, n = C.c_void_p(), C.c_uint64()
-    rc = L.load().dx_screen_select(r.ctypes.data if len(r) else None, ln.ctypes.data if len(ln) else None, len(r), int(min_hits),
-                                   int(min_permille), L.DX_SCREEN_DROP if drop else L.DX_SCREEN_KEEP, C.byref(ids), C.byref(n))
-    if rc != 0:
-        raise L.DexGPUError(rc, "dx_screen_select: min_permille is 0 to 1000")
-    try:
-        return np.ctypeslib.as_array(C.cast(ids, C.POINTER(C.c_uint64)), (n.value,)).copy() if n.value else np.zeros(0, np.uint64)
-    finally:
-        L.load().dx_file_free(ids)
-
-
-def _dev(x):
-    """a device array -> (its address, its bytes): a DevBuf, a DevView (bytes unknown: None), a torch tensor, or None"""
-    if x is None:
-        return None, 0
-    if hasattr(x, "data_ptr"):
-        return x.data_ptr(), x.numel() * x.element_size()
-    return x.ptr, getattr(x, "nbytes", None)
+    n = C.c_uint64()
+    with _Outs(L.load(), 1) as (ids,):
+        rc = L.load().dx_screen_select(r.ctypes.data if len(r) else None, ln.ctypes.data if len(ln) else None, len(r), int(min_hits),
+                                       int(min_permille), L.DX_SCREEN_DROP if drop else L.DX_SCREEN_KEEP, C.byref(ids), C.byref(n))
+        if rc != 0:
+            raise L.DexGPUError(rc, "dx_screen_select: min_permille is 0 to 1000")
+        return _take(ids, np.uint64, n.value)
 
 
 def kmer_code(letters, arrow=False, canonical=False) -> int:
@@ -1378,12 +1317,11 @@ def _cut_mode(mode):
 
 def cut_dict(cut) -> dict:
     """a dx_cut as a dict"""
-    return {f: int(getattr(cut, f)) for f, _ in L.Cut._fields_}
+    return _fields(cut)
 
 
 def _cut_selection(sel, n):
-    return {name: np.ctypeslib.as_array(C.cast(a, C.POINTER(t)), (n + 1,))[:n].copy()
-            for name, a, t in zip(("ids", "beg", "end"), sel, (C.c_uint64, C.c_uint32, C.c_uint32))}
+    return {name: _take(a, t, n) for name, a, t in zip(("ids", "beg", "end"), sel, (np.uint64, np.uint32, np.uint32))}
 
 
 def cut_plan(hits, start, rec_len, min_len=0, mode="split"):
@@ -1397,17 +1335,14 @@ def cut_plan(hits, start, rec_len, min_len=0, mode="split"):
     if len(h) != len(st):
         raise ValueError("hits / start: one start a hit")
     lib = L.load()
-    sel, n, cut = [C.c_void_p() for _ in range(3)], C.c_uint64(), L.Cut()
-    rc = lib.dx_hits_cut_plan(h.ctypes.data if len(h) else None, st.ctypes.data if len(st) else None, len(h),
-                              rl.ctypes.data if len(rl) else None, len(rl), int(min_len), _cut_mode(mode),
-                              *[C.byref(a) for a in sel], C.byref(n), C.byref(cut))
-    if rc != 0:
-        raise L.DexGPUError(rc, "dx_hits_cut_plan")
-    try:
+    n, cut = C.c_uint64(), L.Cut()
+    with _Outs(lib, 3) as sel:
+        rc = lib.dx_hits_cut_plan(h.ctypes.data if len(h) else None, st.ctypes.data if len(st) else None, len(h),
+                                  rl.ctypes.data if len(rl) else None, len(rl), int(min_len), _cut_mode(mode),
+                                  *[C.byref(a) for a in sel], C.byref(n), C.byref(cut))
+        if rc != 0:
+            raise L.DexGPUError(rc, "dx_hits_cut_plan")
         return _cut_selection(sel, n.value), cut_dict(cut)
-    finally:
-        for a in sel:
-            lib.dx_file_free(a)
 
 
 def census_dict(cs) -> dict:
@@ -1420,11 +1355,10 @@ def census_dict(cs) -> dict:
 
 def compare_dict(cm) -> dict:
     """a dx_compare as Context.compare returns it"""
-    none = 2**64 - 1
     out = {f: int(getattr(cm, f)) for f in ("lines", "records_a", "records_b", "headers_differ", "lengths_differ", "records_differ")}
     out["same"], out["prefix_differs"] = bool(cm.same), bool(cm.prefix_differs)
     for f in ("first_header", "first_length", "first_record"):
-        out[f] = None if getattr(cm, f) == none else int(getattr(cm, f))
+        out[f] = None if getattr(cm, f) == _NONE64 else int(getattr(cm, f))
     out["first_line"] = None if out["first_record"] is None else int(cm.first_line)
     out["first_column"] = None if out["first_record"] is None else int(cm.first_column)
     for f in ("differ", "line_records", "sum_abs", "max_abs"):
@@ -1467,25 +1401,22 @@ def subset_layout(kind, img: bytes, ids=None, beg=None, end=None) -> dict:
     dx_reads_repack fills it with.  {"frame": bytes (every payload byte 0), "src_off", "dst_off" (uint64), "src_beg", "len" (uint32)}:
     unit j is symbols [src_beg[j], src_beg[j] + len[j]) of the packed read at img[src_off[j]:], to frame[dst_off[j]:].  The selection
     names its units here (ids, or beg and end): the arrays have one value each."""
-    k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW}[kind]
+    if kind == "quiva":                                      # (a .dexqv image has no packed reads to lay out)
+        raise KeyError(kind)
+    k = _kind(kind)
     ids, beg, end, n = _subset_selection(ids, beg, end)
     if n is None:
         raise ValueError("subset_layout: give ids, or beg and end (the arrays that come back have one value a unit)")
-    lib = L.load()
-    frame, ln = C.c_void_p(), C.c_size_t()
-    arr = [C.c_void_p() for _ in range(4)]
-    rc = lib.dx_file_subset_layout(k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), n, C.byref(frame), C.byref(ln),
-                                   *[C.byref(a) for a in arr])
-    if rc != 0:
-        raise L.DexGPUError(rc, (lib.dx_last_error(None) or b"").decode())
-    try:
-        out = {"frame": C.string_at(frame.value, ln.value)}
-        for name, a, t in zip(("src_off", "src_beg", "len", "dst_off"), arr, (C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64)):
-            out[name] = np.ctypeslib.as_array(C.cast(a, C.POINTER(t)), (n + 1,))[:n].copy()
+    lib, ln = L.load(), C.c_size_t()
+    with _Outs(lib, 5) as (frame, *arr):
+        rc = lib.dx_file_subset_layout(k, img, len(img), _ptr(ids), _ptr(beg), _ptr(end), n, C.byref(frame), C.byref(ln),
+                                       *[C.byref(a) for a in arr])
+        if rc != 0:
+            raise _error(rc, _words(lib, None))
+        out = {"frame": _text(frame, ln)}
+        for name, a, t in zip(("src_off", "src_beg", "len", "dst_off"), arr, (np.uint64, np.uint32, np.uint32, np.uint64)):
+            out[name] = _take(a, t, n)
         return out
-    finally:
-        for a in [frame] + arr:
-            lib.dx_file_free(a)
 
 
 def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
@@ -1495,8 +1426,7 @@ def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
 
 def text_options(kind, text: bytes):
     """dx_file_text_options (host): (upper, width) that give `text` back, as dx_file_verify reads them off it"""
-    k = {"fasta": L.DX_KIND_FASTA, "arrow": L.DX_KIND_ARROW, "quiva": L.DX_KIND_QUIVA}[kind]
-    upper, width = C.c_int(), C.c_uint32()
+    k, upper, width = _kind(kind), C.c_int(), C.c_uint32()
     rc = L.load().dx_file_text_options(k, text, len(text), C.byref(upper), C.byref(width))
     if rc != 0:
         raise L.DexGPUError(rc, "the text does not index")
@@ -1505,10 +1435,7 @@ def text_options(kind, text: bytes):
 
 def qv_build(hist, tot, params, lossy=False) -> L.QVCoding:
     """Create_QVcoding (QV.c:1029-1169) on the host."""
-    lib = L.load()
-    h = L.HIST()
-    np.ctypeslib.as_array(h)[:] = np.asarray(hist, dtype=np.uint64).reshape(6, 256)
-    c = L.QVCoding()
+    lib, h, c = L.load(), _hist(hist), L.QVCoding()
     rc = lib.dx_qv_build(C.byref(h), int(tot), C.byref(params), int(lossy), C.byref(c))
     if rc != 0:
         raise L.DexGPUError(rc, "dx_qv_build")
@@ -1517,9 +1444,7 @@ def qv_build(hist, tot, params, lossy=False) -> L.QVCoding:
 
 def qv_out_bound(hist, n, coding, lossy=False) -> int:
     """dx_qv_out_bound: bytes (without framing) the batch whose raw histograms are `hist` can encode to at most."""
-    lib = L.load()
-    h = L.HIST()
-    np.ctypeslib.as_array(h)[:] = np.asarray(hist, dtype=np.uint64).reshape(6, 256)
+    lib, h = L.load(), _hist(hist)
     return int(lib.dx_qv_out_bound(C.byref(h), int(n), C.byref(coding), int(lossy)))
 
 
@@ -1550,11 +1475,8 @@ def qv_walk(img: bytes, index=False):
     group index of dx_qv_walk_indexed (gidx words, gidx_off, gidx_none)."""
     lib = L.load()
     x = L.QVIndex()
-    if isinstance(img, np.ndarray):                       # (a big image: no copy into a bytes object)
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        rc = lib.dx_qv_walk_indexed(img.ctypes.data_as(C.c_void_p), img.size, C.byref(x), int(bool(index)))
-    else:
-        rc = lib.dx_qv_walk_indexed(img, len(img), C.byref(x), int(bool(index)))
+    p, nb = _host_bytes(img)
+    rc = lib.dx_qv_walk_indexed(p, nb, C.byref(x), int(bool(index)))
     if rc != 0:
         raise L.DexGPUError(rc, "dx_qv_walk")
     try:
@@ -1584,19 +1506,13 @@ def qv_walk_records(buf, start, rlen, coding, flip=False):
     start = np.ascontiguousarray(start, dtype=np.uint64)
     rlen = np.ascontiguousarray(rlen, dtype=np.uint32)
     assert len(start) == len(rlen)
-    if isinstance(buf, np.ndarray):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        bp, nb = buf.ctypes.data_as(C.c_void_p), buf.size
-    else:
-        bp, nb = buf, len(buf)
+    bp, nb = _host_bytes(buf)
     seg = np.zeros((len(start), 5), np.uint32)
     bad = C.c_uint64()
     rc = lib.dx_qv_walk_records(bp, nb, start.ctypes.data, rlen.ctypes.data, len(start), C.byref(coding), int(bool(flip)),
                                 seg.ctypes.data, C.byref(bad))
     if rc != 0:
-        e = L.DexGPUError(rc, f"dx_qv_walk_records: entry {bad.value}")
-        e.bad_entry = bad.value if bad.value != 2**64 - 1 else None
-        raise e
+        raise _error(rc, f"dx_qv_walk_records: entry {bad.value}", bad_entry=_index(bad))
     return seg
 
 
