@@ -128,6 +128,14 @@ class ScreenReport(C.Structure):                 # dx_screen_report
     _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64),
                 ("covered", C.c_uint64), ("records_hit", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
 
+class Span(C.Structure):                         # dx_span
+    _fields_ = [("record", C.c_uint64), ("beg", C.c_uint32), ("end", C.c_uint32)]
+
+class SpansReport(C.Structure):                  # dx_spans_report
+    _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("covered", C.c_uint64), ("records_hit", C.c_uint64),
+                ("raw_spans", C.c_uint64), ("spans", C.c_uint64), ("span_symbols", C.c_uint64), ("listed", C.c_uint64),
+                ("k", C.c_uint32), ("reserved", C.c_uint32)]
+
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 DX_SCREEN_KEEP, DX_SCREEN_DROP = 0, 1
 DX_CUT_SPLIT, DX_CUT_LONGEST, DX_CUT_DROP = 0, 1, 2
@@ -297,6 +305,16 @@ SIGNATURES = {
                                       C.POINTER(C.c_uint64)]),
     "dx_file_screen": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(ScreenReport), C.POINTER(_P), C.POINTER(_P)]),
     "dx_screen_select": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "dx_code_kmer_spans": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64 * 3),
+                                     C.POINTER(C.c_uint64)]),
+    "dx_spans_join": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64 * 2), C.POINTER(C.c_uint64)]),
+    "dx_file_screen_spans": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SpansReport),
+                                       C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "dx_spans_cut_plan": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                    C.POINTER(C.c_uint64), C.POINTER(Cut)]),
+    "dx_file_screen_cut": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                     C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(Cut), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                     C.POINTER(C.c_uint64)]),
     "dx_file_text_options": (C.c_int, [C.c_int, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "dx_entries_new": (_P, []),
     "dx_entries_free": (None, [_P]),

@@ -1002,6 +1002,81 @@ class Context:
                                               C.byref(rec), C.byref(rl)))
             return _fields(rp), _take(rec, SCREEN_DTYPE, rp.records), _take(rl, np.uint32, rp.records)
 
+    # ---- screen spans: where a read matches the set, and the image cut there ------------------------------
+    def code_kmer_spans(self, d_in, boff, beg, length, kset, count=None, cap=0, spans=None, in_bytes=None, n=None):
+        """dx_code_kmer_spans: units and set as for code_kmer_screen; the spans of a unit are the maximal runs of symbols that lie in
+        a window whose code is in the set.  count: a device array of n uint32 for every unit's spans, or None; spans: a device array
+        of 16 cap bytes, or None: made and freed here (cap 0: counted only).  Returns (totals: uint64 [spans, covered symbols, units
+        with a span], the first min(cap, spans) spans in the order (unit, beg) as a SPAN_DTYPE array).  Raises DexGPUError:
+        DX_E_FORMAT (.bad_unit, .totals) for a unit outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        n, cap = int(b_len // 4 if n is None else n), int(cap)
+        tot, bad = (C.c_uint64 * 3)(), C.c_uint64()
+
+        def call(p_spans):
+            rc = self.lib.dx_code_kmer_spans(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                             n, kset.h if kset is not None else None, _addr(count), p_spans, cap, C.byref(tot),
+                                             C.byref(bad))
+            if rc != 0:
+                raise self._err(rc, bad_unit=_index(bad), totals=np.array(list(tot), np.uint64))
+            return tot[0]
+        lst = self._listed(call, cap, SPAN_DTYPE, spans)
+        return np.array(list(tot), np.uint64), lst
+
+    def spans_join(self, spans, max_gap=0, min_span=0, cap=None, n=None, out=None):
+        """dx_spans_join: a list as code_kmer_spans leaves it -- a SPAN_DTYPE array on the host (uploaded here) or a device array of n
+        16-byte entries -- joined across gaps of at most max_gap within a record, then the joined spans of fewer than min_span
+        symbols dropped.  out: a device array of 16 cap bytes, or None: made and freed here (cap None: n, which always suffices; 0:
+        counted only).  Returns (totals: uint64 [spans kept, their symbols], the first min(cap, kept) as a SPAN_DTYPE array).  Raises
+        DexGPUError: DX_E_FORMAT (.bad_unit = the smallest index that breaks the list's order)."""
+        own = None
+        if isinstance(spans, np.ndarray):
+            a = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+            n = len(a) if n is None else int(n)
+            spans = own = self.to_device(a) if len(a) else None
+        else:
+            n = int(_dev(spans)[1] // 16 if n is None else n)
+        cap = n if cap is None else int(cap)
+        tot, bad = (C.c_uint64 * 2)(), C.c_uint64()
+
+        def call(p_out):
+            rc = self.lib.dx_spans_join(self.h, _addr(spans), n, int(max_gap), int(min_span), p_out, cap, C.byref(tot), C.byref(bad))
+            if rc != 0:
+                raise self._bad_unit(rc, bad)
+            return tot[0]
+        try:
+            lst = self._listed(call, cap, SPAN_DTYPE, out)
+        finally:
+            if own is not None:
+                own.free()
+        return np.array(list(tot), np.uint64), lst
+
+    def screen_spans(self, kind, img: bytes, kset, max_gap=0, min_span=0, max_spans=1 << 20):
+        """dx_file_screen_spans: where the records of a .dexta / .dexar image match the KmerSet kset -- per slice the raw spans
+        listed on the device, joined across gaps of at most max_gap and those of fewer than min_span symbols dropped -> (report:
+        records, symbols, covered, records_hit, raw_spans, spans, span_symbols, listed, k; spans: the first max_spans kept spans in
+        the order (record, beg) as a SPAN_DTYPE array; rec_spans: uint32 a record, its kept spans; rec_len: every record's symbols).
+        api.spans_cut_plan turns (spans, rec_len) into the selection Context.subset takes."""
+        rp = L.SpansReport()
+        with _Outs(self.lib, 3) as (sp, rs, rl):
+            self._chk(self.lib.dx_file_screen_spans(self.h, _kind(kind), img, len(img), kset.h if kset is not None else None,
+                                                    int(max_gap), int(min_span), int(max_spans), C.byref(rp), C.byref(sp), C.byref(rs),
+                                                    C.byref(rl)))
+            return (_fields(rp), _take(sp, SPAN_DTYPE, rp.listed), _take(rs, np.uint32, rp.records), _take(rl, np.uint32, rp.records))
+
+    def screen_cut(self, kind, img: bytes, kset, max_gap=0, min_span=0, min_len=0, mode="split"):
+        """dx_file_screen_cut: the image ("fasta" or "arrow") with what matches the KmerSet kset cut out of its records -- screen_spans
+        with every span listed, spans_cut_plan, subset -- byte for byte what dexta / dexar writes for the cut text.  mode and min_len
+        as for Context.cut.  Returns (image, report, selection) as Context.cut does: the selection {"ids", "beg", "end"} is what
+        Context.subset takes to cut the .dexar and the .dexqv of the same records in the same places."""
+        ln, cut, n = C.c_size_t(), L.Cut(), C.c_uint64()
+        with _Outs(self.lib, 4) as (out, *sel):
+            self._chk(self.lib.dx_file_screen_cut(self.h, _kind(kind), img, len(img), kset.h if kset is not None else None,
+                                                  int(max_gap), int(min_span), int(min_len), _cut_mode(mode), C.byref(out),
+                                                  C.byref(ln), C.byref(cut), *[C.byref(a) for a in sel], C.byref(n)))
+            return _text(out, ln), cut_dict(cut), _cut_selection(sel, n.value)
+
     # ---- subset ------------------------------------------------------------------------------------
     def reads_repack(self, d_in, in_bytes, d_boff, d_beg, d_len, n, d_out, d_out_off):
         """dx_reads_repack: unit j = symbols [d_beg[j], d_beg[j] + d_len[j]) of the packed read at d_in + d_boff[j] (d_beg None:
@@ -1208,6 +1283,7 @@ KMER64_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u8"), ("letters", "S3
 
 
 SCREEN_DTYPE = np.dtype([("hits", "<u4"), ("covered", "<u4"), ("first", "<u4"), ("last", "<u4")])                 # dx_screen
+SPAN_DTYPE = np.dtype([("record", "<u8"), ("beg", "<u4"), ("end", "<u4")])                                         # dx_span
 
 
 class KmerSet:
@@ -1342,6 +1418,21 @@ def cut_plan(hits, start, rec_len, min_len=0, mode="split"):
                                   *[C.byref(a) for a in sel], C.byref(n), C.byref(cut))
         if rc != 0:
             raise L.DexGPUError(rc, "dx_hits_cut_plan")
+        return _cut_selection(sel, n.value), cut_dict(cut)
+
+
+def spans_cut_plan(spans, rec_len, min_len=0, mode="split"):
+    """dx_spans_cut_plan (host, no GPU): cut_plan over spans given directly -- a SPAN_DTYPE array, symbols [beg, end) of record
+    `record`, as Context.screen_spans lists them.  Returns (selection, report) as cut_plan does."""
+    sp = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+    rl = np.ascontiguousarray(rec_len, dtype=np.uint32)
+    lib = L.load()
+    n, cut = C.c_uint64(), L.Cut()
+    with _Outs(lib, 3) as sel:
+        rc = lib.dx_spans_cut_plan(sp.ctypes.data if len(sp) else None, len(sp), rl.ctypes.data if len(rl) else None, len(rl),
+                                   int(min_len), _cut_mode(mode), *[C.byref(a) for a in sel], C.byref(n), C.byref(cut))
+        if rc != 0:
+            raise L.DexGPUError(rc, "dx_spans_cut_plan")
         return _cut_selection(sel, n.value), cut_dict(cut)
 
 

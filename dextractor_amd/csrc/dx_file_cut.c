@@ -1,6 +1,6 @@
 /*
  * dx_file_cut.c -- what is kept of the records of an image once the occurrences of given sequences are cut out of them, and the image of
- * it: dx_hits_cut_plan (host), dx_file_cut.
+ * it: dx_hits_cut_plan, dx_spans_cut_plan (host), dx_file_cut.
  *
  * Everything one does with a found adapter or primer needs both of its ends: cutting it out, splitting a chimeric subread at a missed
  * SMRTbell adapter, dropping the read.  dx_file_find_edit_spans has both ends (the starts by dx_code_hit_starts, on the device, while a
@@ -10,7 +10,8 @@
  * step takes undexta of the whole file, a text scan on one core and dexta again -- and the same for the .dexar and the .dexqv of the run,
  * for which dx_file_cut hands its selection back.
  *
- * The plan needs no device and no context (tools/cut_host_check.c runs it under the sanitizers).
+ * The plan needs no device and no context (tools/cut_host_check.c runs it under the sanitizers).  It works on (record, beg, end) triples,
+ * so the spans of a k-mer screen (dx_file_screen_spans.c) get the same plan through dx_spans_cut_plan (tools/spans_host_check.c).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,10 +22,8 @@
 #include "dx_env.h"
 #include "dx_files.h"
 
-typedef struct { uint64_t record; uint32_t beg, end; } span;
-
 static int by_record_beg(const void *a, const void *b)
-{ const span *x = a, *y = b;
+{ const dx_span *x = a, *y = b;
   if (x->record != y->record) return x->record < y->record ? -1 : 1;
   if (x->beg != y->beg) return x->beg < y->beg ? -1 : 1;
   return x->end < y->end ? -1 : x->end > y->end;
@@ -48,29 +47,18 @@ static int keep(uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n, uin
   return DX_OK;
 }
 
-int dx_hits_cut_plan(const dx_hit *hits, const uint32_t *start, uint64_t n_hits, const uint32_t *rec_len, uint64_t records,
-                     uint32_t min_len, int mode, uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids, dx_cut *report)
+/* the plan of n spans (sp: the plan's own copy, sorted here; every one inside its record) over `records` records: what both entry points
+   share.  The outputs are the caller's, emptied already; mode is one of the three */
+static int plan_spans(dx_span *sp, uint64_t n_hits, const uint32_t *rec_len, uint64_t records, uint32_t min_len, int mode,
+                      uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids, dx_cut *report)
 { const uint32_t least = min_len ? min_len : 1;            /* a piece has one symbol at least */
-  span     *sp = NULL;
-  uint64_t *oi = NULL, n = 0, cap = 0, h, r, k = 0;
+  uint64_t *oi = NULL, n = 0, cap = 0, r, k = 0;
   uint32_t *ob = NULL, *oe = NULL;
   dx_cut    cut;
   int       rc;
-
-  if (ids == NULL || beg == NULL || end == NULL || n_ids == NULL) return DX_E_ARG;
-  *ids = NULL; *beg = NULL; *end = NULL; *n_ids = 0;
-  if (report) memset(report, 0, sizeof(*report));
-  if (mode != DX_CUT_SPLIT && mode != DX_CUT_LONGEST && mode != DX_CUT_DROP) return DX_E_ARG;
-  if ((n_hits && (hits == NULL || start == NULL)) || (records && rec_len == NULL)) return DX_E_ARG;
   memset(&cut, 0, sizeof(cut));
   cut.records_in = records;
-
-  if ((sp = malloc(((size_t) n_hits + 1) * sizeof(*sp))) == NULL) return DX_E_NOMEM;
-  for (h = 0; h < n_hits; h++)
-    { if (hits[h].record >= records || start[h] > hits[h].pos || hits[h].pos > rec_len[hits[h].record]) { rc = DX_E_ARG; goto done; }
-      sp[h].record = hits[h].record; sp[h].beg = start[h]; sp[h].end = hits[h].pos;
-    }
-  qsort(sp, (size_t) n_hits, sizeof(*sp), by_record_beg);  /* (the list comes by (record, pos): not by start) */
+  qsort(sp, (size_t) n_hits, sizeof(*sp), by_record_beg);  /* (a list of hits comes by (record, pos): not by start) */
 
   for (r = 0; r < records; r++)
     { const uint32_t len = rec_len[r];
@@ -112,7 +100,54 @@ int dx_hits_cut_plan(const dx_hit *hits, const uint32_t *start, uint64_t n_hits,
   rc = DX_OK;
 
 done:
-  free(sp); free(oi); free(ob); free(oe);
+  free(oi); free(ob); free(oe);
+  return rc;
+}
+
+/* what both entry points ask of their arguments before they look at a span; the outputs emptied */
+static int plan_args(const void *a, const void *b, uint64_t n, const uint32_t *rec_len, uint64_t records, int mode,
+                     uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids, dx_cut *report)
+{ if (ids == NULL || beg == NULL || end == NULL || n_ids == NULL) return DX_E_ARG;
+  *ids = NULL; *beg = NULL; *end = NULL; *n_ids = 0;
+  if (report) memset(report, 0, sizeof(*report));
+  if (mode != DX_CUT_SPLIT && mode != DX_CUT_LONGEST && mode != DX_CUT_DROP) return DX_E_ARG;
+  if ((n && (a == NULL || b == NULL)) || (records && rec_len == NULL)) return DX_E_ARG;
+  return DX_OK;
+}
+
+int dx_hits_cut_plan(const dx_hit *hits, const uint32_t *start, uint64_t n_hits, const uint32_t *rec_len, uint64_t records,
+                     uint32_t min_len, int mode, uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids, dx_cut *report)
+{ dx_span *sp;
+  uint64_t h;
+  int      rc;
+  if ((rc = plan_args(hits, start, n_hits, rec_len, records, mode, ids, beg, end, n_ids, report)) != DX_OK) return rc;
+  if ((sp = malloc(((size_t) n_hits + 1) * sizeof(*sp))) == NULL) return DX_E_NOMEM;
+  for (h = 0; h < n_hits; h++)
+    { if (hits[h].record >= records || start[h] > hits[h].pos || hits[h].pos > rec_len[hits[h].record]) { rc = DX_E_ARG; goto done; }
+      sp[h].record = hits[h].record; sp[h].beg = start[h]; sp[h].end = hits[h].pos;
+    }
+  rc = plan_spans(sp, n_hits, rec_len, records, min_len, mode, ids, beg, end, n_ids, report);
+
+done:
+  free(sp);
+  return rc;
+}
+
+int dx_spans_cut_plan(const dx_span *spans, uint64_t n, const uint32_t *rec_len, uint64_t records, uint32_t min_len, int mode,
+                      uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids, dx_cut *report)
+{ dx_span *sp;
+  uint64_t h;
+  int      rc;
+  if ((rc = plan_args(spans, spans, n, rec_len, records, mode, ids, beg, end, n_ids, report)) != DX_OK) return rc;
+  if ((sp = malloc(((size_t) n + 1) * sizeof(*sp))) == NULL) return DX_E_NOMEM;
+  for (h = 0; h < n; h++)
+    { if (spans[h].record >= records || spans[h].beg > spans[h].end || spans[h].end > rec_len[spans[h].record]) { rc = DX_E_ARG; goto done; }
+      sp[h] = spans[h];
+    }
+  rc = plan_spans(sp, n, rec_len, records, min_len, mode, ids, beg, end, n_ids, report);
+
+done:
+  free(sp);
   return rc;
 }
 

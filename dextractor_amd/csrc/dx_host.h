@@ -49,6 +49,15 @@ __attribute__((visibility("hidden"))) int dx_kmers_wide_fail(dx_ctx *ctx, int co
    screen/dx_screen.hip, for dx_file_screen.c */
 __attribute__((visibility("hidden"))) int dx_kmer_set_fail(dx_ctx *ctx, int code, const char *what);
 __attribute__((visibility("hidden"))) int dx_screen_fail(dx_ctx *ctx, int code, const char *what);
+/* ... and "<who>: <what>", defined in screen/dx_screen_spans.hip, for the two drivers of dx_file_screen_spans.c */
+__attribute__((visibility("hidden"))) int dx_screen_spans_fail(dx_ctx *ctx, int code, const char *who, const char *what);
+
+/* What dx_file_screen_spans wants of dx_code_kmer_spans beyond the C-ABI (screen/dx_screen_spans.hip): the list alone, for units whose
+   counts a counting call over the same arguments (d_beg NULL) has left in d_count -- the driver counts a slice first, to size the
+   list, and the look-ups are made once more, not twice.  *listed (may be NULL) = the counts' sum. */
+__attribute__((visibility("hidden"))) int dx_spans_list_counted(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_boff,
+                                                                const uint32_t *d_len, uint64_t n, const dx_kmer_set *set, uint32_t *d_count,
+                                                                dx_span *d_spans, uint64_t cap, uint64_t *listed);
 
 /* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
    arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their

@@ -42,84 +42,17 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in the
 // profiler's name table and are timed with events on the context's stream (tools/screen_rate.py).
-#include "kmers/dx_kmer_windows.hpp"
-#include "screen/dx_kmer_set.hpp"
+#include "screen/dx_screen_look.hpp"
 
 extern "C" {
 #include "dx_host.h"
 }
 
-#define SC_BATCH  8u                       // positions a lane asks for before it waits for any
-#define SC_LINEAR 4u                       // codes of a bucket that are looked at one after the other; more are bisected first
-#define SC_NONE   0xffffffffu
-
-// what a kernel needs of a dx_kmer_set
-struct sc_set { const uint64_t *code; const uint32_t *first; uint32_t k, shift; };     // shift = 2 k - p
-
 // ---------------------------------------------------------------------------------------------
-//  k_screen
+//  k_screen  (sc_set, sc_mask, sc_cover, sc_chunk_mask: screen/dx_screen_look.hpp, which k_spans shares)
 // ---------------------------------------------------------------------------------------------
-// the part's hit mask: bit bit0 + i = window i of the part is in the set (bit0 + p.n <= 64)
-template <bool CANON>
-__device__ __forceinline__ uint64_t sc_mask(const kc_part &p, uint32_t bit0, const sc_set &s)
-{ uint64_t m = 0ull;
-  if (p.n == 0u) return m;
-  kc_roll<CANON> r(p, s.k);
-  for (uint32_t i0 = 0; i0 < p.n; i0 += SC_BATCH)
-    { uint64_t c[SC_BATCH], v[SC_BATCH];
-      uint32_t lo[SC_BATCH], hi[SC_BATCH];
-      #pragma unroll
-      for (uint32_t t = 0; t < SC_BATCH; t++) { c[t] = r.code(); r.step(); }
-      #pragma unroll
-      for (uint32_t t = 0; t < SC_BATCH; t++)
-        { const uint64_t two = *(const u64_u *) (s.first + (c[t] >> s.shift));
-          lo[t] = (uint32_t) two; hi[t] = (uint32_t) (two >> 32);
-        }
-      #pragma unroll
-      for (uint32_t t = 0; t < SC_BATCH; t++)
-        { while (hi[t] - lo[t] > SC_LINEAR)                           // (a long bucket: a small p, or many codes that share their top bits)
-            { const uint32_t mid = lo[t] + (hi[t] - lo[t]) / 2u;
-              if (s.code[mid] <= c[t]) lo[t] = mid; else hi[t] = mid;
-            }
-          v[t] = lo[t] < hi[t] ? s.code[lo[t]] : ~c[t];
-        }
-      #pragma unroll
-      for (uint32_t t = 0; t < SC_BATCH; t++)
-        { bool hit = v[t] == c[t];
-          for (uint32_t j = lo[t] + 1u; !hit && j < hi[t] && v[t] < c[t]; j++)
-            { v[t] = s.code[j];
-              hit = v[t] == c[t];
-            }
-          if (hit && i0 + t < p.n) m |= 1ull << (bit0 + i0 + t);
-        }
-    }
-  return m;
-}
-
-// the positions of a chunk that lie in a hit window: the chunk's mask m and the mask of the chunk in front of it
-__device__ __forceinline__ uint64_t sc_cover(uint64_t m, uint64_t prev, uint32_t k)
-{ uint64_t hi = m, lo = prev;
-  uint32_t w = 1;
-  for (; 2u * w <= k; w *= 2u)                                         // (w < 64: k <= 32)
-    { hi |= (hi << w) | (lo >> (64u - w));
-      lo |= lo << w;
-    }
-  if (k > w)
-    { const uint32_t d = k - w;
-      hi |= (hi << d) | (lo >> (64u - d));
-    }
-  return hi;
-}
-
 // what a lane has gathered of a unit
 struct sc_acc { uint32_t hits, covered, first, last; };
-
-// chunk `a` (its byte) of the unit that is symbols [S0, S1) of the buffer: its mask; prev: the mask of the chunk in front
-template <bool CANON>
-__device__ __forceinline__ uint64_t sc_chunk_mask(const uint8_t *in, uint64_t bytes, uint64_t a, uint64_t S0, uint64_t S1, const sc_set &s)
-{ const kc_part p = kc_take(in, bytes, a, S0, S1, s.k);
-  return p.n ? sc_mask<CANON>(p, (uint32_t) (S0 + p.first - 4u * a), s) : 0ull;
-}
 
 // ... added to the lane's account; base = 4 a - S0: the chunk's first position as a symbol of the unit (negative in the first chunk)
 __device__ __forceinline__ void sc_add(sc_acc &x, uint64_t m, uint64_t prev, int64_t base, uint32_t k)

@@ -1191,6 +1191,74 @@ int dx_screen_select(const dx_screen *rec, const uint32_t *rec_len, uint64_t rec
                      int mode, uint64_t **ids, uint64_t *n_ids);
 
 /* ------------------------------------------------------------------------------------------
+ *  screen spans: WHERE a read matches the set, and the archive cut there  (csrc/screen/dx_screen_spans.hip, csrc/dx_file_screen_spans.c)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { uint64_t record; uint32_t beg, end; } dx_span;     /* 16 bytes: symbols [beg, end) of unit / record `record` */
+
+/* Units, windows and codes are dx_code_kmer_screen's: any byte offset and phase, d_beg in front of the unit, pad bits and foreign
+ * symbols part of no window, nothing outside [0, in_bytes) read, the set's k and canonical.  The SPANS of unit j are the maximal runs
+ * of symbols that lie in at least one window whose code is in the set -- the union of the [p, p + k) that dx_screen.covered counts,
+ * written out as intervals.  So every span has k symbols at least, two spans of a unit are one symbol apart at least, the lengths
+ * sum to dx_screen.covered, the first beg is dx_screen.first and the last end dx_screen.last + k.
+ * The list is in the order (unit, beg), the same bytes on every call (places come from counts and a prefix sum, no atomic cursor):
+ * d_spans (8-byte aligned) gets the first min(cap, spans) of them, each one complete, nothing at cap or beyond; cap == 0 counts only.
+ * d_count[j] (may be NULL) = unit j's spans, all of them (at most len / (k + 1) + 1: it does not saturate).  total[0 .. 3) (host) =
+ * the spans, listed or not, the covered symbols and the units with a span, over the good units.  A unit that does not lie inside
+ * the in_bytes has no spans, count 0, adds nothing; the smallest such j goes back in *bad_unit (UINT64_MAX otherwise; may be NULL)
+ * with DX_E_FORMAT, the other units' spans are made all the same.  One read-back a call, and with a list the prefix sum's besides.
+ * DX_E_ARG for a NULL set or another pointer that is needed, n >= 2^31, cap >= 2^32, a list or counts that are not aligned.        */
+int dx_code_kmer_spans(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                       const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                       const dx_kmer_set *set,
+                       uint32_t *d_count /* n; may be NULL: every unit's spans */,
+                       dx_span *d_spans /* cap entries; may be NULL when cap == 0 */, uint64_t cap,
+                       uint64_t total[3] /* host: spans, covered symbols, units with a span */,
+                       uint64_t *bad_unit /* may be NULL */);
+
+/* A list as dx_code_kmer_spans leaves it -- beg < end for every entry, the records not decreasing, end[i] <= beg[i + 1] within a
+ * record -- joined and filtered on the device: (1) consecutive spans of one record are joined while beg[i + 1] - end[i] <= max_gap,
+ * a joined span running from the first one's beg to the last one's end; (2) a joined span is kept if end - beg >= min_span.  The
+ * join comes first and the filter does not influence it; max_gap UINT32_MAX leaves one span a record.  d_out (8-byte aligned, not
+ * overlapping d_in) gets the first min(cap, kept) in the input's order, the same bytes on every call, nothing at cap or beyond;
+ * cap == 0 counts only.  total[0 .. 2) (host) = the spans kept, listed or not, and their symbols.  A joined span may take in any
+ * number of entries.  DX_E_FORMAT with *bad (may be NULL; UINT64_MAX otherwise) = the smallest index that breaks the input's
+ * order; the totals are 0 then and what d_out holds means nothing.  n == 0 launches nothing.  DX_E_ARG for a NULL pointer that is
+ * needed, a list that is not aligned, d_out overlapping d_in, cap >= 2^32, n >= 2^36.                                              */
+int dx_spans_join(dx_ctx *ctx, const dx_span *d_in, uint64_t n, uint32_t max_gap, uint32_t min_span,
+                  dx_span *d_out /* cap entries; not overlapping d_in */, uint64_t cap,
+                  uint64_t total[2] /* host: spans kept, their symbols */, uint64_t *bad /* may be NULL */);
+
+typedef struct { uint64_t records, symbols, covered, records_hit, raw_spans, spans, span_symbols, listed; uint32_t k, reserved; } dx_spans_report;   /* 72 bytes */
+
+/* The records of a .dexta / .dexar image screened against the set as dx_file_screen screens them (the same walk, the same slices, the
+ * same refusals), and per slice the raw spans counted, listed into a device list of exactly that size (DX_E_NOMEM, dx_last_error
+ * naming the bytes, if it cannot be had), joined and filtered (dx_spans_join: max_gap, min_span); only the joined, kept spans come
+ * down.  *spans (may be NULL; malloc'd, dx_file_free) has out->listed = min(out->spans, max_spans) of them in the order (record,
+ * beg), `record` being the image's record number; *rec_spans (may be NULL; malloc'd) = the kept spans of every record, listed or
+ * not; *rec_len (may be NULL; malloc'd) = every record's symbols.  out->covered, records_hit (dx_file_screen's) and raw_spans
+ * describe the raw spans, out->spans and span_symbols what the join and the filter keep.  A record lies in one slice: the answer
+ * does not depend on the slicing.  *out is untouched on any error.                                                               */
+int dx_file_screen_spans(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const dx_kmer_set *set,
+                         uint32_t max_gap, uint32_t min_span, uint64_t max_spans, dx_spans_report *out,
+                         dx_span **spans /* may be NULL; malloc'd, dx_file_free */,
+                         uint32_t **rec_spans /* may be NULL: kept spans a record */, uint32_t **rec_len /* may be NULL */);
+
+/* Host only, no GPU: dx_hits_cut_plan's plan over spans given directly -- symbols [beg, end) of record `record`, in any order; the
+ * modes, min_len, the union of spans that overlap or touch, the outputs and *report are dx_hits_cut_plan's.  DX_E_ARG for a span with
+ * beg > end, end > its record's length, record >= records, an unknown mode, a NULL pointer that is needed.                        */
+int dx_spans_cut_plan(const dx_span *spans, uint64_t n, const uint32_t *rec_len, uint64_t records, uint32_t min_len, int mode,
+                      uint64_t **ids, uint32_t **beg, uint32_t **end, uint64_t *n_ids, dx_cut *report /* may be NULL */);
+
+/* A .dexta / .dexar image with what matches the set cut out of its records: dx_file_screen_spans with every span listed,
+ * dx_spans_cut_plan, dx_file_subset.  Outputs, the selection handed back for the .dexar and the .dexqv of the same records, the
+ * modes and DX_E_DEGENERATE for a selection without a unit are dx_file_cut's; it never cuts from part of the spans (DX_E_NOMEM).
+ * DX_E_ARG for DX_KIND_QUIVA (cut its .dexta, then apply the selection), an unknown mode, and what dx_file_screen refuses.         */
+int dx_file_screen_cut(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const dx_kmer_set *set,
+                       uint32_t max_gap, uint32_t min_span, uint32_t min_len, int mode,
+                       uint8_t **out, size_t *out_len, dx_cut *report /* may be NULL */,
+                       uint64_t **ids /* may be NULL */, uint32_t **beg /* may be NULL */, uint32_t **end /* may be NULL */, uint64_t *n_ids /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
