@@ -293,6 +293,17 @@ SIGNATURES = {
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dx_file_kmers_wide": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(Kmers64), _P,
                                      C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "dx_code_kmer_bins": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, _P,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_code_kmer_codes_range": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dx_kmer_range_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P, C.POINTER(C.c_uint32)]),
+    "dx_files_kmers_wide": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                      C.POINTER(Kmers64), _P, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint64), _P,
+                                      C.POINTER(C.c_uint32)]),
+    "dx_sorted_take": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dx_files_kmer_set": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(_P),
+                                    C.POINTER(Kmers64), C.POINTER(C.c_uint32)]),
     "dx_kmer_code64": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     "dx_kmer_letters64": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_char_p]),
     "dx_kmer_set_from_codes": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -949,6 +949,106 @@ class Context:
         return self._file_kmers(self.lib.dx_file_kmers_wide, L.Kmers64(), KMER64_DTYPE, KMER64_LIST_DTYPE, kmer_letters64, kind, img, k,
                                 canonical, nspec, min_count, max_list)
 
+    # ---- ... of several files, in passes over ranges of the codes ------------------------------------------
+    def code_kmer_bins(self, d_in, boff, beg, length, k, bits, canonical=False, bins=None, in_bytes=None, n=None):
+        """dx_code_kmer_bins: the windows of code_kmer_codes' units counted by the top `bits` bits (1 to min(2 k, 12)) of their codes,
+        ADDED to bins[code >> (2 k - bits)].  bins: a device array of 2^bits 64-bit words; None: a zeroed DevBuf made here, the
+        caller's to free.  Returns (bins, windows of this call).  Raises DexGPUError: DX_E_FORMAT (.bad_unit, .windows) for a unit
+        outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        own = None
+        if bins is None:
+            bins = own = self.alloc(8 << max(0, min(int(bits), 12))).zero()
+        win, bad = C.c_uint64(), C.c_uint64()
+        rc = self.lib.dx_code_kmer_bins(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                        int(b_len // 4 if n is None else n), int(k), int(bool(canonical)), int(bits), _addr(bins),
+                                        C.byref(win), C.byref(bad))
+        if rc != 0:
+            if own:
+                own.free()
+            raise self._err(rc, bad_unit=_index(bad), windows=win.value)
+        return bins, win.value
+
+    def code_kmer_codes_range(self, d_in, boff, beg, length, k, bits, bin_lo, bin_hi, canonical=False, cap=None, codes=None,
+                              in_bytes=None, n=None):
+        """dx_code_kmer_codes_range: code_kmer_codes for the windows with bin_lo <= code >> (2 k - bits) < bin_hi alone, written
+        densely in the order (unit, position).  codes, cap as for code_kmer_codes (cap None without codes: room for every window).
+        Returns (codes, the windows kept).  Raises DexGPUError: DX_E_NOMEM (.windows = the windows kept) when cap is short,
+        DX_E_FORMAT (.bad_unit) for a unit outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        k, n = int(k), int(b_len // 4 if n is None else n)
+        own = None
+        if codes is None:
+            if cap is None:
+                ln = (length.cpu().numpy()[:n] if hasattr(length, "cpu") else length.download(np.uint32, n)).astype(np.int64)
+                cap = int(np.maximum(ln - k + 1, 0).sum())
+            codes = own = self.alloc(8 * int(cap) + 8)
+        elif cap is None:
+            cap = _dev(codes)[1] // 8
+        win, bad = C.c_uint64(), C.c_uint64()
+        rc = self.lib.dx_code_kmer_codes_range(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                               n, k, int(bool(canonical)), int(bits), int(bin_lo), int(bin_hi), _addr(codes), int(cap),
+                                               C.byref(win), C.byref(bad))
+        if rc != 0:
+            if own:
+                own.free()
+            raise self._err(rc, bad_unit=_index(bad), windows=win.value)
+        return codes, win.value
+
+    def sorted_take(self, sorted_codes, n, min_count=1, cap=0):
+        """dx_sorted_take of a sorted device array of n keys: (found: the runs of min_count keys at least, the first keys of the first
+        min(cap, found) of them as a uint64 array); cap 0 counts only."""
+        cap, found = int(cap), C.c_uint64()
+        own = self.alloc(8 * cap + 8) if cap > 0 else None
+        try:
+            self._chk(self.lib.dx_sorted_take(self.h, _addr(sorted_codes), int(n), int(min_count), _addr(own), cap, C.byref(found)))
+            return found.value, self._download(_addr(own), np.uint64, min(cap, found.value))
+        finally:
+            if own is not None:
+                own.free()
+
+    @staticmethod
+    def _images(imgs):
+        """a sequence of images (bytes) -> (what ctypes passes as const uint8_t *const *, as const size_t *, how many, what keeps them alive)"""
+        keep = [C.c_char_p(bytes(b)) for b in imgs]
+        n = len(keep)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.cast(p, C.c_void_p) for p in keep])
+        sizes = (C.c_size_t * max(n, 1))(*[len(b) for b in imgs])
+        return ptrs, sizes, n, keep
+
+    def kmers_wide_files(self, kind, imgs, k, canonical=False, nspec=256, min_count=0, max_list=0, room=0):
+        """dx_files_kmers_wide: kmers_wide over several images of one kind, counted into one answer -- in passes over ranges of the
+        codes when the windows do not fit the device at once.  room: the windows a pass may hold (16 bytes of device memory each), 0:
+        chosen from the free memory.  Returns (report, spectrum, list) as kmers_wide does; the report also has "passes" (the ranges
+        that were sorted) and "files": a {"records", "symbols", "windows"} an image."""
+        ptrs, sizes, n, keep = self._images(imgs)
+        kd, spec, km, cnt, passes = _kind(kind), np.zeros(int(nspec), np.uint64), L.Kmers64(), C.c_uint64(), C.c_uint32()
+        per = (L.Kmers64 * max(n, 1))()
+        with _Outs(self.lib, 1) as (lst,):
+            self._chk(self.lib.dx_files_kmers_wide(self.h, kd, ptrs, sizes, n, int(k), int(bool(canonical)), int(min_count), int(max_list),
+                                                   int(room), C.byref(km), spec.ctypes.data, int(nspec), C.byref(lst), C.byref(cnt), per,
+                                                   C.byref(passes)))
+            rep = _fields(km)
+            rep["listed"], rep["passes"] = cnt.value, passes.value
+            rep["files"] = [{f: getattr(per[i], f) for f in ("records", "symbols", "windows")} for i in range(n)]
+            got, out = _take(lst, KMER64_DTYPE, cnt.value), np.zeros(cnt.value, KMER64_LIST_DTYPE)
+            if cnt.value:
+                out["count"], out["code"] = got["count"], got["code"]
+                out["letters"] = [kmer_letters64(int(c), int(k), arrow=kind == "arrow") for c in got["code"]]
+            return rep, spec, out
+
+    def kmer_set_files(self, kind, imgs, k, canonical=False, min_count=1, room=0, report=False):
+        """dx_files_kmer_set: kmer_set over several images of one kind, by kmers_wide_files' passes.  report: (set, what
+        kmers_wide_files reports without its list and its files)."""
+        ptrs, sizes, n, keep = self._images(imgs)
+        h, km, passes = C.c_void_p(), L.Kmers64(), C.c_uint32()
+        self._chk(self.lib.dx_files_kmer_set(self.h, _kind(kind), ptrs, sizes, n, int(k), int(bool(canonical)), int(min_count), int(room),
+                                             C.byref(h), C.byref(km), C.byref(passes)))
+        s = KmerSet(self, h)
+        return (s, dict(_fields(km), passes=passes.value)) if report else s
+
     # ---- screen: the reads that share k-mers with a set ---------------------------------------------------
     def kmer_set(self, kind, img: bytes, k, canonical=False, min_count=1, report=False):
         """dx_file_kmer_set: the distinct k-mers (1 <= k <= 32) of a .dexta / .dexar image that are counted min_count times at least,
@@ -1374,6 +1474,18 @@ def kmer_letters64(code, k, arrow=False) -> bytes:
     if rc != 0:
         raise L.DexGPUError(rc, f"dx_kmer_letters64: code {code} is not one of {k} symbols, or k is not 1 to 32")
     return out.value
+
+
+def kmer_range_plan(bins, room) -> np.ndarray:
+    """dx_kmer_range_plan: the bins (what code_kmer_bins counted) cut into ranges of consecutive bins of at most `room` windows each,
+    greedily; room 0: one range.  Returns the cuts as a uint32 array: range r is bins [cut[r], cut[r + 1]), cut[0] = 0, cut[-1] =
+    len(bins).  Host only.  Raises DexGPUError (DX_E_NOMEM, the bin and its windows named) for a single bin above room."""
+    b = np.ascontiguousarray(np.asarray(bins, np.uint64))
+    cut, ranges, lib = np.zeros(len(b) + 1, np.uint32), C.c_uint32(), L.load()
+    rc = lib.dx_kmer_range_plan(None, b.ctypes.data if len(b) else None, len(b), int(room), cut.ctypes.data, C.byref(ranges))
+    if rc != 0:
+        raise _error(rc, _words(lib, None))
+    return cut[:ranges.value + 1].copy()
 
 
 def equery(*x):

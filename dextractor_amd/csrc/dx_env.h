@@ -6,7 +6,10 @@
  * forced for a test, a threshold lowered so that a small file takes the large files' path, a failure injected -- is a key of ONE
  * variable, DEXGPU_TEST: keys and key=value pairs separated by commas or blanks, e.g.
  *     DEXGPU_TEST="no_tokens,onepass_groups=3,device_walk_min=1"
- * looked up where the decision is made (never inside a kernel's launch loop); tests/ and tools/ set nothing else.
+ * looked up where the decision is made (never inside a kernel's launch loop); tests/ and tools/ set nothing else.  README.md lists
+ * the keys.  Three of them lower the figure from which a wave sweeps its workgroup's LDS counters into the global words, so that a
+ * test reaches the sweep at small shapes: hist_flush=<bytes> (dx_byte_hist_ranges), kmer_flush=<windows> (dx_code_kmers, k <= 7),
+ * bins_flush=<windows> (dx_code_kmer_bins).
  */
 #ifndef DX_ENV_H
 #define DX_ENV_H

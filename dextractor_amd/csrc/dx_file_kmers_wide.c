@@ -11,8 +11,8 @@
  * The image is opened and walked as dx_file_kmers_add walks it (dxf_image_open; slices of whole records under dxf_u2_cap /
  * DEXGPU_TEXT_BUDGET, handed over by dxf_u2_slices, dx_file_u2.c).  The windows are known from the lengths before anything is
  * allocated; the codes and the sort's second array stand on the device together, 16 bytes a window.  An image whose windows do not
- * fit that way is DX_E_NOMEM: passes over ranges of the codes are the next step, as is counting several files into one
- * answer.
+ * fit that way is DX_E_NOMEM here: dx_files_kmers_wide (dx_file_kmers_files.c) counts such an image, and several images into one
+ * answer, in passes over ranges of the codes.
  */
 #include <stdlib.h>
 #include <string.h>

@@ -1,7 +1,7 @@
 /*
  * dx_file_u2.c -- the packed reads of a walked .dexta / .dexar image on the device, slice by slice of whole records: dxf_u2_slices,
  * the one loop under every driver that works on the reads where they lie (dx_file_census, dx_file_find / _find_edit / _cut,
- * dx_file_kmers_add, dx_file_kmers_wide); and what decides the slices, dxf_u2_cap and dxf_u2_slice_end.
+ * dx_file_kmers_add, dx_file_kmers_wide, dx_files_kmers_wide); and what decides the slices, dxf_u2_cap and dxf_u2_slice_end.
  *
  * The decoded-text side has the same shape in dxf_unpack2_slices / dxf_undexqv_sliced and their slice_fn.  A slice here is the image's
  * bytes from its first record's packed read to its last one's end, every record's offset into them, and the lengths: what the unit

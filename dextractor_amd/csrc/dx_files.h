@@ -17,6 +17,7 @@
  *     dx_file_kmers.c  the k-mers of an image's reads, counted: dx_file_kmers_add, dx_file_kmers; dx_kmer_code, dx_kmer_letters (host)
  *     dx_file_kmers_wide.c  ... for k up to 32, counted by sorting: dx_file_kmers_wide; the same k-mers as a set on the device: dx_file_kmer_set;
  *                      dx_kmer_code64, dx_kmer_letters64 (host)
+ *     dx_file_kmers_files.c  ... of several images into one answer, in passes over ranges of the codes: dx_files_kmers_wide, dx_files_kmer_set
  *     dx_file_screen.c the records that share k-mers with a set: dx_file_screen; dx_screen_select (host)
  *     dx_file_screen_spans.c  WHERE a record matches the set, as joined intervals, and the image cut there: dx_file_screen_spans, dx_file_screen_cut
  *     dx_file_cut.c    what is kept of the records once the occurrences are cut out, and the image of it: dx_hits_cut_plan, dx_spans_cut_plan

@@ -45,6 +45,12 @@ __attribute__((visibility("hidden"))) int dx_cut_fail(dx_ctx *ctx, int code, con
 __attribute__((visibility("hidden"))) int dx_kmers_fail(dx_ctx *ctx, int code, const char *what);
 /* ... and "dx_file_kmers_wide: <what>", defined in kmers/dx_kmer_runs.hip, for dx_file_kmers_wide.c */
 __attribute__((visibility("hidden"))) int dx_kmers_wide_fail(dx_ctx *ctx, int code, const char *what);
+/* ... and "<who>: <what>", defined in kmers/dx_kmer_bins.hip, for the two drivers of dx_file_kmers_files.c; "<who>: image <i>: <the words
+   the walk left>" for an image that does not open (image < 0 empties the text and changes nothing else); and what they copy from one
+   device array to another, behind everything on the context's stream, which is waited for */
+__attribute__((visibility("hidden"))) int dx_kmers_files_fail(dx_ctx *ctx, int code, const char *who, const char *what);
+__attribute__((visibility("hidden"))) int dx_kmers_files_image_fail(dx_ctx *ctx, int code, const char *who, int64_t image);
+__attribute__((visibility("hidden"))) int dx_d2d(dx_ctx *ctx, void *d_dst, const void *d_src, size_t bytes);
 /* ... and "dx_file_kmer_set: <what>", defined in screen/dx_kmer_set.hip, for dx_file_kmers_wide.c, and "dx_file_screen: <what>", in
    screen/dx_screen.hip, for dx_file_screen.c */
 __attribute__((visibility("hidden"))) int dx_kmer_set_fail(dx_ctx *ctx, int code, const char *what);

@@ -1,6 +1,7 @@
 // dx_kmer_set.hip -- a set of k-mers that stays on the device, 1 <= k <= 32, for dx_code_kmer_screen (dx_screen.hip) to ask.
 //
-//   dx_kmer_set_from_sorted   a SORTED device array (what dx_sort_u64 leaves) -> the codes whose run has min_count keys at least
+//   dx_sorted_take            a SORTED device array (what dx_sort_u64 leaves) -> the first key of every run of min_count keys at least
+//   dx_kmer_set_from_sorted   ... and those codes as a set: dx_sorted_take counts them, then fills an array of exactly that size
 //   dx_kmer_set_from_codes    host codes, any order, repeats allowed: folded (canonical), uploaded, sorted, then the above
 //   dx_kmer_set_info / _codes / _free
 //
@@ -43,11 +44,11 @@ extern "C" {
 //  k_set_take
 // ---------------------------------------------------------------------------------------------
 // WRITE false: pass[t] = the runs of min_count keys at least that begin in tile t.  WRITE true: their first keys to out, from
-// start[t] on (the exclusive sums of the counts), in the order of the keys.  (need = min_count - 1 < n.)
+// start[t] on (the exclusive sums of the counts), in the order of the keys, none at cap or beyond.  (need = min_count - 1 < n.)
 template <bool WRITE>
 __global__ __launch_bounds__(DX_BLOCK)
 void k_set_take(const uint64_t *__restrict__ key, uint64_t n, uint64_t need, uint32_t *__restrict__ pass,
-                const uint64_t *__restrict__ start, uint64_t *__restrict__ out)
+                const uint64_t *__restrict__ start, uint64_t *__restrict__ out, uint64_t cap)
 { __shared__ uint32_t s_n[DX_WAVES_PER_BLK];
   const uint64_t i0 = (uint64_t) blockIdx.x * KS_TILE + (uint64_t) KS_ITEMS * threadIdx.x;
   uint64_t v[KS_ITEMS];
@@ -74,7 +75,10 @@ void k_set_take(const uint64_t *__restrict__ key, uint64_t n, uint64_t need, uin
   for (uint32_t w = 0; w < wave; w++) at += s_n[w];
   #pragma unroll
   for (uint32_t j = 0; j < KS_ITEMS; j++)
-    if (take[j]) out[at++] = v[j];
+    if (take[j])
+      { if (at < cap) out[at] = v[j];
+        at++;
+      }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -128,6 +132,38 @@ extern "C" int dx_kmer_set_free(dx_ctx *ctx, dx_kmer_set *set)
   return DX_OK;
 }
 
+extern "C" int dx_sorted_take(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count, uint64_t *d_out, uint64_t cap,
+                              uint64_t *found)
+{ const char *who = "dx_sorted_take";
+  if (ctx == NULL) return DX_E_ARG;
+  if (found) *found = 0;
+  if (found == NULL || (d_sorted == NULL && n) || (d_out == NULL && cap)) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
+  if (min_count < 1u) return dx_fail(ctx, DX_E_ARG, "%s: min_count 0 (1 at least: the unseen codes are in no set)", who);
+  if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
+  DX_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = dx_after_pending(ctx);
+  if (rc != DX_OK) return rc;
+
+  // the runs that pass, a tile: counted, and summed to every tile's first place
+  const uint64_t tiles = (n + KS_TILE - 1u) / KS_TILE, need = min_count - 1u;
+  uint64_t      *d_start = NULL;
+  uint32_t      *d_pass = NULL;
+  if (n == 0 || need >= n) return DX_OK;
+  if ((rc = dx_scratch(ctx, (tiles + 1u + (tiles + 1u) / 2u) * 8u, (void **) &d_start)) != DX_OK) return rc;
+  d_pass = (uint32_t *) (d_start + tiles + 1u);
+  hipLaunchKernelGGL(k_set_take<false>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, d_pass,
+                     (const uint64_t *) NULL, (uint64_t *) NULL, (uint64_t) 0);
+  DX_HIP(ctx, hipGetLastError());
+  if ((rc = dx_scan_u32(ctx, d_pass, tiles, d_start, found)) != DX_OK) return rc;
+  if (cap && *found)
+    { hipLaunchKernelGGL(k_set_take<true>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, (uint32_t *) NULL,
+                         (const uint64_t *) d_start, d_out, cap);
+      DX_HIP(ctx, hipGetLastError());
+      DX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the caller may free d_sorted; the scratch is free again)
+    }
+  return DX_OK;
+}
+
 extern "C" int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count, uint32_t k, int canonical,
                                        int arrow, dx_kmer_set **set)
 { const char *who = "dx_kmer_set_from_sorted";
@@ -140,20 +176,10 @@ extern "C" int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, ui
   if (min_count < 1u) return dx_fail(ctx, DX_E_ARG, "%s: min_count 0 (1 at least: the unseen codes are in no set)", who);
   if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
   DX_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = dx_after_pending(ctx)) != DX_OK) return rc;
 
-  // the runs that pass, a tile: counted, and summed to every tile's first place
-  const uint64_t tiles = (n + KS_TILE - 1u) / KS_TILE, need = min_count - 1u;
-  uint64_t      *d_start = NULL, found = 0;
-  uint32_t      *d_pass = NULL;
-  if (n && need < n)
-    { if ((rc = dx_scratch(ctx, (tiles + 1u + (tiles + 1u) / 2u) * 8u, (void **) &d_start)) != DX_OK) return rc;
-      d_pass = (uint32_t *) (d_start + tiles + 1u);
-      hipLaunchKernelGGL(k_set_take<false>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, d_pass,
-                         (const uint64_t *) NULL, (uint64_t *) NULL);
-      DX_HIP(ctx, hipGetLastError());
-      if ((rc = dx_scan_u32(ctx, d_pass, tiles, d_start, &found)) != DX_OK) return rc;
-    }
+  // counted first: the set's array has exactly the size (the tiles are counted once more when it is filled: 8 bytes a key, beside a sort)
+  uint64_t found = 0, again = 0;
+  if ((rc = dx_sorted_take(ctx, d_sorted, n, min_count, NULL, 0, &found)) != DX_OK) return rc;
   if (found >= KS_NMAX)
     return dx_fail(ctx, DX_E_ARG, "%s: %llu codes in the set (fewer than 2^32 - 1)", who, (unsigned long long) found);
 
@@ -164,17 +190,15 @@ extern "C" int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, ui
   const uint64_t buckets = 1ull << s->bits;
   s->device_bytes = found * 8u + (buckets + 1u) * 4u;
   if ((rc = dx_malloc(ctx, (size_t) found * 8u + 64u, (void **) &s->d_codes)) != DX_OK ||
-      (rc = dx_malloc(ctx, (size_t) (buckets + 1u) * 4u + 64u, (void **) &s->d_first)) != DX_OK)
+      (rc = dx_malloc(ctx, (size_t) (buckets + 1u) * 4u + 64u, (void **) &s->d_first)) != DX_OK ||
+      (found && (rc = dx_sorted_take(ctx, d_sorted, n, min_count, s->d_codes, found, &again)) != DX_OK))
     { (void) dx_kmer_set_free(ctx, s);                   // (dx_malloc has left the words)
       return rc;
     }
-  if (found)
-    hipLaunchKernelGGL(k_set_take<true>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, (uint32_t *) NULL,
-                       (const uint64_t *) d_start, s->d_codes);
   hipLaunchKernelGGL(k_set_index, dim3((unsigned) ((buckets + 1u + DX_BLOCK - 1u) / DX_BLOCK)), dim3(DX_BLOCK), 0, ctx->stream,
                      (const uint64_t *) s->d_codes, (uint32_t) found, s->bits, 2u * k - s->bits, s->d_first);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (the caller may free d_sorted; the scratch is free again)
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (the caller may free d_sorted)
   if (e != hipSuccess)
     { (void) dx_kmer_set_free(ctx, s);
       return dx_fail(ctx, DX_E_HIP, "%s: %s", who, hipGetErrorString(e));

@@ -1111,6 +1111,51 @@ int dx_file_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint
                        uint64_t *spectrum /* host, nspec; may be NULL */, uint32_t nspec,
                        dx_kmer64 **list /* may be NULL; malloc'd, dx_file_free */, uint64_t *listed);
 
+/* How the windows of dx_code_kmer_codes spread over the top `bits` bits of their codes (csrc/kmers/dx_kmer_bins.hip): every window adds
+ * one to d_bins[code >> (2 k - bits)], the canonical code's with canonical; d_bins: 2^bits 64-bit words on the device, ADDED to;
+ * 1 <= bits <= min(2 k, 12).  Units, the bounds check, *windows (may be NULL) and *bad_unit are dx_code_kmer_codes': a unit that does
+ * not lie inside the in_bytes adds nothing and is DX_E_FORMAT, the good units counted all the same.  DX_E_ARG for k outside 1..32,
+ * bits out of range, a NULL pointer that is needed, n >= 2^31.  n == 0 changes nothing.                                              */
+int dx_code_kmer_bins(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                      const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                      uint32_t k /* 1..32 */, int canonical, uint32_t bits /* 1..min(2 k, 12) */,
+                      uint64_t *d_bins /* 2^bits, added to */, uint64_t *windows /* host; may be NULL */, uint64_t *bad_unit /* may be NULL */);
+
+/* dx_code_kmer_codes for a range of the codes (csrc/kmers/dx_kmer_codes_range.hip): only the windows with
+ * bin_lo <= code >> (2 k - bits) < bin_hi are written, densely, in the order (unit, position) -- the same array on every call; the
+ * places come from a counting launch and a prefix sum, no atomic cursor.  bits as for dx_code_kmer_bins, 0 <= bin_lo <= bin_hi <=
+ * 2^bits (bins state the range so that k = 32 needs no 2^64).  *windows = the windows KEPT.  If that exceeds cap nothing is written
+ * and the call is DX_E_NOMEM, *windows still set.  *bad_unit, DX_E_FORMAT and DX_E_ARG as for dx_code_kmer_codes, and DX_E_ARG for
+ * bits or the bins out of range.                                                                                                     */
+int dx_code_kmer_codes_range(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                             const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                             uint32_t k /* 1..32 */, int canonical, uint32_t bits, uint32_t bin_lo, uint32_t bin_hi,
+                             uint64_t *d_codes, uint64_t cap /* keys of room */, uint64_t *windows /* host */, uint64_t *bad_unit /* may be NULL */);
+
+/* Host only (ctx may be NULL: it is where the error text goes).  bins[0 .. nbins) cut into ranges of consecutive bins: cut[0] = 0 <
+ * ... < cut[*ranges] = nbins (cut has room for nbins + 1), range r = bins [cut[r], cut[r + 1]).  Greedy: a range takes bins while its
+ * sum stays <= room; an empty bin costs nothing and never begins a range.  room == 0, or everything fitting, gives one range.  A
+ * single bin above room is DX_E_NOMEM, and dx_last_error names the bin and its windows.  DX_E_ARG for a NULL pointer, nbins == 0.    */
+int dx_kmer_range_plan(dx_ctx *ctx, const uint64_t *bins, uint32_t nbins, uint64_t room, uint32_t *cut /* nbins + 1 */, uint32_t *ranges);
+
+/* dx_file_kmers_wide over SEVERAL images of one kind, counted into one answer, in passes over ranges of the codes when the windows do
+ * not fit the device at once (csrc/dx_file_kmers_files.c).  room: the windows a pass may hold, 16 bytes of device memory each; 0: chosen
+ * -- 0.8 x the free memory / 16 --; 2^36 - 1 at most.  All windows within room: ONE pass, whose launches are dx_file_kmers_wide's,
+ * image after image.  Otherwise the windows are counted by the top min(2 k, 12) bits of their codes (dx_code_kmer_bins),
+ * dx_kmer_range_plan cuts the bins into ranges, and every range, ascending, is written (dx_code_kmer_codes_range over all images),
+ * sorted and read off its runs; a single bin above room is DX_E_NOMEM (dx_last_error names it).  The ranges' answers concatenate:
+ * spectra and distinct add, the list takes the ranges' entries one behind the other up to max_list, max_code is the smallest code
+ * with the largest count.  The images are uploaded once a pass.  The meaning of every argument that dx_file_kmers_wide has, and of
+ * *out, is its own, summed over the images; per_file[i] (nimg of them; may be NULL): image i's records, symbols, windows and k, the
+ * rest zero; *passes (may be NULL): the ranges that were sorted, 0 when there is no window.  nimg == 0 is the empty answer.  The
+ * refusals are dx_file_kmers_wide's; an image that does not open is dx_file_unpack2's error, and dx_last_error names it ("image 1").
+ * On any error *out, the caller's spectrum, per_file and *passes are untouched, *list is NULL and no device memory stays behind.    */
+int dx_files_kmers_wide(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k /* 1..32 */,
+                        int canonical, uint64_t min_count, uint64_t max_list, uint64_t room /* windows a pass; 0: chosen */,
+                        dx_kmers64 *out, uint64_t *spectrum /* host, nspec; may be NULL */, uint32_t nspec,
+                        dx_kmer64 **list /* may be NULL; malloc'd, dx_file_free */, uint64_t *listed,
+                        dx_kmers64 *per_file /* nimg; may be NULL */, uint32_t *passes /* may be NULL */);
+
 /* dx_kmer_code and dx_kmer_letters for 1 <= k <= 32.  Host only.  DX_E_ARG for k outside 1..32, a letter that is not the kind's (the
  * text's end among them), a code of more than 2 k bits (k < 32), a NULL pointer.                                                  */
 int dx_kmer_code64(int arrow, const char *letters, uint32_t k, int canonical, uint64_t *code);
@@ -1145,6 +1190,22 @@ int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, u
  * dx_file_kmers_wide reports for the image.  The refusals and errors are dx_file_kmers_wide's, and min_count 0.                   */
 int dx_file_kmer_set(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count,
                      dx_kmer_set **set, dx_kmers64 *out /* may be NULL */);
+
+/* The first key of every run of min_count (>= 1) keys at least of a SORTED device array of n keys, in the order of the keys:
+ * *found = how many there are, d_out gets the first min(cap, *found) of them, nothing at cap or beyond; cap == 0 counts only.  What
+ * dx_kmer_set_from_sorted makes its codes with.  The array is only read; places come from counts and a prefix sum, the same array on
+ * every call.  DX_E_ARG for a NULL pointer that is needed (d_out may be NULL when cap == 0), min_count 0, n >= 2^36.                */
+int dx_sorted_take(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count /* >= 1 */,
+                   uint64_t *d_out /* cap; may be NULL when cap == 0 */, uint64_t cap, uint64_t *found);
+
+/* dx_file_kmer_set over SEVERAL images of one kind: dx_files_kmers_wide's passes; after each range's sort dx_sorted_take counts the
+ * kept codes and writes them into a device array of exactly that size, and at the end the arrays are copied one behind the other on
+ * the device -- the ranges ascend, so the result is sorted and distinct -- and handed to dx_kmer_set_from_sorted (min_count 1).
+ * *out (may be NULL) is what dx_files_kmers_wide reports; room and *passes (may be NULL) are its own.  The refusals and errors are
+ * dx_files_kmers_wide's, and min_count 0.  *set is NULL on any error, and no device memory stays behind.                             */
+int dx_files_kmer_set(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k, int canonical,
+                      uint64_t min_count, uint64_t room /* windows a pass; 0: chosen */, dx_kmer_set **set, dx_kmers64 *out /* may be NULL */,
+                      uint32_t *passes /* may be NULL */);
 
 int dx_kmer_set_info(const dx_kmer_set *set, dx_set_info *info);
 /* the codes back, ascending: out (host) has room for cap of them; DX_E_NOMEM when that is fewer than the set holds */
