@@ -329,15 +329,10 @@ extern "C" int dx_code_find_edit(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_b
 
   // one scratch block: the frame and the nq totals, then (with a list) every unit's first place and its room
   units_frame    f;
-  uint64_t       back[UF_OUT + FE_QMAX], *d_w = NULL;
+  uint64_t       back[UF_OUT + FE_QMAX], *d_start = NULL;
+  uint32_t      *d_room = NULL;
   const uint64_t bound = in_bytes;
-  const size_t   words = UF_OUT + FE_QMAX;
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_scratch(ctx, (words + (cap ? n + 1u + (n + 1u) / 2u : 0u)) * 8u, (void **) &d_w);
-  if (rc != DX_OK) return rc;
-  uint64_t *d_start = cap ? d_w + words : NULL;
-  uint32_t *d_room  = cap ? (uint32_t *) (d_start + n + 1u) : NULL;
-  rc = units_begin(ctx, "dx_code_find_edit", n, d_boff && d_len && (d_in || !in_bytes), d_w, FE_QMAX, 16, &d_in, &in_bytes, &f);
+  int rc = units_list_begin(ctx, "dx_code_find_edit", n, d_boff && d_len && (d_in || !in_bytes), FE_QMAX, 16, cap != 0, &d_in, &in_bytes, &f, &d_start, &d_room);
   if (rc != DX_OK) return rc;
   const int      grid   = dx_grid_waves(ctx, n, 16);
   const uint32_t target = FE_TARGET / nq > FE_FLOOR ? FE_TARGET / nq : FE_FLOOR;
@@ -347,14 +342,11 @@ extern "C" int dx_code_find_edit(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_b
                      d_count, d_room, (const uint64_t *) NULL, (u32x4_u *) NULL, cap, f.out, f.bad, f.ticket);
   if (cap)
     { uint64_t listed = 0;
-      DX_HIP(ctx, hipGetLastError());
-      if ((rc = dx_scan_u32(ctx, d_room, n, d_start, &listed)) != DX_OK) return rc;
+      if ((rc = units_list_places(ctx, f, d_room, n, d_start, &listed)) != DX_OK) return rc;
       if (listed)
-        { DX_HIP(ctx, hipMemsetAsync(f.ticket, 0, 4, ctx->stream));           // (the counter; the units a ticket stay)
-          hipLaunchKernelGGL(k_find_edit<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len, n,
-                             Q, nq, (uint32_t *) NULL, d_room, (const uint64_t *) d_start, (u32x4_u *) d_hits, cap,
-                             (unsigned long long *) NULL, f.bad, f.ticket);
-        }
+        hipLaunchKernelGGL(k_find_edit<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len, n,
+                           Q, nq, (uint32_t *) NULL, d_room, (const uint64_t *) d_start, (u32x4_u *) d_hits, cap,
+                           (unsigned long long *) NULL, f.bad, f.ticket);
     }
   rc = units_end(ctx, f, back, bad_unit, "%s: unit %llu does not lie inside the %llu packed bytes", bound);
   for (uint32_t k = 0; k < nq; k++)

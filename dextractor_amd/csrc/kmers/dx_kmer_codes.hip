@@ -145,19 +145,14 @@ extern "C" int dx_code_kmer_codes(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_
 
   // one scratch block: the frame, then every unit's first place (n + 1) and its windows (n)
   units_frame    f;
-  uint64_t       back[UF_OUT + 1], *d_w = NULL, total = 0;
+  uint64_t       back[UF_OUT + 1], *d_off = NULL, total = 0;
+  uint32_t      *d_win = NULL;
   const uint64_t bound = in_bytes;
-  const size_t   words = UF_OUT + 1;
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_scratch(ctx, (words + n + 1u + (n + 1u) / 2u) * 8u, (void **) &d_w);
-  if (rc != DX_OK) return rc;
-  uint64_t *d_off = d_w + words;
-  uint32_t *d_win = (uint32_t *) (d_off + n + 1u);
-  rc = units_begin(ctx, "dx_code_kmer_codes", n, d_boff && d_len && (d_in || !in_bytes), d_w, 1, 16, &d_in, &in_bytes, &f);
+  int rc = units_list_begin(ctx, "dx_code_kmer_codes", n, d_boff && d_len && (d_in || !in_bytes), 1, 16, true, &d_in, &in_bytes, &f, &d_off, &d_win);
   if (rc != DX_OK) return rc;
   hipLaunchKernelGGL(k_kc_windows, dim3((unsigned) ((n + DX_BLOCK - 1u) / DX_BLOCK)), dim3(DX_BLOCK), 0, ctx->stream, d_boff, d_beg, d_len, n,
                      bound, k, d_win);
-  DX_HIP(ctx, hipGetLastError());
+  DX_HIP(ctx, hipGetLastError());                          // (no ticket has been drawn yet: the first is, after the scan)
   if ((rc = dx_scan_u32(ctx, d_win, n, d_off, &total)) != DX_OK) return rc;
   *windows = total;
   if (total > cap)

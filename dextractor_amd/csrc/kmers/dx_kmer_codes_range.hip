@@ -176,30 +176,21 @@ extern "C" int dx_code_kmer_codes_range(dx_ctx *ctx, const uint8_t *d_in, uint64
 
   // one scratch block: the frame, then every unit's first place (n + 1) and its kept windows (n)
   units_frame    f;
-  uint64_t       back[UF_OUT + 1], *d_w = NULL, total = 0;
+  uint64_t       back[UF_OUT + 1], *d_off = NULL, total = 0;
+  uint32_t      *d_win = NULL;
   const uint64_t bound = in_bytes;
-  const size_t   words = UF_OUT + 1;
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_scratch(ctx, (words + n + 1u + (n + 1u) / 2u) * 8u, (void **) &d_w);
-  if (rc != DX_OK) return rc;
-  uint64_t *d_off = d_w + words;
-  uint32_t *d_win = (uint32_t *) (d_off + n + 1u);
-  rc = units_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), d_w, 1, 16, &d_in, &in_bytes, &f);
+  int rc = units_list_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), 1, 16, true, &d_in, &in_bytes, &f, &d_off, &d_win);
   if (rc != DX_OK) return rc;
   const kr_keep K    = { 2u * k - bits, bin_lo, bin_hi - bin_lo };
   const int     grid = dx_grid_waves(ctx, n, 16);
   hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
                      KC_TARGET, KC_BATCH, f.ticket);
   kr_launch<false>(ctx, grid, canonical, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, K, d_win, (const uint64_t *) NULL, (uint64_t *) NULL, f);
-  DX_HIP(ctx, hipGetLastError());
-  if ((rc = dx_scan_u32(ctx, d_win, n, d_off, &total)) != DX_OK) return rc;
+  if ((rc = units_list_places(ctx, f, d_win, n, d_off, &total)) != DX_OK) return rc;
   *windows = total;
   if (total > cap)
     return dx_fail(ctx, DX_E_NOMEM, "%s: %llu windows in the range, and room for %llu codes", who, (unsigned long long) total, (unsigned long long) cap);
 
-  if (total)
-    { DX_HIP(ctx, hipMemsetAsync(f.ticket, 0, sizeof(uint32_t), ctx->stream));                       // (the counter alone: the units a ticket stay)
-      kr_launch<true>(ctx, grid, canonical, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, K, (uint32_t *) NULL, (const uint64_t *) d_off, d_codes, f);
-    }
+  if (total) kr_launch<true>(ctx, grid, canonical, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, K, (uint32_t *) NULL, (const uint64_t *) d_off, d_codes, f);
   return units_end(ctx, f, back, bad_unit, "%s: unit %llu does not lie inside the %llu packed bytes", bound);
 }

@@ -68,10 +68,7 @@
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in
 // the profiler's name table and are timed with events on the context's stream (tools/kmer_rate.py).
 #include "units/dx_units.hpp"
-
-extern "C" {
-#include "dx_host.h"
-}
+#include "tiles/dx_tiles.hpp"
 
 #define KM_KMAX    14u                     // 4^14 cells of 8 bytes: 2 GiB
 #define KM_LDS_K   7u                      // up to here the table stands in LDS
@@ -85,7 +82,6 @@ extern "C" {
 #define KM_BLOCK   8u                      // positions between two moves of the words
 #define KM_FLUSH   (1ull << 29)            // windows a wave takes between two sweeps of the workgroup's cells
 #define KM_BINS    4096u                   // bins of the spectrum that stand in LDS
-#define KM_TILE    2048u                   // cells a workgroup lists: 8 a thread
 #define KM_EVEN    0x55555555u
 
 
@@ -287,66 +283,40 @@ void k_kmers(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
 // ---------------------------------------------------------------------------------------------
 //  k_kmer_spectrum
 // ---------------------------------------------------------------------------------------------
-struct km_block_out { unsigned long long distinct, max_count, max_code; };       // a workgroup's: its cells in use, the largest, its smallest code
-
-// spec: nspec words (nspec 0: none) the workgroups add their bins to; per: a km_block_out a workgroup
+// spec: nspec words (nspec 0: none) the workgroups add their bins to; per: a tile_figures a workgroup
 __global__ __launch_bounds__(DX_BLOCK)
 void k_kmer_spectrum(const unsigned long long *__restrict__ table, uint64_t cells, uint32_t nspec,
-                     unsigned long long *__restrict__ spec, km_block_out *__restrict__ per)
-{ __shared__ uint32_t           s_bin[KM_BINS];
-  __shared__ unsigned long long s_d[DX_WAVES_PER_BLK], s_m[DX_WAVES_PER_BLK], s_c[DX_WAVES_PER_BLK];
-  const uint32_t inside = nspec < KM_BINS ? nspec : KM_BINS;
-  for (uint32_t b = threadIdx.x; b < inside; b += DX_BLOCK) s_bin[b] = 0u;
-  __syncthreads();
+                     unsigned long long *__restrict__ spec, tile_figures *__restrict__ per)
+{ __shared__ uint32_t     s_bin[KM_BINS];
+  __shared__ tile_figures s_g[DX_WAVES_PER_BLK];
+  spectrum_begin(nspec, KM_BINS, s_bin);
 
-  unsigned long long d = 0, m = 0, mc = 0;
+  tile_figures g = { 0ull, 0ull, 0ull };
   const uint64_t stride = (uint64_t) gridDim.x * DX_BLOCK;
   for (uint64_t c = (uint64_t) blockIdx.x * DX_BLOCK + threadIdx.x; c < cells; c += stride)
     { const unsigned long long v = table[c];
       if (v == 0ull) continue;
-      d++;
-      if (v > m) { m = v; mc = c; }                        // (a lane's codes ascend: of equal counts the first stays)
-      if (nspec)
-        { const uint32_t b = v < (unsigned long long) (nspec - 1u) ? (uint32_t) v : nspec - 1u;
-          if (b < KM_BINS) atomicAdd(s_bin + b, 1u);
-          else             atomicAdd(spec + b, 1ull);
-        }
+      figures_note(g, v, c);                               // (a lane's codes ascend)
+      spectrum_bin(v, nspec, KM_BINS, s_bin, spec);
     }
-  #pragma unroll
-  for (int s = 32; s > 0; s >>= 1)
-    { const unsigned long long om = __shfl_xor(m, s), oc = __shfl_xor(mc, s);
-      d += __shfl_xor(d, s);
-      if (om > m || (om == m && oc < mc)) { m = om; mc = oc; }
-    }
-  if (lane_id() == 0) { s_d[threadIdx.x / DX_WAVE] = d; s_m[threadIdx.x / DX_WAVE] = m; s_c[threadIdx.x / DX_WAVE] = mc; }
-  __syncthreads();
-  if (threadIdx.x == 0u)
-    { for (uint32_t w = 1; w < DX_WAVES_PER_BLK; w++)
-        { d += s_d[w];
-          if (s_m[w] > m || (s_m[w] == m && s_c[w] < mc)) { m = s_m[w]; mc = s_c[w]; }
-        }
-      per[blockIdx.x].distinct = d; per[blockIdx.x].max_count = m; per[blockIdx.x].max_code = m ? mc : 0ull;
-    }
-  for (uint32_t b = threadIdx.x; b < inside; b += DX_BLOCK)
-    if (s_bin[b]) atomicAdd(spec + b, (unsigned long long) s_bin[b]);
+  figures_fold(g, s_g, per);
+  spectrum_flush(nspec, KM_BINS, s_bin, spec);
 }
 
 // ---------------------------------------------------------------------------------------------
 //  k_kmer_tiles, k_kmer_list
 // ---------------------------------------------------------------------------------------------
-// tile t is cells [KM_TILE t, KM_TILE (t + 1)), thread x of its workgroup has cells 8 x .. 8 x + 7 of it
+// tile t is cells [TL_TILE t, TL_TILE (t + 1)), thread x of its workgroup has cells 8 x .. 8 x + 7 of it
 __global__ __launch_bounds__(DX_BLOCK)
 void k_kmer_tiles(const unsigned long long *__restrict__ table, uint64_t cells, uint64_t min_count, uint32_t *__restrict__ count)
 { __shared__ uint32_t s_n[DX_WAVES_PER_BLK];
-  const uint64_t c0 = (uint64_t) blockIdx.x * KM_TILE + 8u * threadIdx.x;
+  const uint64_t c0 = (uint64_t) blockIdx.x * TL_TILE + TL_ITEMS * threadIdx.x;
   uint32_t mine = 0;
   #pragma unroll
-  for (uint32_t j = 0; j < 8u; j++)
+  for (uint32_t j = 0; j < TL_ITEMS; j++)
     if (c0 + j < cells && table[c0 + j] >= min_count) mine++;
-  const uint32_t all = wave_sum(mine);
-  if (lane_id() == 0) s_n[threadIdx.x / DX_WAVE] = all;
-  __syncthreads();
-  if (threadIdx.x == 0u) count[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+  const uint32_t all = tile_total(mine, s_n);
+  if (threadIdx.x == 0u) count[blockIdx.x] = all;
 }
 
 // start: every tile's first place in the list (dx_scan_u32 of the counts); an entry is 16 bytes: count (8), code (4), 0 (4)
@@ -354,37 +324,31 @@ __global__ __launch_bounds__(DX_BLOCK)
 void k_kmer_list(const unsigned long long *__restrict__ table, uint64_t cells, uint64_t min_count,
                  const uint64_t *__restrict__ start, u32x4_u *__restrict__ out, uint64_t cap)
 { __shared__ uint32_t s_n[DX_WAVES_PER_BLK];
-  const uint64_t first = start[blockIdx.x];
-  if (first >= cap) return;                                // (uniform: the whole workgroup leaves)
-  const uint64_t c0 = (uint64_t) blockIdx.x * KM_TILE + 8u * threadIdx.x;
-  unsigned long long v[8];
+  uint64_t first;
+  if (tile_idle(start, blockIdx.x, cap, first)) return;
+  const uint64_t c0 = (uint64_t) blockIdx.x * TL_TILE + TL_ITEMS * threadIdx.x;
+  unsigned long long v[TL_ITEMS];
   uint32_t mine = 0;
   #pragma unroll
-  for (uint32_t j = 0; j < 8u; j++)
+  for (uint32_t j = 0; j < TL_ITEMS; j++)
     { v[j] = c0 + j < cells ? table[c0 + j] : 0ull;
       if (c0 + j < cells && v[j] >= min_count) mine++;
     }
-  const uint32_t incl = wave_incl_scan(mine), wave = threadIdx.x / DX_WAVE;
-  if (lane_id() == 63) s_n[wave] = incl;
-  __syncthreads();
-  uint64_t at = first + (incl - mine);
-  for (uint32_t w = 0; w < wave; w++) at += s_n[w];
+  uint64_t at = tile_place(mine, first, s_n);
   #pragma unroll
-  for (uint32_t j = 0; j < 8u; j++)
+  for (uint32_t j = 0; j < TL_ITEMS; j++)
     if (c0 + j < cells && v[j] >= min_count)
-      { if (at < cap)
-          { u32x4 e;
-            e.x = (uint32_t) v[j]; e.y = (uint32_t) (v[j] >> 32); e.z = (uint32_t) (c0 + j); e.w = 0u;
-            out[at] = e;
-          }
-        at++;
-      }
+      tile_put(at, cap, [&](uint64_t to)
+        { u32x4 e;
+          e.x = (uint32_t) v[j]; e.y = (uint32_t) (v[j] >> 32); e.z = (uint32_t) (c0 + j); e.w = 0u;
+          out[to] = e;
+        });
 }
 
 // ---------------------------------------------------------------------------------------------
 //  the entry points
 // ---------------------------------------------------------------------------------------------
-static_assert(sizeof(dx_kmer) == 16 && sizeof(dx_kmers) == 48 && sizeof(km_block_out) == 24, "an entry of the list is one 16-byte store");
+static_assert(sizeof(dx_kmer) == 16 && sizeof(dx_kmers) == 48 && sizeof(tile_figures) == 24, "an entry of the list is one 16-byte store");
 
 template <bool CANON, bool LDS>
 static int km_launch(dx_ctx *ctx, int grid, size_t lds, const uint8_t *d_in, uint64_t in_bytes, uint64_t bound, const uint64_t *d_boff,
@@ -446,25 +410,13 @@ extern "C" int dx_kmer_spectrum(dx_ctx *ctx, const uint64_t *d_table, uint32_t k
   if (rc != DX_OK) return rc;
   const uint64_t cells = 1ull << (2u * k);
   const int      grid  = dx_grid_waves(ctx, (cells + 63u) / 64u, 8);
-  const size_t   words = (size_t) nspec + 3u * (size_t) grid;
-  uint64_t      *d_w   = NULL;
-  if ((rc = dx_scratch(ctx, words * 8u, (void **) &d_w)) != DX_OK) return rc;
+  uint64_t      *d_w   = NULL, mc = 0;
+  if ((rc = dx_scratch(ctx, figures_words(nspec, grid) * 8u, (void **) &d_w)) != DX_OK) return rc;
   if (nspec) DX_HIP(ctx, hipMemsetAsync(d_w, 0, (size_t) nspec * 8u, ctx->stream));
   hipLaunchKernelGGL(k_kmer_spectrum, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, (const unsigned long long *) d_table, cells, nspec,
-                     (unsigned long long *) d_w, (km_block_out *) (d_w + nspec));
+                     (unsigned long long *) d_w, (tile_figures *) (d_w + nspec));
   DX_HIP(ctx, hipGetLastError());
-  std::vector<uint64_t> back(words);
-  DX_HIP(ctx, hipMemcpyAsync(back.data(), d_w, words * 8u, hipMemcpyDeviceToHost, ctx->stream));
-  DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  uint64_t d = 0, m = 0, mc = 0;
-  for (int b = 0; b < grid; b++)
-    { const uint64_t *o = back.data() + nspec + 3u * (size_t) b;
-      d += o[0];
-      if (o[1] > m || (o[1] == m && m && o[2] < mc)) { m = o[1]; mc = o[2]; }
-    }
-  if (nspec) memcpy(spectrum, back.data(), (size_t) nspec * 8u);
-  if (distinct) *distinct = d;
-  if (max_count) *max_count = m;
+  if ((rc = figures_read(ctx, d_w, nspec, grid, spectrum, distinct, max_count, &mc)) != DX_OK) return rc;
   if (max_code) *max_code = (uint32_t) mc;
   return DX_OK;
 }
@@ -479,17 +431,16 @@ extern "C" int dx_kmer_list(dx_ctx *ctx, const uint64_t *d_table, uint32_t k, ui
   DX_HIP(ctx, hipSetDevice(ctx->device));
   int rc = dx_after_pending(ctx);
   if (rc != DX_OK) return rc;
-  const uint64_t cells = 1ull << (2u * k), tiles = (cells + KM_TILE - 1u) / KM_TILE;
-  uint64_t      *d_start = NULL;
-  if ((rc = dx_scratch(ctx, (tiles + 1u + (tiles + 1u) / 2u) * 8u, (void **) &d_start)) != DX_OK) return rc;
-  uint32_t *d_count = (uint32_t *) (d_start + tiles + 1u);
+  const uint64_t cells = 1ull << (2u * k), tiles = (cells + TL_TILE - 1u) / TL_TILE;
+  tiles_layout   l;
+  bool           list = false;
+  if ((rc = tiles_scratch(ctx, 0, tiles, false, &l)) != DX_OK) return rc;
   hipLaunchKernelGGL(k_kmer_tiles, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, (const unsigned long long *) d_table, cells,
-                     min_count, d_count);
-  DX_HIP(ctx, hipGetLastError());
-  if ((rc = dx_scan_u32(ctx, d_count, tiles, d_start, found)) != DX_OK) return rc;
-  if (cap && *found)
+                     min_count, l.pass);
+  if ((rc = tiles_places(ctx, l, tiles, cap, found, &list)) != DX_OK) return rc;
+  if (list)
     { hipLaunchKernelGGL(k_kmer_list, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, (const unsigned long long *) d_table, cells,
-                         min_count, (const uint64_t *) d_start, (u32x4_u *) d_out, cap);
+                         min_count, (const uint64_t *) l.start, (u32x4_u *) d_out, cap);
       DX_HIP(ctx, hipGetLastError());
       DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -5,7 +5,7 @@
 //   dx_kmer_set_from_codes    host codes, any order, repeats allowed: folded (canonical), uploaded, sorted, then the above
 //   dx_kmer_set_info / _codes / _free
 //
-//   k_set_take    tile t (KS_TILE = 2048 keys): the first key of every run of min_count keys at least -- counted (the tile's word),
+//   k_set_take    tile t (TL_TILE = 2048 keys): the first key of every run of min_count keys at least -- counted (the tile's word),
 //                 then, the places known from dx_scan_u32 of the counts, written to its place
 //   k_set_index   one thread a bucket: first[b] = the lower bound of b << (2 k - p) in the codes
 //
@@ -25,20 +25,12 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in the
 // profiler's name table and are timed with events on the context's stream (tools/screen_rate.py).
-#include "dx_internal.hpp"
-#include "dx_device.hpp"
+#include "tiles/dx_tiles.hpp"
 #include "screen/dx_kmer_set.hpp"
-
-extern "C" {
-#include "dx_host.h"
-}
 
 #include <new>
 
 #define KS_KMAX  32u
-#define KS_ITEMS 8u                           // keys a thread
-#define KS_TILE  (DX_BLOCK * KS_ITEMS)        // keys a workgroup
-#define KS_SORTED_MAX (1ull << 36)            // keys of a sorted array (dx_sort_u64's and dx_kmer_runs' bound)
 
 // ---------------------------------------------------------------------------------------------
 //  k_set_take
@@ -50,13 +42,13 @@ __global__ __launch_bounds__(DX_BLOCK)
 void k_set_take(const uint64_t *__restrict__ key, uint64_t n, uint64_t need, uint32_t *__restrict__ pass,
                 const uint64_t *__restrict__ start, uint64_t *__restrict__ out, uint64_t cap)
 { __shared__ uint32_t s_n[DX_WAVES_PER_BLK];
-  const uint64_t i0 = (uint64_t) blockIdx.x * KS_TILE + (uint64_t) KS_ITEMS * threadIdx.x;
-  uint64_t v[KS_ITEMS];
-  bool     take[KS_ITEMS];
+  const uint64_t i0 = (uint64_t) blockIdx.x * TL_TILE + (uint64_t) TL_ITEMS * threadIdx.x;
+  uint64_t v[TL_ITEMS];
+  bool     take[TL_ITEMS];
   uint32_t mine = 0;
   uint64_t prev = i0 && i0 < n ? key[i0 - 1u] : 0ull;
   #pragma unroll
-  for (uint32_t j = 0; j < KS_ITEMS; j++)
+  for (uint32_t j = 0; j < TL_ITEMS; j++)
     { const uint64_t i = i0 + j;
       const bool have = i < n;
       v[j] = have ? key[i] : 0ull;
@@ -64,21 +56,15 @@ void k_set_take(const uint64_t *__restrict__ key, uint64_t n, uint64_t need, uin
       mine += take[j] ? 1u : 0u;
       prev = v[j];
     }
-  const uint32_t incl = wave_incl_scan(mine), wave = threadIdx.x / DX_WAVE;
-  if (lane_id() == 63) s_n[wave] = incl;
-  __syncthreads();
   if (!WRITE)
-    { if (threadIdx.x == 0u) pass[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    { const uint32_t all = tile_total(mine, s_n);
+      if (threadIdx.x == 0u) pass[blockIdx.x] = all;
       return;
     }
-  uint64_t at = start[blockIdx.x] + (incl - mine);
-  for (uint32_t w = 0; w < wave; w++) at += s_n[w];
+  uint64_t at = tile_place(mine, start[blockIdx.x], s_n);
   #pragma unroll
-  for (uint32_t j = 0; j < KS_ITEMS; j++)
-    if (take[j])
-      { if (at < cap) out[at] = v[j];
-        at++;
-      }
+  for (uint32_t j = 0; j < TL_ITEMS; j++)
+    if (take[j]) tile_put(at, cap, [&](uint64_t to) { out[to] = v[j]; });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -139,25 +125,23 @@ extern "C" int dx_sorted_take(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n,
   if (found) *found = 0;
   if (found == NULL || (d_sorted == NULL && n) || (d_out == NULL && cap)) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
   if (min_count < 1u) return dx_fail(ctx, DX_E_ARG, "%s: min_count 0 (1 at least: the unseen codes are in no set)", who);
-  if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
+  if (n >= TL_NMAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
   DX_HIP(ctx, hipSetDevice(ctx->device));
   int rc = dx_after_pending(ctx);
   if (rc != DX_OK) return rc;
 
   // the runs that pass, a tile: counted, and summed to every tile's first place
-  const uint64_t tiles = (n + KS_TILE - 1u) / KS_TILE, need = min_count - 1u;
-  uint64_t      *d_start = NULL;
-  uint32_t      *d_pass = NULL;
+  const uint64_t tiles = (n + TL_TILE - 1u) / TL_TILE, need = min_count - 1u;
+  tiles_layout   l;
+  bool           list = false;
   if (n == 0 || need >= n) return DX_OK;
-  if ((rc = dx_scratch(ctx, (tiles + 1u + (tiles + 1u) / 2u) * 8u, (void **) &d_start)) != DX_OK) return rc;
-  d_pass = (uint32_t *) (d_start + tiles + 1u);
-  hipLaunchKernelGGL(k_set_take<false>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, d_pass,
+  if ((rc = tiles_scratch(ctx, 0, tiles, false, &l)) != DX_OK) return rc;
+  hipLaunchKernelGGL(k_set_take<false>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, l.pass,
                      (const uint64_t *) NULL, (uint64_t *) NULL, (uint64_t) 0);
-  DX_HIP(ctx, hipGetLastError());
-  if ((rc = dx_scan_u32(ctx, d_pass, tiles, d_start, found)) != DX_OK) return rc;
-  if (cap && *found)
+  if ((rc = tiles_places(ctx, l, tiles, cap, found, &list)) != DX_OK) return rc;
+  if (list)
     { hipLaunchKernelGGL(k_set_take<true>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, d_sorted, n, need, (uint32_t *) NULL,
-                         (const uint64_t *) d_start, d_out, cap);
+                         (const uint64_t *) l.start, d_out, cap);
       DX_HIP(ctx, hipGetLastError());
       DX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the caller may free d_sorted; the scratch is free again)
     }
@@ -174,7 +158,7 @@ extern "C" int dx_kmer_set_from_sorted(dx_ctx *ctx, const uint64_t *d_sorted, ui
   if (rc != DX_OK) return rc;
   if (d_sorted == NULL && n) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
   if (min_count < 1u) return dx_fail(ctx, DX_E_ARG, "%s: min_count 0 (1 at least: the unseen codes are in no set)", who);
-  if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
+  if (n >= TL_NMAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu keys (fewer than 2^36)", who, (unsigned long long) n);
   DX_HIP(ctx, hipSetDevice(ctx->device));
 
   // counted first: the set's array has exactly the size (the tiles are counted once more when it is filled: 8 bytes a key, beside a sort)
@@ -224,7 +208,7 @@ extern "C" int dx_kmer_set_from_codes(dx_ctx *ctx, const uint64_t *codes, uint64
   int rc = ks_args(ctx, who, k, canonical, arrow);
   if (rc != DX_OK) return rc;
   if (codes == NULL && n) return dx_fail(ctx, DX_E_ARG, "%s: NULL pointer", who);
-  if (n >= KS_SORTED_MAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu codes (fewer than 2^36)", who, (unsigned long long) n);
+  if (n >= TL_NMAX) return dx_fail(ctx, DX_E_ARG, "%s: %llu codes (fewer than 2^36)", who, (unsigned long long) n);
   if (n == 0) return dx_kmer_set_from_sorted(ctx, NULL, 0, 1, k, canonical, arrow, set);
 
   std::vector<uint64_t> own;

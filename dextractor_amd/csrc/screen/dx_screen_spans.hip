@@ -49,10 +49,7 @@
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in the
 // profiler's name table and are timed with events on the context's stream (tools/screen_spans_rate.py).
 #include "screen/dx_screen_look.hpp"
-
-extern "C" {
-#include "dx_host.h"
-}
+#include "tiles/dx_tiles.hpp"
 
 // ---------------------------------------------------------------------------------------------
 //  k_spans
@@ -242,16 +239,9 @@ static int spans_run(dx_ctx *ctx, const char *who, const uint8_t *d_in, uint64_t
 
   // one scratch block: the frame and the three totals, then (with a list) every unit's first place, and the counts nobody asked for
   units_frame    f;
-  uint64_t       back[UF_OUT + 3], *d_w = NULL;
+  uint64_t       back[UF_OUT + 3], *d_start = NULL;
   const uint64_t bound = in_bytes;
-  const size_t   words = UF_OUT + 3;
-  const bool     own   = cap && d_count == NULL;
-  DX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = dx_scratch(ctx, (words + (cap ? n + 1u : 0u) + (own ? (n + 1u) / 2u : 0u)) * 8u, (void **) &d_w);
-  if (rc != DX_OK) return rc;
-  uint64_t *d_start = cap ? d_w + words : NULL;
-  if (own) d_count = (uint32_t *) (d_start + n + 1u);
-  rc = units_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), d_w, 3, 16, &d_in, &in_bytes, &f);
+  int rc = units_list_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), 3, 16, cap != 0, &d_in, &in_bytes, &f, &d_start, &d_count);
   if (rc != DX_OK) return rc;
   const sc_set s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
   const int grid = dx_grid_waves(ctx, n, 16);
@@ -265,11 +255,9 @@ static int spans_run(dx_ctx *ctx, const char *who, const uint8_t *d_in, uint64_t
     }
   uint64_t spans = 0;
   if (cap)
-    { DX_HIP(ctx, hipGetLastError());
-      if ((rc = dx_scan_u32(ctx, d_count, n, d_start, &spans)) != DX_OK) return rc;
+    { if ((rc = units_list_places(ctx, f, d_count, n, d_start, &spans)) != DX_OK) return rc;
       if (spans)
-        { DX_HIP(ctx, hipMemsetAsync(f.ticket, 0, 4, ctx->stream));           // (the counter; the units a ticket stay)
-          if (set->canonical) hipLaunchKernelGGL((k_spans<true, true>), dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound,
+        { if (set->canonical) hipLaunchKernelGGL((k_spans<true, true>), dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound,
                                                  d_boff, d_beg, d_len, n, s, d_count, (const uint64_t *) d_start, d_spans, cap,
                                                  (unsigned long long *) NULL, f.bad, f.ticket);
           else                hipLaunchKernelGGL((k_spans<false, true>), dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound,
@@ -483,29 +471,27 @@ extern "C" int dx_spans_join(dx_ctx *ctx, const dx_span *d_in, uint64_t n, uint3
   int rc = dx_after_pending(ctx);
   if (rc != DX_OK) return rc;
 
-  // one scratch block: the smallest bad index and the two totals, every tile's first place in the list (tiles + 1), and behind them
-  // the tiles' counts and first heads
+  // in front of the tiles' words: the smallest bad index and the two totals
   const uint64_t tiles = (n + SJ_TILE - 1u) / SJ_TILE;
-  uint64_t      *d_w   = NULL, back[3], found = 0;
-  if ((rc = dx_scratch(ctx, (3u + tiles + 1u + tiles + 1u) * 8u, (void **) &d_w)) != DX_OK) return rc;
-  uint64_t *d_start = d_w + 3u;
-  uint32_t *d_pass  = (uint32_t *) (d_start + tiles + 1u), *d_first = d_pass + tiles;
-  DX_HIP(ctx, hipMemsetAsync(d_w, 0xff, 8, ctx->stream));
-  DX_HIP(ctx, hipMemsetAsync(d_w + 1, 0, 16, ctx->stream));
-  hipLaunchKernelGGL(k_join_heads, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, (const u32x4_u *) d_in, n, max_gap, d_first,
-                     (unsigned long long *) d_w);
+  uint64_t       back[3], found = 0;
+  tiles_layout   l;
+  bool           list = false;
+  if ((rc = tiles_scratch(ctx, 3, tiles, true, &l)) != DX_OK) return rc;
+  DX_HIP(ctx, hipMemsetAsync(l.head, 0xff, 8, ctx->stream));
+  DX_HIP(ctx, hipMemsetAsync(l.head + 1, 0, 16, ctx->stream));
+  hipLaunchKernelGGL(k_join_heads, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, (const u32x4_u *) d_in, n, max_gap, l.first,
+                     (unsigned long long *) l.head);
   hipLaunchKernelGGL(k_join<false>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, (const u32x4_u *) d_in, n,
-                     (const uint32_t *) d_first, tiles, max_gap, min_span, d_pass, (const uint64_t *) NULL, (u32x4_u *) NULL, cap,
-                     (unsigned long long *) (d_w + 1));
-  DX_HIP(ctx, hipGetLastError());
-  if ((rc = dx_scan_u32(ctx, d_pass, tiles, d_start, &found)) != DX_OK) return rc;
-  if (cap && found)
+                     (const uint32_t *) l.first, tiles, max_gap, min_span, l.pass, (const uint64_t *) NULL, (u32x4_u *) NULL, cap,
+                     (unsigned long long *) (l.head + 1));
+  if ((rc = tiles_places(ctx, l, tiles, cap, &found, &list)) != DX_OK) return rc;
+  if (list)
     { hipLaunchKernelGGL(k_join<true>, dim3((unsigned) tiles), dim3(DX_BLOCK), 0, ctx->stream, (const u32x4_u *) d_in, n,
-                         (const uint32_t *) d_first, tiles, max_gap, min_span, (uint32_t *) NULL, (const uint64_t *) d_start,
+                         (const uint32_t *) l.first, tiles, max_gap, min_span, (uint32_t *) NULL, (const uint64_t *) l.start,
                          (u32x4_u *) d_out, cap, (unsigned long long *) NULL);
       DX_HIP(ctx, hipGetLastError());
     }
-  DX_HIP(ctx, hipMemcpyAsync(back, d_w, 24, hipMemcpyDeviceToHost, ctx->stream));
+  DX_HIP(ctx, hipMemcpyAsync(back, l.head, 24, hipMemcpyDeviceToHost, ctx->stream));
   DX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (back[0] != UINT64_MAX)
     { if (bad) *bad = back[0];

@@ -7,6 +7,10 @@
 #include "dx_device.hpp"
 #include "dx_words.h"
 
+extern "C" {
+#include "dx_host.h"
+}
+
 #define UNITS_GROUP   16u                  // lanes that take a short unit together
 #define UNITS_LEN_MAX 0x7fffffffu          // symbols a packed unit (DAZZ_READ.rlen is an int); more are refused like a unit out of bounds
 
@@ -146,6 +150,32 @@ static int units_begin(dx_ctx *ctx, const char *who, uint64_t n, bool have, uint
     { if (*in_bytes) DX_HIP(ctx, hipMemcpyAsync(d_w + UF_PAD, *d_in, *in_bytes, hipMemcpyDeviceToDevice, ctx->stream));
       *d_in = (const uint8_t *) (d_w + UF_PAD); *in_bytes = least;
     }
+  return DX_OK;
+}
+
+// The same for an entry point that may list: ONE scratch block with the frame and out_words answer words in front and, when
+// `places`, every unit's first place in the list behind them (*d_start: n + 1 words; NULL without) and, when the caller brings no
+// counts (*d_room == NULL), a room[n] of its own, which *d_room then names.
+static int units_list_begin(dx_ctx *ctx, const char *who, uint64_t n, bool have, size_t out_words, uint32_t least, bool places,
+                            const uint8_t **d_in, uint64_t *in_bytes, units_frame *f, uint64_t **d_start, uint32_t **d_room)
+{ uint64_t    *d_w   = NULL;
+  const size_t words = UF_OUT + out_words;
+  const bool   own   = places && *d_room == NULL;
+  DX_HIP(ctx, hipSetDevice(ctx->device));
+  const int rc = dx_scratch(ctx, (words + (places ? n + 1u : 0u) + (own ? (n + 1u) / 2u : 0u)) * 8u, (void **) &d_w);
+  if (rc != DX_OK) return rc;
+  *d_start = places ? d_w + words : NULL;
+  if (own) *d_room = (uint32_t *) (*d_start + n + 1u);
+  return units_begin(ctx, who, n, have, d_w, out_words, least, d_in, in_bytes, f);
+}
+
+// Between the counting launch and the listing launch: d_room[n] summed to every unit's first place, *listed what the list holds
+// (one read-back), and, when it holds anything, the ticket counter back at 0 for the second walk over the units.
+static int units_list_places(dx_ctx *ctx, const units_frame &f, const uint32_t *d_room, uint64_t n, uint64_t *d_start, uint64_t *listed)
+{ DX_HIP(ctx, hipGetLastError());
+  const int rc = dx_scan_u32(ctx, d_room, n, d_start, listed);
+  if (rc != DX_OK) return rc;
+  if (*listed) DX_HIP(ctx, hipMemsetAsync(f.ticket, 0, 4, ctx->stream));     // (the counter; the units a ticket stay)
   return DX_OK;
 }
 

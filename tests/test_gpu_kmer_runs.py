@@ -14,7 +14,7 @@ from dextractor_amd import api
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
-TILE = 2048                                                        # KR_TILE of csrc/kmers/dx_kmer_runs.hip
+TILE = 2048                                                        # TL_TILE of csrc/tiles/dx_tiles.hpp
 GUARD = 4                                                          # entries behind the list's cap
 MARK = np.uint64(0xD00DD00DD00DD00D)
 
@@ -94,6 +94,17 @@ def test_a_run_far_longer_than_a_tile(ctx):
     assert len(keys) == 200000
     found, lst, fig = check(ctx, keys, min_count=2, nspec=16)
     assert found >= 1 and fig["max_count"] >= 100000 and fig["spectrum"][15] >= 1
+
+
+def test_a_run_whose_end_lies_more_than_256_tiles_away(ctx):
+    """the search of the tiles that follow takes 256 of them a step: this run's next begin is found in its second step"""
+    long = 257 * TILE + 3
+    counts = [1] * (TILE // 2 + 5) + [long] + [1, 2, 1, 3, 1]        # the run begins in the middle of a tile
+    keys = from_runs(np.arange(len(counts), dtype=np.uint64) * np.uint64(11) + np.uint64(3), counts)
+    found, lst, fig = check(ctx, keys)
+    assert found == len(counts) and lst["count"].tolist() == counts
+    found, lst, fig = check(ctx, keys, min_count=long)
+    assert found == 1 and int(lst["count"][0]) == long == fig["max_count"] and int(lst["code"][0]) == 11 * (TILE // 2 + 5) + 3
 
 
 def test_two_codes_tie_for_the_longest_run(ctx):

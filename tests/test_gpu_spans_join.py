@@ -121,6 +121,19 @@ def test_one_joined_span_of_100000_entries(ctx):
     assert len(run(ctx, lst, 2, 51)[0]) == 1
 
 
+def test_one_joined_span_whose_end_lies_more_than_256_tiles_away(ctx):
+    """the search of the tiles that follow takes 256 of them a step: this span's next head is found in its second step"""
+    n, pre = 257 * TILE + 3, TILE // 2 + 5                                     # (the span begins in the middle of a tile)
+    i = np.arange(n, dtype=np.int64)
+    lst = np.zeros(pre + n + 3, SP.SPAN)
+    lst["record"][:pre], lst["beg"][:pre], lst["end"][:pre] = 3, 20 * np.arange(pre), 20 * np.arange(pre) + 7     # gaps of 13: none joins
+    lst["record"][pre:pre + n], lst["beg"][pre:pre + n], lst["end"][pre:pre + n] = 4, 100 + 6 * i, 104 + 6 * i    # gaps of 2: all join
+    lst[pre + n:] = [(5, 3, 9), (5, 12, 20), (5, 30, 32)]
+    got, totals = run(ctx, lst, 2, 0)
+    assert len(got) == pre + 4 and tuple(int(v) for v in got[pre]) == (4, 100, 6 * n + 98)
+    assert [tuple(int(v) for v in x) for x in got[pre + 1:]] == [(5, 3, 9), (5, 12, 20), (5, 30, 32)]
+
+
 def test_a_record_change_with_a_small_numeric_gap_does_not_join(ctx):
     lst = SP.as_spans([(0, 0, 10), (1, 11, 20), (1, 21, 30), (2, 0, 5), (2 ** 40, 6, 8), (2 ** 40 + 1, 9, 10)])
     got, _ = run(ctx, lst, 5, 0)
