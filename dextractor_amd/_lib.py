@@ -128,6 +128,14 @@ class ScreenReport(C.Structure):                 # dx_screen_report
     _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64),
                 ("covered", C.c_uint64), ("records_hit", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
 
+class Depth(C.Structure):                        # dx_depth
+    _fields_ = [("windows", C.c_uint32), ("hits", C.c_uint32), ("sum", C.c_uint64), ("min", C.c_uint16), ("q1", C.c_uint16),
+                ("median", C.c_uint16), ("q3", C.c_uint16), ("max", C.c_uint16), ("reserved", C.c_uint16 * 3)]
+
+class DepthReport(C.Structure):                  # dx_depth_report
+    _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64),
+                ("sum", C.c_uint64), ("records_hit", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
+
 class Span(C.Structure):                         # dx_span
     _fields_ = [("record", C.c_uint64), ("beg", C.c_uint32), ("end", C.c_uint32)]
 
@@ -139,6 +147,7 @@ class SpansReport(C.Structure):                  # dx_spans_report
 DX_KIND_FASTA, DX_KIND_ARROW, DX_KIND_QUIVA = 0, 1, 2
 DX_SCREEN_KEEP, DX_SCREEN_DROP = 0, 1
 DX_CUT_SPLIT, DX_CUT_LONGEST, DX_CUT_DROP = 0, 1, 2
+DX_DEPTH_MIN, DX_DEPTH_Q1, DX_DEPTH_MEDIAN, DX_DEPTH_Q3, DX_DEPTH_MAX = range(5)
 VERIFY_WHERE = ["NONE", "HEADER", "BODY", "LENGTH", "COUNT", "IMAGE"]      # DX_VERIFY_*
 
 # name -> (restype, argtypes); every symbol include/dexgpu.h declares
@@ -316,6 +325,21 @@ SIGNATURES = {
                                       C.POINTER(C.c_uint64)]),
     "dx_file_screen": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(ScreenReport), C.POINTER(_P), C.POINTER(_P)]),
     "dx_screen_select": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "dx_kmer_set_counted": (C.c_int, [_P]),
+    "dx_kmer_set_counts": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "dx_kmer_set_from_sorted_counted": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dx_kmer_set_from_kmers": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dx_file_kmer_set_counted": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(_P),
+                                           C.POINTER(Kmers64)]),
+    "dx_files_kmer_set_counted": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(_P),
+                                            C.POINTER(Kmers64), C.POINTER(C.c_uint32)]),
+    "dx_code_kmer_depths": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64)]),
+    "dx_depth_stats": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64 * 4)]),
+    "dx_file_depth": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.POINTER(DepthReport), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                C.POINTER(_P)]),
+    "dx_depth_select": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P),
+                                  C.POINTER(C.c_uint64)]),
     "dx_code_kmer_spans": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64 * 3),
                                      C.POINTER(C.c_uint64)]),
     "dx_spans_join": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64 * 2), C.POINTER(C.c_uint64)]),

@@ -1039,25 +1039,41 @@ class Context:
                 out["letters"] = [kmer_letters64(int(c), int(k), arrow=kind == "arrow") for c in got["code"]]
             return rep, spec, out
 
-    def kmer_set_files(self, kind, imgs, k, canonical=False, min_count=1, room=0, report=False):
-        """dx_files_kmer_set: kmer_set over several images of one kind, by kmers_wide_files' passes.  report: (set, what
-        kmers_wide_files reports without its list and its files)."""
+    def _kmer_set_files(self, fn, kind, imgs, k, canonical, min_count, room, report):
+        """dx_files_kmer_set or its counted sibling"""
         ptrs, sizes, n, keep = self._images(imgs)
         h, km, passes = C.c_void_p(), L.Kmers64(), C.c_uint32()
-        self._chk(self.lib.dx_files_kmer_set(self.h, _kind(kind), ptrs, sizes, n, int(k), int(bool(canonical)), int(min_count), int(room),
-                                             C.byref(h), C.byref(km), C.byref(passes)))
+        self._chk(fn(self.h, _kind(kind), ptrs, sizes, n, int(k), int(bool(canonical)), int(min_count), int(room), C.byref(h), C.byref(km),
+                     C.byref(passes)))
         s = KmerSet(self, h)
         return (s, dict(_fields(km), passes=passes.value)) if report else s
 
+    def kmer_set_files(self, kind, imgs, k, canonical=False, min_count=1, room=0, report=False):
+        """dx_files_kmer_set: kmer_set over several images of one kind, by kmers_wide_files' passes.  report: (set, what
+        kmers_wide_files reports without its list and its files)."""
+        return self._kmer_set_files(self.lib.dx_files_kmer_set, kind, imgs, k, canonical, min_count, room, report)
+
+    def kmer_set_files_counted(self, kind, imgs, k, canonical=False, min_count=1, room=0, report=False):
+        """dx_files_kmer_set_counted: kmer_set_files with every code's count over all the images kept beside it (KmerSet.counts)"""
+        return self._kmer_set_files(self.lib.dx_files_kmer_set_counted, kind, imgs, k, canonical, min_count, room, report)
+
     # ---- screen: the reads that share k-mers with a set ---------------------------------------------------
+    def _kmer_set_file(self, fn, kind, img, k, canonical, min_count, report):
+        """dx_file_kmer_set or its counted sibling"""
+        h, km = C.c_void_p(), L.Kmers64()
+        self._chk(fn(self.h, _kind(kind), img, len(img), int(k), int(bool(canonical)), int(min_count), C.byref(h), C.byref(km)))
+        s = KmerSet(self, h)
+        return (s, _fields(km)) if report else s
+
     def kmer_set(self, kind, img: bytes, k, canonical=False, min_count=1, report=False):
         """dx_file_kmer_set: the distinct k-mers (1 <= k <= 32) of a .dexta / .dexar image that are counted min_count times at least,
         as a KmerSet on the device -- kmers_wide's route up to the sorted codes.  report: (set, what kmers_wide reports for the image)."""
-        h, km = C.c_void_p(), L.Kmers64()
-        self._chk(self.lib.dx_file_kmer_set(self.h, _kind(kind), img, len(img), int(k), int(bool(canonical)), int(min_count), C.byref(h),
-                                            C.byref(km)))
-        s = KmerSet(self, h)
-        return (s, _fields(km)) if report else s
+        return self._kmer_set_file(self.lib.dx_file_kmer_set, kind, img, k, canonical, min_count, report)
+
+    def kmer_set_counted(self, kind, img: bytes, k, canonical=False, min_count=1, report=False):
+        """dx_file_kmer_set_counted: kmer_set with every code's count in the image kept beside it, saturated at 2^32 - 1
+        (KmerSet.counts): the set that Context.depth and code_kmer_depths read depths from."""
+        return self._kmer_set_file(self.lib.dx_file_kmer_set_counted, kind, img, k, canonical, min_count, report)
 
     def kmer_set_from_codes(self, codes, k, canonical=False, arrow=False):
         """dx_kmer_set_from_codes: the KmerSet of the given 64-bit codes (any order, repeats allowed, none at all: the empty set); with
@@ -1068,12 +1084,34 @@ class Context:
                                                   int(bool(arrow)), C.byref(h)))
         return KmerSet(self, h)
 
+    def kmer_set_from_kmers(self, kmers, k, canonical=False, arrow=False):
+        """dx_kmer_set_from_kmers: the counted KmerSet of (code, count) pairs in any order -- a KMER64_DTYPE array, the `code` and
+        `count` fields of kmers_wide's list, or a sequence of pairs.  With canonical each code is folded first; equal codes add; sums
+        saturate at 2^32 - 1; a pair with count 0 is dropped."""
+        a = np.asarray(kmers)
+        if a.dtype.names is None:
+            a = np.asarray(kmers, np.uint64).reshape(-1, 2)
+            a = np.rec.fromarrays([a[:, 0], a[:, 1]], dtype=KMER64_DTYPE)
+        lst = np.zeros(len(a), KMER64_DTYPE)
+        lst["code"], lst["count"] = a["code"], a["count"]
+        h = C.c_void_p()
+        self._chk(self.lib.dx_kmer_set_from_kmers(self.h, lst.ctypes.data if len(lst) else None, len(lst), int(k), int(bool(canonical)),
+                                                  int(bool(arrow)), C.byref(h)))
+        return KmerSet(self, h)
+
+    def _kmer_set_sorted(self, fn, sorted_codes, n, k, min_count, canonical, arrow):
+        """dx_kmer_set_from_sorted or its counted sibling"""
+        h = C.c_void_p()
+        self._chk(fn(self.h, _addr(sorted_codes), int(n), int(min_count), int(k), int(bool(canonical)), int(bool(arrow)), C.byref(h)))
+        return KmerSet(self, h)
+
     def kmer_set_from_sorted(self, sorted_codes, n, k, min_count=1, canonical=False, arrow=False):
         """dx_kmer_set_from_sorted: the KmerSet of the codes whose run in the sorted device array of n keys has min_count keys at least"""
-        h = C.c_void_p()
-        self._chk(self.lib.dx_kmer_set_from_sorted(self.h, _addr(sorted_codes), int(n), int(min_count), int(k), int(bool(canonical)),
-                                                   int(bool(arrow)), C.byref(h)))
-        return KmerSet(self, h)
+        return self._kmer_set_sorted(self.lib.dx_kmer_set_from_sorted, sorted_codes, n, k, min_count, canonical, arrow)
+
+    def kmer_set_from_sorted_counted(self, sorted_codes, n, k, min_count=1, canonical=False, arrow=False):
+        """dx_kmer_set_from_sorted_counted: kmer_set_from_sorted's codes, each with the length of its run as its count"""
+        return self._kmer_set_sorted(self.lib.dx_kmer_set_from_sorted_counted, sorted_codes, n, k, min_count, canonical, arrow)
 
     def code_kmer_screen(self, d_in, boff, beg, length, kset, out=None, in_bytes=None, n=None):
         """dx_code_kmer_screen: unit j = symbols [beg[j], beg[j] + length[j]) of the packed read at d_in + boff[j] (beg None: whole
@@ -1101,6 +1139,59 @@ class Context:
             self._chk(self.lib.dx_file_screen(self.h, _kind(kind), img, len(img), kset.h if kset is not None else None, C.byref(rp),
                                               C.byref(rec), C.byref(rl)))
             return _fields(rp), _take(rec, SCREEN_DTYPE, rp.records), _take(rl, np.uint32, rp.records)
+
+    # ---- depth: how often a read's k-mers were seen ---------------------------------------------------------
+    def code_kmer_depths(self, d_in, boff, beg, length, kset, cap=None, depth=None, off=None, in_bytes=None, n=None):
+        """dx_code_kmer_depths: units as for code_kmer_codes, against the KmerSet kset; window p of unit j -> depth[off[j] + p] =
+        min(the count of its code in the set, 65535), 0 for a code the set does not hold, 1 for every code of an uncounted set.
+        depth: a device array of cap 16-bit words; None: a DevBuf of cap words made here (cap None: every unit's windows, from a
+        host copy of `length`), the caller's to free.  off: a device array of n + 1 uint64 for the units' places, or None.  Returns
+        (depth, windows).  Raises DexGPUError: DX_E_NOMEM (.windows = what is needed) when cap is short, DX_E_FORMAT (.bad_unit)
+        for a unit outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        n = int(b_len // 4 if n is None else n)
+        own = None
+        if depth is None:
+            if cap is None:
+                ln = (length.cpu().numpy()[:n] if hasattr(length, "cpu") else length.download(np.uint32, n)).astype(np.int64)
+                cap = int(np.maximum(ln - kset.info["k"] + 1, 0).sum())
+            depth = own = self.alloc(2 * int(cap) + 16)
+        elif cap is None:
+            cap = _dev(depth)[1] // 2
+        win, bad = C.c_uint64(), C.c_uint64()
+        rc = self.lib.dx_code_kmer_depths(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                          n, kset.h if kset is not None else None, _addr(depth), int(cap), _addr(off), C.byref(win),
+                                          C.byref(bad))
+        if rc != 0:
+            if own:
+                own.free()
+            raise self._err(rc, bad_unit=_index(bad), windows=win.value)
+        return depth, win.value
+
+    def depth_stats(self, depth, off, n, out=None):
+        """dx_depth_stats: per stretch depth[off[j] .. off[j + 1]) of a profile (device arrays: 16-bit words, n + 1 uint64) its
+        windows, hits, sum, min, q1, median, q3 and max -- the quantiles exact, s[(t (w - 1)) // 4] of the sorted values.  out: a
+        device array of n 32-byte entries (DEPTH_DTYPE), or None for the totals alone.  Returns the totals as a uint64 array:
+        windows, hits, sum, units with a hit.  Raises DexGPUError: DX_E_FORMAT (.totals) when off decreases."""
+        tot = (C.c_uint64 * 4)()
+        rc = self.lib.dx_depth_stats(self.h, _addr(depth), _addr(off), int(n), _addr(out), C.byref(tot))
+        totals = np.array(list(tot), np.uint64)
+        if rc != 0:
+            raise self._err(rc, totals=totals)
+        return totals
+
+    def depth(self, kind, img: bytes, kset, profile=False):
+        """dx_file_depth: the records of a .dexta / .dexar image against the (counted) KmerSet kset -> (report: records, symbols,
+        windows, hits, sum, records_hit, k; rec: a DEPTH_DTYPE array, one entry a record; rec_len: every record's symbols); with
+        profile also (the whole profile as a uint16 array, rec_off: every record's place in it, records + 1 uint64).
+        api.depth_select turns rec into the ids that Context.subset takes."""
+        rp = L.DepthReport()
+        with _Outs(self.lib, 4) as (rec, rl, pf, ro):
+            self._chk(self.lib.dx_file_depth(self.h, _kind(kind), img, len(img), kset.h if kset is not None else None, C.byref(rp),
+                                             C.byref(rec), C.byref(rl), C.byref(pf) if profile else None, C.byref(ro) if profile else None))
+            out = (_fields(rp), _take(rec, DEPTH_DTYPE, rp.records), _take(rl, np.uint32, rp.records))
+            return out + (_take(pf, np.uint16, rp.windows), _take(ro, np.uint64, rp.records + 1)) if profile else out
 
     # ---- screen spans: where a read matches the set, and the image cut there ------------------------------
     def code_kmer_spans(self, d_in, boff, beg, length, kset, count=None, cap=0, spans=None, in_bytes=None, n=None):
@@ -1384,6 +1475,9 @@ KMER64_LIST_DTYPE = np.dtype([("count", "<u8"), ("code", "<u8"), ("letters", "S3
 
 SCREEN_DTYPE = np.dtype([("hits", "<u4"), ("covered", "<u4"), ("first", "<u4"), ("last", "<u4")])                 # dx_screen
 SPAN_DTYPE = np.dtype([("record", "<u8"), ("beg", "<u4"), ("end", "<u4")])                                         # dx_span
+DEPTH_DTYPE = np.dtype([("windows", "<u4"), ("hits", "<u4"), ("sum", "<u8"), ("min", "<u2"), ("q1", "<u2"), ("median", "<u2"),
+                        ("q3", "<u2"), ("max", "<u2"), ("reserved", "<u2", (3,))])                                    # dx_depth
+_DEPTH_STATS = {"min": L.DX_DEPTH_MIN, "q1": L.DX_DEPTH_Q1, "median": L.DX_DEPTH_MEDIAN, "q3": L.DX_DEPTH_Q3, "max": L.DX_DEPTH_MAX}
 
 
 class KmerSet:
@@ -1404,6 +1498,17 @@ class KmerSet:
         """the set's codes, ascending, as a uint64 array"""
         out = np.zeros(self.info["codes"], np.uint64)
         self.ctx._chk(self.ctx.lib.dx_kmer_set_codes(self.ctx.h, self.h, out.ctypes.data if len(out) else None, len(out)))
+        return out
+
+    @property
+    def counted(self) -> bool:
+        """whether the set keeps a count beside every code (Context.kmer_set_counted, .kmer_set_from_kmers)"""
+        return self.ctx.lib.dx_kmer_set_counted(self.h) == 1
+
+    def counts(self) -> np.ndarray:
+        """a counted set's counts, in the order of codes(), as a uint32 array; DexGPUError (DX_E_ARG) for an uncounted set"""
+        out = np.zeros(self.info["codes"], np.uint32)
+        self.ctx._chk(self.ctx.lib.dx_kmer_set_counts(self.ctx.h, self.h, out.ctypes.data if len(out) else None, len(out)))
         return out
 
     def free(self):
@@ -1431,6 +1536,20 @@ def screen_select(rec, rec_len, min_hits=1, min_permille=0, drop=False) -> np.nd
                                        int(min_permille), L.DX_SCREEN_DROP if drop else L.DX_SCREEN_KEEP, C.byref(ids), C.byref(n))
         if rc != 0:
             raise L.DexGPUError(rc, "dx_screen_select: min_permille is 0 to 1000")
+        return _take(ids, np.uint64, n.value)
+
+
+def depth_select(rec, stat="median", lo=0, hi=65535, min_windows=1, drop=False) -> np.ndarray:
+    """dx_depth_select: the records of Context.depth's answer that match -- windows >= max(min_windows, 1) and lo <= stat <= hi, stat
+    one of "min", "q1", "median", "q3", "max" (or a DX_DEPTH_* number) --, or with drop the others, ascending, as the uint64 ids
+    Context.subset takes.  Host only."""
+    r = np.ascontiguousarray(np.asarray(rec, DEPTH_DTYPE))
+    n = C.c_uint64()
+    with _Outs(L.load(), 1) as (ids,):
+        rc = L.load().dx_depth_select(r.ctypes.data if len(r) else None, len(r), int(_DEPTH_STATS.get(stat, stat)), int(lo), int(hi),
+                                      int(min_windows), L.DX_SCREEN_DROP if drop else L.DX_SCREEN_KEEP, C.byref(ids), C.byref(n))
+        if rc != 0:
+            raise L.DexGPUError(rc, "dx_depth_select: stat is min, q1, median, q3 or max, and lo <= hi")
         return _take(ids, np.uint64, n.value)
 
 

@@ -1,7 +1,7 @@
 /*
  * dx_file_kmers_files.c -- the k-mers of the reads of SEVERAL .dexta / .dexar images, 1 <= k <= 32, counted into one answer, in as
  * many passes over ranges of the codes as the device's memory asks for: dx_files_kmers_wide; and the same k-mers as one set on the
- * device: dx_files_kmer_set.
+ * device: dx_files_kmer_set, and with every code's count beside it dx_files_kmer_set_counted (one body, a flag).
  *
  * dx_file_kmers_wide (dx_file_kmers_wide.c) writes every window's code of ONE image into one array, sorts it and reads the counts off
  * the runs: 16 bytes of device memory a window.  The answer of a range of codes depends on no other range, and the order is the
@@ -260,14 +260,14 @@ done:
 }
 
 /* ---- dx_files_kmer_set ------------------------------------------------------------------------------------------------ */
-typedef struct { dx_ctx *ctx; uint64_t min_count, total; int report; dx_kmers64 *km; void **part; uint64_t *len; uint32_t parts; } set_fold;
+typedef struct
+  { dx_ctx *ctx; uint64_t min_count, total; int report, counted; dx_kmers64 *km; void **part, **cpart; uint64_t *len; uint32_t parts; } set_fold;
 
-/* a range's kept codes, into a device array of exactly their size */
+/* a range's kept codes, into a device array of exactly their size -- and, counted, their runs' lengths into a second one */
 static int set_range(void *arg, uint64_t *d_codes, uint64_t *d_tmp, uint64_t n)
 { set_fold *s = arg;
   uint64_t  found = 0, again = 0, listed = 0, distinct = 0, mx = 0, mc = 0;
   int       rc;
-  (void) d_tmp;
   if (s->report)                                           /* the report's other three figures, as dx_file_kmer_set reads them off the runs */
     { if ((rc = dx_kmer_runs(s->ctx, d_codes, n, 1, NULL, 0, &listed, NULL, 0, &distinct, &mx, &mc)) != DX_OK) return rc;
       s->km->distinct += distinct;
@@ -275,17 +275,20 @@ static int set_range(void *arg, uint64_t *d_codes, uint64_t *d_tmp, uint64_t n)
     }
   if ((rc = dx_sorted_take(s->ctx, d_codes, n, s->min_count, NULL, 0, &found)) != DX_OK || found == 0) return rc;
   if ((rc = dx_malloc(s->ctx, (size_t) found * 8 + 64, &s->part[s->parts])) != DX_OK) return rc;
+  if (s->counted && (rc = dx_malloc(s->ctx, (size_t) found * 4 + 64, &s->cpart[s->parts])) != DX_OK) return rc;   /* (the caller frees the part) */
   s->len[s->parts++] = found;
   s->total += found;
+  if (s->counted)
+    return dx_sorted_take_counted(s->ctx, d_codes, n, s->min_count, d_tmp, n, s->part[s->parts - 1], s->cpart[s->parts - 1], found, &again);
   return dx_sorted_take(s->ctx, d_codes, n, s->min_count, s->part[s->parts - 1], found, &again);
 }
 
-int dx_files_kmer_set(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k, int canonical,
-                      uint64_t min_count, uint64_t room, dx_kmer_set **set, dx_kmers64 *out, uint32_t *passes)
+static int files_kmer_set(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k, int canonical,
+                          uint64_t min_count, uint64_t room, int counted, dx_kmer_set **set, dx_kmers64 *out, uint32_t *passes)
 { dx_kmers64   km;
   dx_kmer_set *made = NULL;
   set_fold     s;
-  void        *d_all = NULL;
+  void        *d_all = NULL, *d_call = NULL;
   uint64_t     at = 0;
   uint32_t     np = 0, p;
   int          rc;
@@ -296,19 +299,24 @@ int dx_files_kmer_set(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const s
 
   fmark(NULL);
   memset(&s, 0, sizeof(s));
-  s.ctx = ctx; s.min_count = min_count; s.report = out != NULL; s.km = &km;
-  if ((s.part = calloc((1u << BINS_BITS) + 1, sizeof(*s.part))) == NULL || (s.len = calloc((1u << BINS_BITS) + 1, sizeof(*s.len))) == NULL)
+  s.ctx = ctx; s.min_count = min_count; s.report = out != NULL; s.counted = counted; s.km = &km;
+  if ((s.part = calloc((1u << BINS_BITS) + 1, sizeof(*s.part))) == NULL || (s.len = calloc((1u << BINS_BITS) + 1, sizeof(*s.len))) == NULL ||
+      (s.cpart = calloc((1u << BINS_BITS) + 1, sizeof(*s.cpart))) == NULL)
     { rc = DX_E_NOMEM; goto done; }                        /* (a range holds a bin at least) */
   TRY(files_passes(ctx, "dx_files_kmer_set", kind, imgs, bytes, nimg, k, canonical, room, &km, NULL, &np, set_range, &s));
 
   /* the ranges ascend: their arrays one behind the other are sorted and distinct */
   if (s.total) TRY(dx_malloc(ctx, (size_t) s.total * 8 + 64, &d_all));
+  if (s.total && counted) TRY(dx_malloc(ctx, (size_t) s.total * 4 + 64, &d_call));
   for (p = 0; p < s.parts; p++)
     { TRY(dx_d2d(ctx, (uint64_t *) d_all + at, s.part[p], (size_t) s.len[p] * 8));
+      if (counted) TRY(dx_d2d(ctx, (uint32_t *) d_call + at, s.cpart[p], (size_t) s.len[p] * 4));
       at += s.len[p];
       (void) dx_free(ctx, s.part[p]); s.part[p] = NULL;
+      if (s.cpart[p]) { (void) dx_free(ctx, s.cpart[p]); s.cpart[p] = NULL; }
     }
-  TRY(dx_kmer_set_from_sorted(ctx, d_all, s.total, 1, k, canonical, kind == DX_KIND_ARROW, &made));
+  if (counted) TRY(dx_kmer_set_from_counted(ctx, d_all, d_call, s.total, k, canonical, kind == DX_KIND_ARROW, &made));
+  else         TRY(dx_kmer_set_from_sorted(ctx, d_all, s.total, 1, k, canonical, kind == DX_KIND_ARROW, &made));
   fmark("the set made");
   if (out) *out = km;
   if (passes) *passes = np;
@@ -316,10 +324,21 @@ int dx_files_kmer_set(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const s
   rc = DX_OK;
 
 done:
-  for (p = 0; s.part && p < s.parts; p++)
-    if (s.part[p]) (void) dx_free(ctx, s.part[p]);
+  for (p = 0; s.part && s.cpart && p <= s.parts && p <= (1u << BINS_BITS); p++)      /* (a range that failed half made stands at s.parts) */
+    { if (s.part[p]) (void) dx_free(ctx, s.part[p]);
+      if (s.cpart[p]) (void) dx_free(ctx, s.cpart[p]);
+    }
   if (d_all) (void) dx_free(ctx, d_all);
-  free(s.part); free(s.len);
+  if (d_call) (void) dx_free(ctx, d_call);
+  free(s.part); free(s.cpart); free(s.len);
   fmark("the device arrays freed");
   return rc;
 }
+
+int dx_files_kmer_set(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k, int canonical,
+                      uint64_t min_count, uint64_t room, dx_kmer_set **set, dx_kmers64 *out, uint32_t *passes)
+{ return files_kmer_set(ctx, kind, imgs, bytes, nimg, k, canonical, min_count, room, 0, set, out, passes); }
+
+int dx_files_kmer_set_counted(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k,
+                              int canonical, uint64_t min_count, uint64_t room, dx_kmer_set **set, dx_kmers64 *out, uint32_t *passes)
+{ return files_kmer_set(ctx, kind, imgs, bytes, nimg, k, canonical, min_count, room, 1, set, out, passes); }

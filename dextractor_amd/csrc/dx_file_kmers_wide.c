@@ -1,6 +1,7 @@
 /*
  * dx_file_kmers_wide.c -- the k-mers of the reads of a .dexta / .dexar image for 1 <= k <= 32, counted by sorting: dx_file_kmers_wide;
- * the same k-mers as a set that stays on the device (screen/dx_kmer_set.hip), by the same route up to the sorted array: dx_file_kmer_set;
+ * the same k-mers as a set that stays on the device (screen/dx_kmer_set.hip), by the same route up to the sorted array: dx_file_kmer_set,
+ * and with every code's count beside it dx_file_kmer_set_counted (one body, a flag);
  * and the two host helpers that turn letters into a 64-bit code and back, dx_kmer_code64 and dx_kmer_letters64.
  *
  * dx_file_kmers (dx_file_kmers.c) counts into a table of 4^k cells and stops at k = 14.  Here every window's code is written into ONE
@@ -163,8 +164,8 @@ done:
 }
 
 /* ---- the same k-mers as a set on the device --------------------------------------------------------------------------- */
-int dx_file_kmer_set(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count,
-                     dx_kmer_set **set, dx_kmers64 *out)
+static int file_kmer_set(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count, int counted,
+                         dx_kmer_set **set, dx_kmers64 *out)
 { dx_kmers64   km;
   dx_kmer_set *s = NULL;
   uint64_t     found = 0;
@@ -179,7 +180,8 @@ int dx_file_kmer_set(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32
   TRY(wide_sorted(ctx, kind, img, m, k, canonical, dx_kmer_set_fail, &km, &d_codes, &d_tmp));
   if (out != NULL && km.windows)                           /* the report's other three figures, as dx_file_kmers_wide reads them off the runs */
     TRY(dx_kmer_runs(ctx, d_codes, km.windows, 1, NULL, 0, &found, NULL, 0, &km.distinct, &km.max_count, &km.max_code));
-  TRY(dx_kmer_set_from_sorted(ctx, d_codes, km.windows, min_count, k, canonical, kind == DX_KIND_ARROW, &s));
+  TRY((counted ? dx_kmer_set_from_sorted_counted : dx_kmer_set_from_sorted)(ctx, d_codes, km.windows, min_count, k, canonical,
+                                                                          kind == DX_KIND_ARROW, &s));
   wmark("the set made");
   if (out) *out = km;
   *set = s;
@@ -191,3 +193,11 @@ done:
   wmark("the device arrays freed");
   return rc;
 }
+
+int dx_file_kmer_set(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count,
+                     dx_kmer_set **set, dx_kmers64 *out)
+{ return file_kmer_set(ctx, kind, img, m, k, canonical, min_count, 0, set, out); }
+
+int dx_file_kmer_set_counted(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count,
+                             dx_kmer_set **set, dx_kmers64 *out)
+{ return file_kmer_set(ctx, kind, img, m, k, canonical, min_count, 1, set, out); }

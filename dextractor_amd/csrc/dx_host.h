@@ -55,6 +55,19 @@ __attribute__((visibility("hidden"))) int dx_d2d(dx_ctx *ctx, void *d_dst, const
    screen/dx_screen.hip, for dx_file_screen.c */
 __attribute__((visibility("hidden"))) int dx_kmer_set_fail(dx_ctx *ctx, int code, const char *what);
 __attribute__((visibility("hidden"))) int dx_screen_fail(dx_ctx *ctx, int code, const char *what);
+/* ... and "dx_file_depth: <what>", defined in screen/dx_screen_depth.hip, for dx_file_depth.c */
+__attribute__((visibility("hidden"))) int dx_depth_fail(dx_ctx *ctx, int code, const char *what);
+
+/* What dx_files_kmer_set_counted wants of screen/dx_kmer_set.hip beyond the C-ABI.  dx_sorted_take_counted: dx_sorted_take with every kept
+   run's length, saturated at 2^32 - 1, in d_count beside its first key in d_codes (cap of each; cap == 0 counts only, cap < *found is
+   DX_E_ARG); the runs are listed by dx_kmer_runs as 16-byte pairs, into d_tmp when 2 *found <= tmp_words (d_tmp may be NULL), else into a
+   block made and freed there.  dx_kmer_set_from_counted: the counted set of n distinct ascending codes and their counts on the device,
+   which are copied. */
+__attribute__((visibility("hidden"))) int dx_sorted_take_counted(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count,
+                                                                 void *d_tmp, uint64_t tmp_words, uint64_t *d_codes, uint32_t *d_count,
+                                                                 uint64_t cap, uint64_t *found);
+__attribute__((visibility("hidden"))) int dx_kmer_set_from_counted(dx_ctx *ctx, const uint64_t *d_codes, const uint32_t *d_count, uint64_t n,
+                                                                   uint32_t k, int canonical, int arrow, dx_kmer_set **set);
 /* ... and "<who>: <what>", defined in screen/dx_screen_spans.hip, for the two drivers of dx_file_screen_spans.c */
 __attribute__((visibility("hidden"))) int dx_screen_spans_fail(dx_ctx *ctx, int code, const char *who, const char *what);
 

@@ -12,5 +12,6 @@ struct dx_kmer_set
   uint64_t  n;                             // distinct codes, ascending (compared unsigned)
   uint64_t *d_codes;                       // n of them (never NULL: an empty set has a block of its own too)
   uint32_t *d_first;                       // 2^p + 1: first[b] = the place of the first code whose top p bits are >= b; first[2^p] = n
-  uint64_t  device_bytes;                  // what the two arrays take
+  uint32_t *d_count;                       // NULL: an uncounted set; else n words, count[i] = how often codes[i] was seen, saturated at 2^32 - 1
+  uint64_t  device_bytes;                  // what the arrays take
 };

@@ -50,6 +50,41 @@ __device__ __forceinline__ uint64_t sc_mask(const kc_part &p, uint32_t bit0, con
   return m;
 }
 
+// sc_mask's sibling for k_depths (screen/dx_screen_depth.hip): the same buckets, the same batches of SC_BATCH positions and the same
+// search, but what is kept of a code that is found is its PLACE in the set, not a bit.  at[t] = the place of batch position t's code,
+// SC_NONE when the set does not hold it; r stands at the batch's first window and is moved SC_BATCH windows on.  (A position past the
+// part's windows makes a code of the words all the same and asks for a bucket that exists; its answer is the caller's to drop.)
+template <bool CANON>
+__device__ __forceinline__ void sc_places(kc_roll<CANON> &r, const sc_set &s, uint32_t at[SC_BATCH])
+{ uint64_t c[SC_BATCH], v[SC_BATCH];
+  uint32_t lo[SC_BATCH], hi[SC_BATCH];
+  #pragma unroll
+  for (uint32_t t = 0; t < SC_BATCH; t++) { c[t] = r.code(); r.step(); }
+  #pragma unroll
+  for (uint32_t t = 0; t < SC_BATCH; t++)
+    { const uint64_t two = *(const u64_u *) (s.first + (c[t] >> s.shift));
+      lo[t] = (uint32_t) two; hi[t] = (uint32_t) (two >> 32);
+    }
+  #pragma unroll
+  for (uint32_t t = 0; t < SC_BATCH; t++)
+    { while (hi[t] - lo[t] > SC_LINEAR)
+        { const uint32_t mid = lo[t] + (hi[t] - lo[t]) / 2u;
+          if (s.code[mid] <= c[t]) lo[t] = mid; else hi[t] = mid;
+        }
+      v[t] = lo[t] < hi[t] ? s.code[lo[t]] : ~c[t];
+    }
+  #pragma unroll
+  for (uint32_t t = 0; t < SC_BATCH; t++)
+    { uint32_t j = lo[t];
+      bool hit = v[t] == c[t];
+      for (; !hit && j + 1u < hi[t] && v[t] < c[t]; )
+        { v[t] = s.code[++j];
+          hit = v[t] == c[t];
+        }
+      at[t] = hit ? j : SC_NONE;
+    }
+}
+
 // the positions of a chunk that lie in a hit window: the chunk's mask m and the mask of the chunk in front of it
 __device__ __forceinline__ uint64_t sc_cover(uint64_t m, uint64_t prev, uint32_t k)
 { uint64_t hi = m, lo = prev;

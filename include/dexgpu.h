@@ -1252,6 +1252,89 @@ int dx_screen_select(const dx_screen *rec, const uint32_t *rec_len, uint64_t rec
                      int mode, uint64_t **ids, uint64_t *n_ids);
 
 /* ------------------------------------------------------------------------------------------
+ *  depth: HOW OFTEN the k-mers of a read were seen -- counted sets, a depth profile, per-read quantiles
+ *         (csrc/screen/dx_kmer_set.hip, csrc/screen/dx_screen_depth.hip, csrc/dx_file_depth.c)
+ * ------------------------------------------------------------------------------------------ */
+/* A COUNTED set keeps a 32-bit count beside every code, saturated at 2^32 - 1; dx_set_info.device_bytes includes the counts.
+ * dx_code_kmer_screen and dx_code_kmer_spans take a counted set and ignore its counts; every set made by the calls above is
+ * uncounted and behaves as before.  dx_kmer_set_counted: 1 or 0, DX_E_ARG for NULL.  dx_kmer_set_counts: the counts in the order
+ * of dx_kmer_set_codes; DX_E_NOMEM when cap is fewer than the set holds, DX_E_ARG (dx_last_error says so) for an uncounted set.   */
+int dx_kmer_set_counted(const dx_kmer_set *set);
+int dx_kmer_set_counts(dx_ctx *ctx, const dx_kmer_set *set, uint32_t *out /* host */, uint64_t cap);
+
+/* dx_kmer_set_from_sorted with every kept code's count = min(the length of its run, 2^32 - 1).  The codes are byte for byte
+ * dx_kmer_set_from_sorted's of the same input; a run may be longer than any tile (dx_kmer_runs measures it); places come from
+ * counts and a prefix sum, the same bytes on every call.  The refusals are dx_kmer_set_from_sorted's.                              */
+int dx_kmer_set_from_sorted_counted(dx_ctx *ctx, const uint64_t *d_sorted, uint64_t n, uint64_t min_count, uint32_t k, int canonical,
+                                    int arrow, dx_kmer_set **set);
+
+/* The counted set of n host (code, count) pairs in any order -- the lists dx_file_kmers_wide and dx_files_kmers_wide hand out, or a
+ * table from elsewhere.  With canonical every code is replaced by min(code, rc(code)) first; entries with equal codes ADD; a sum,
+ * and a single count, saturates at 2^32 - 1; a pair with count 0 is dropped.  The pairs are sorted and added on the host, the two
+ * arrays uploaded and indexed.  The refusals are dx_kmer_set_from_codes', the index named.                                          */
+int dx_kmer_set_from_kmers(dx_ctx *ctx, const dx_kmer64 *list /* host */, uint64_t n, uint32_t k, int canonical, int arrow,
+                           dx_kmer_set **set);
+
+/* dx_file_kmer_set and dx_files_kmer_set with the runs' lengths kept beside the codes: the same arguments, the same route and passes
+ * (in the multi-pass route a range's counts are gathered and concatenated as its codes are), the same refusals and errors.        */
+int dx_file_kmer_set_counted(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, uint64_t min_count,
+                             dx_kmer_set **set, dx_kmers64 *out /* may be NULL */);
+int dx_files_kmer_set_counted(dx_ctx *ctx, int kind, const uint8_t *const *imgs, const size_t *bytes, uint32_t nimg, uint32_t k,
+                              int canonical, uint64_t min_count, uint64_t room /* windows a pass; 0: chosen */, dx_kmer_set **set,
+                              dx_kmers64 *out /* may be NULL */, uint32_t *passes /* may be NULL */);
+
+/* The depth profile.  Units, windows, codes and bounds are dx_code_kmer_codes', with the set's k and canonical.  Window p of unit j
+ * goes to d_depth[off[j] + p], off = the exclusive sums of w_j = max(0, d_len[j] - k + 1), a unit that does not lie inside the
+ * in_bytes counting 0; d_off[0 .. n] (device, 8-byte aligned; may be NULL) gets off, d_off[n] = the windows.  The value is
+ * min(count of the window's code, 65535), 0 for a code that is not in the set; an uncounted set counts 1 for every code it holds.
+ * *windows = sum w_j.  If that exceeds cap nothing is written (d_off neither) and the call is DX_E_NOMEM, *windows still set.
+ * DX_E_FORMAT, *bad_unit and DX_E_ARG are dx_code_kmer_codes' (the good units' depths are written all the same), and DX_E_ARG for a
+ * NULL set.  The same bytes on every call; nothing behind d_depth[*windows] is touched.  n == 0 writes d_off[0] = 0 alone.          */
+int dx_code_kmer_depths(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                        const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                        const dx_kmer_set *set,
+                        uint16_t *d_depth, uint64_t cap /* words of room */,
+                        uint64_t *d_off /* n + 1, device; may be NULL */,
+                        uint64_t *windows /* host */, uint64_t *bad_unit /* may be NULL */);
+
+typedef struct { uint32_t windows, hits; uint64_t sum; uint16_t min, q1, median, q3, max, reserved[3]; } dx_depth;   /* 32 bytes */
+
+/* Per unit j the statistics of v = d_depth[d_off[j] .. d_off[j + 1]), w values: windows = w; hits = the values that are not 0; sum =
+ * their 64-bit sum (of the clamped values, as stored); min and max over all w; with s = v sorted ascending q1 = s[(w - 1) / 4],
+ * median = s[2 (w - 1) / 4], q3 = s[3 (w - 1) / 4] (integer divisions, 64-bit products: values that occur; exact); w == 0 gives all
+ * zeros; reserved is 0.  d_out (n entries, 4-byte aligned; may be NULL) gets them; total[0 .. 4) (host) = the windows, the hits, the
+ * sum and the units with a hit.  DX_E_FORMAT if d_off decreases (or a unit has 2^32 values or more), the smallest index in
+ * dx_last_error: that unit gets zeros, the others and the totals are made all the same.  DX_E_ARG for a NULL pointer that is needed
+ * (d_depth, d_off, total), an array that is not aligned, n >= 2^31.  n == 0 launches nothing.                                         */
+int dx_depth_stats(dx_ctx *ctx, const uint16_t *d_depth, const uint64_t *d_off /* n + 1 */, uint64_t n,
+                   dx_depth *d_out /* n; may be NULL */, uint64_t total[4] /* host: windows, hits, sum, units with a hit */);
+
+typedef struct { uint64_t records, symbols, windows, hits, sum, records_hit; uint32_t k, reserved; } dx_depth_report;   /* 56 bytes */
+
+/* The records of a .dexta / .dexar image against a (counted) set, where they lie: walked and sliced as dx_file_screen does it, 32
+ * bytes of entries a record; per slice a device profile of exactly the slice's windows (known from the lengths; the slices are
+ * narrowed so that a slice and its profile fit together, and DX_E_NOMEM names the bytes if one record's do not), dx_code_kmer_depths,
+ * dx_depth_stats, and the entries brought down.  *rec (may be NULL; malloc'd, dx_file_free) one dx_depth a record, *rec_len (may
+ * be NULL; malloc'd) every record's symbols; *profile (may be NULL; malloc'd) the whole profile, brought down only when it is asked
+ * for, and *rec_off (may be NULL; malloc'd) every record's place in it, records + 1 words, the last the windows.  A record lies in
+ * one slice: the answer does not depend on the slicing.  The refusals are dx_file_screen's.  *out is untouched on any error.        */
+int dx_file_depth(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const dx_kmer_set *set, dx_depth_report *out,
+                  dx_depth **rec /* may be NULL */, uint32_t **rec_len /* may be NULL */,
+                  uint16_t **profile /* may be NULL */, uint64_t **rec_off /* may be NULL; records + 1 */);
+
+#define DX_DEPTH_MIN    0
+#define DX_DEPTH_Q1     1
+#define DX_DEPTH_MEDIAN 2
+#define DX_DEPTH_Q3     3
+#define DX_DEPTH_MAX    4
+/* Host only, no GPU: the records that dx_file_depth's answer selects.  A record matches when windows >= max(min_windows, 1) and
+ * lo <= stat <= hi, stat one of DX_DEPTH_*; mode DX_SCREEN_KEEP: the records that match, DX_SCREEN_DROP: the others.  *ids (malloc'd,
+ * dx_file_free; *n_ids of them, ascending) goes to dx_file_subset unchanged -- for the .dexta, the .dexar and the .dexqv of the same
+ * records.  *n_ids == 0 is DX_OK.  DX_E_ARG for an unknown stat or mode, lo > hi, a NULL pointer that is needed.                     */
+int dx_depth_select(const dx_depth *rec, uint64_t records, int stat, uint32_t lo, uint32_t hi, uint32_t min_windows, int mode,
+                    uint64_t **ids, uint64_t *n_ids);
+
+/* ------------------------------------------------------------------------------------------
  *  screen spans: WHERE a read matches the set, and the archive cut there  (csrc/screen/dx_screen_spans.hip, csrc/dx_file_screen_spans.c)
  * ------------------------------------------------------------------------------------------ */
 typedef struct { uint64_t record; uint32_t beg, end; } dx_span;     /* 16 bytes: symbols [beg, end) of unit / record `record` */
