@@ -136,6 +136,15 @@ class DepthReport(C.Structure):                  # dx_depth_report
     _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64),
                 ("sum", C.c_uint64), ("records_hit", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32)]
 
+class IndexInfo(C.Structure):                    # dx_index_info
+    _fields_ = [("codes", C.c_uint64), ("windows", C.c_uint64), ("targets", C.c_uint64), ("symbols", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("k", C.c_uint32), ("canonical", C.c_uint32), ("arrow", C.c_uint32), ("reserved", C.c_uint32)]
+
+class PlaceReport(C.Structure):                  # dx_place_report
+    _fields_ = [("records", C.c_uint64), ("symbols", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64), ("seeds", C.c_uint64),
+                ("votes", C.c_uint64), ("records_placed", C.c_uint64), ("groups", C.c_uint64), ("reserved", C.c_uint64),
+                ("k", C.c_uint32), ("band_bits", C.c_uint32)]
+
 class Span(C.Structure):                         # dx_span
     _fields_ = [("record", C.c_uint64), ("beg", C.c_uint32), ("end", C.c_uint32)]
 
@@ -340,6 +349,22 @@ SIGNATURES = {
                                 C.POINTER(_P)]),
     "dx_depth_select": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P),
                                   C.POINTER(C.c_uint64)]),
+    "dx_code_kmer_index": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dx_file_kmer_index": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "dx_kmer_index_from_letters": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "dx_pack_letters": (C.c_int, [C.c_int, _P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "dx_kmer_index_info": (C.c_int, [_P, C.POINTER(IndexInfo)]),
+    "dx_kmer_index_set": (_P, [_P]),
+    "dx_kmer_index_targets": (_P, [_P, C.POINTER(C.c_uint64)]),
+    "dx_kmer_index_positions": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64]),
+    "dx_kmer_index_free": (C.c_int, [_P, _P]),
+    "dx_code_kmer_seeds": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.c_uint64,
+                                     C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_uint64)]),
+    "dx_seeds_place": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint64 * 3)]),
+    "dx_file_place": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(PlaceReport), C.POINTER(_P),
+                                C.POINTER(_P)]),
+    "dx_place_select": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                  C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "dx_code_kmer_spans": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64 * 3),
                                      C.POINTER(C.c_uint64)]),
     "dx_spans_join": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64 * 2), C.POINTER(C.c_uint64)]),

@@ -1193,6 +1193,102 @@ class Context:
             out = (_fields(rp), _take(rec, DEPTH_DTYPE, rp.records), _take(rl, np.uint32, rp.records))
             return out + (_take(pf, np.uint16, rp.windows), _take(ro, np.uint64, rp.records + 1)) if profile else out
 
+    # ---- place: where on a reference a read lies ------------------------------------------------------------
+    def kmer_index(self, kind, img: bytes, k, canonical=False):
+        """dx_file_kmer_index: the records of a .dexta / .dexar image as the targets of a KmerIndex -- a counted KmerSet of their
+        windows that also keeps where on the reference (the targets one behind the other) every k-mer stands, and on which strand"""
+        h = C.c_void_p()
+        self._chk(self.lib.dx_file_kmer_index(self.h, _kind(kind), img, len(img), int(k), int(bool(canonical)), C.byref(h)))
+        return KmerIndex(self, h)
+
+    def kmer_index_from_letters(self, seqs, k, canonical=False, arrow=False):
+        """dx_kmer_index_from_letters: the KmerIndex of plain sequences (str or bytes: acgtACGT, or 1234 with arrow), packed on the
+        host.  Raises DexGPUError (DX_E_ARG, the target and the position named) for a letter that is not the kind's."""
+        pats, n = _patterns(seqs)
+        lens = np.array([len(p) for p in pats[:n]], np.uint32)
+        h = C.c_void_p()
+        self._chk(self.lib.dx_kmer_index_from_letters(self.h, int(bool(arrow)), pats, lens.ctypes.data if n else None, n, int(k),
+                                                      int(bool(canonical)), C.byref(h)))
+        return KmerIndex(self, h)
+
+    def code_kmer_index(self, d_in, boff, beg, length, k, canonical=False, arrow=False, in_bytes=None, n=None):
+        """dx_code_kmer_index: the units of a packed device buffer (as for code_kmer_codes) are the targets of the KmerIndex"""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        h = C.c_void_p()
+        self._chk(self.lib.dx_code_kmer_index(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                              int(b_len // 4 if n is None else n), int(k), int(bool(canonical)), int(bool(arrow)),
+                                              C.byref(h)))
+        return KmerIndex(self, h)
+
+    def code_kmer_seeds(self, d_in, boff, beg, length, index, max_occ=1, count=None, off=None, cap=0, seeds=None, in_bytes=None, n=None):
+        """dx_code_kmer_seeds: units as for code_kmer_codes, against the KmerIndex index; every occurrence on the reference of a
+        window whose code the index holds at most max_occ times is a seed {unit, pos, gpos, strand}.  count: a device array of n
+        uint32 for every unit's seeds, or None; off: a device array of n + 1 uint64 for the units' places in the list, or None;
+        seeds: a device array of 16 cap bytes, or None: made and freed here (cap 0: counted only).  Returns (totals: uint64
+        [windows, windows with a seed, seeds, units with a seed], the seeds in the order (unit, pos, gpos) as a SEED_DTYPE array).
+        Raises DexGPUError: DX_E_NOMEM (.totals) when cap is short -- nothing is written --, DX_E_FORMAT (.bad_unit, .totals) for a
+        unit outside in_bytes."""
+        p_in, b_in = _dev(d_in)
+        p_len, b_len = _dev(length)
+        n, cap = int(b_len // 4 if n is None else n), int(cap)
+        tot, bad = (C.c_uint64 * 4)(), C.c_uint64()
+
+        def call(p_seeds):
+            rc = self.lib.dx_code_kmer_seeds(self.h, p_in, int(b_in if in_bytes is None else in_bytes), _addr(boff), _addr(beg), p_len,
+                                             n, index.h if index is not None else None, int(max_occ), _addr(count), _addr(off),
+                                             p_seeds, cap, C.byref(tot), C.byref(bad))
+            if rc != 0:
+                raise self._err(rc, bad_unit=_index(bad), totals=np.array(list(tot), np.uint64))
+            return tot[2]
+        lst = self._listed(call, cap, SEED_DTYPE, seeds)
+        return np.array(list(tot), np.uint64), lst
+
+    def seeds_place(self, seeds, off, k, band_bits=8, n=None, out=None):
+        """dx_seeds_place: per unit j the vote over the diagonals of its seeds seeds[off[j] .. off[j + 1]) -- seeds: a SEED_DTYPE
+        array on the host (uploaded here) or a device array; off: n + 1 uint64, on the host or the device.  out: a device array of n
+        32-byte entries, or None: made and freed here.  Returns (totals: uint64 [seeds, votes, units placed], a PLACE_DTYPE array,
+        one entry a unit).  Raises DexGPUError: DX_E_FORMAT (.totals) when off decreases or a seed names another unit."""
+        own = []
+        try:
+            if isinstance(seeds, np.ndarray):
+                a = np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
+                seeds = self.to_device(a) if len(a) else None
+                own.append(seeds)
+            if isinstance(off, np.ndarray):
+                o = np.ascontiguousarray(off, dtype=np.uint64)
+                n = len(o) - 1 if n is None else int(n)
+                off = self.to_device(o)
+                own.append(off)
+            else:
+                n = int(_dev(off)[1] // 8 - 1 if n is None else n)
+            if out is None:
+                out = self.alloc(32 * n + 32)
+                own.append(out)
+            tot = (C.c_uint64 * 3)()
+            rc = self.lib.dx_seeds_place(self.h, _addr(seeds), _addr(off), n, int(k), int(band_bits), _addr(out), C.byref(tot))
+            totals = np.array(list(tot), np.uint64)
+            if rc != 0:
+                raise self._err(rc, totals=totals)
+            return totals, self._download(_addr(out), PLACE_DTYPE, n)
+        finally:
+            for b in own:
+                if b is not None:
+                    b.free()
+
+    def place(self, kind, img: bytes, index, max_occ=1, band_bits=8, seed_room=0):
+        """dx_file_place: the records of a .dexta / .dexar image placed on the KmerIndex's reference -> (report: records, symbols,
+        windows, hits, seeds, votes, records_placed, groups, k, band_bits; rec: a PLACE_DTYPE array, one entry a record; rec_len: every
+        record's symbols; where: a PLACE_WHERE_DTYPE array -- target: the one that holds gbeg, tbeg and tend: gbeg and min(gend, the
+        target's end) relative to it, all UINT32_MAX for a record that is not placed).  api.place_select turns rec into the ids that
+        Context.subset takes."""
+        rp = L.PlaceReport()
+        with _Outs(self.lib, 2) as (rec, rl):
+            self._chk(self.lib.dx_file_place(self.h, _kind(kind), img, len(img), index.h if index is not None else None, int(max_occ),
+                                             int(band_bits), int(seed_room), C.byref(rp), C.byref(rec), C.byref(rl)))
+            r = _take(rec, PLACE_DTYPE, rp.records)
+            return _fields(rp), r, _take(rl, np.uint32, rp.records), place_where(r, index.targets())
+
     # ---- screen spans: where a read matches the set, and the image cut there ------------------------------
     def code_kmer_spans(self, d_in, boff, beg, length, kset, count=None, cap=0, spans=None, in_bytes=None, n=None):
         """dx_code_kmer_spans: units and set as for code_kmer_screen; the spans of a unit are the maximal runs of symbols that lie in
@@ -1477,6 +1573,10 @@ SCREEN_DTYPE = np.dtype([("hits", "<u4"), ("covered", "<u4"), ("first", "<u4"), 
 SPAN_DTYPE = np.dtype([("record", "<u8"), ("beg", "<u4"), ("end", "<u4")])                                         # dx_span
 DEPTH_DTYPE = np.dtype([("windows", "<u4"), ("hits", "<u4"), ("sum", "<u8"), ("min", "<u2"), ("q1", "<u2"), ("median", "<u2"),
                         ("q3", "<u2"), ("max", "<u2"), ("reserved", "<u2", (3,))])                                    # dx_depth
+SEED_DTYPE = np.dtype([("unit", "<u4"), ("pos", "<u4"), ("gpos", "<u4"), ("strand", "<u4")])                       # dx_seed
+PLACE_DTYPE = np.dtype([("seeds", "<u4"), ("votes", "<u4"), ("strand", "<u4"), ("diag", "<u4"), ("rbeg", "<u4"), ("rend", "<u4"),
+                        ("gbeg", "<u4"), ("gend", "<u4")])                                                           # dx_place
+PLACE_WHERE_DTYPE = np.dtype([("target", "<u4"), ("tbeg", "<u4"), ("tend", "<u4")])                               # Context.place's
 _DEPTH_STATS = {"min": L.DX_DEPTH_MIN, "q1": L.DX_DEPTH_Q1, "median": L.DX_DEPTH_MEDIAN, "q3": L.DX_DEPTH_Q3, "max": L.DX_DEPTH_MAX}
 
 
@@ -1521,6 +1621,99 @@ class KmerSet:
 
     def __exit__(self, *a):
         self.free()
+
+
+class _IndexSet(KmerSet):
+    """the KmerSet inside a KmerIndex: the index's own, so free() only forgets it"""
+
+    def free(self):
+        self.h = None
+
+
+class KmerIndex:
+    """A dx_kmer_index: a counted set of a reference's k-mers that keeps their positions, on a Context's device (Context.kmer_index,
+    .kmer_index_from_letters, .code_kmer_index).  free() it, or use it as a context manager, before the Context is closed."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+
+    @property
+    def info(self) -> dict:
+        """{"codes", "windows", "targets", "symbols", "device_bytes", "k", "canonical", "arrow"}"""
+        i = L.IndexInfo()
+        self.ctx._chk(self.ctx.lib.dx_kmer_index_info(self.h, C.byref(i)))
+        return _fields(i)
+
+    def kset(self) -> KmerSet:
+        """the counted KmerSet inside (the index's own: it goes when the index does); screen, screen_spans and depth take it"""
+        return _IndexSet(self.ctx, C.c_void_p(self.ctx.lib.dx_kmer_index_set(self.h)))
+
+    def targets(self) -> np.ndarray:
+        """toff: the exclusive sums of the targets' lengths, targets + 1 uint64"""
+        n = C.c_uint64()
+        p = self.ctx.lib.dx_kmer_index_targets(self.h, C.byref(n))
+        return _take(C.c_void_p(p), np.uint64, n.value + 1) if p else np.zeros(1, np.uint64)
+
+    def positions(self):
+        """(start: codes + 1 uint32, the exclusive sums of the counts; pos: windows uint32, the occurrences of code i as
+        gpos << 1 | flip in pos[start[i] : start[i + 1]], ascending)"""
+        i = self.info
+        start, pos = np.zeros(i["codes"] + 1, np.uint32), np.zeros(i["windows"], np.uint32)
+        self.ctx._chk(self.ctx.lib.dx_kmer_index_positions(self.ctx.h, self.h, start.ctypes.data, len(start),
+                                                           pos.ctypes.data if len(pos) else None, len(pos)))
+        return start, pos
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.dx_kmer_index_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+def pack_letters(seq, arrow=False) -> bytes:
+    """dx_pack_letters: letters (acgtACGT, or 1234 with arrow) -> four symbols a byte, the first on top, as
+    Context.kmer_index_from_letters packs a target.  Host only.  Raises DexGPUError (.bad_pos) for a letter that is not the kind's."""
+    b = seq.encode() if isinstance(seq, str) else bytes(seq)
+    out, bad = C.create_string_buffer((len(b) + 3) // 4 + 1), C.c_uint32()
+    rc = L.load().dx_pack_letters(int(bool(arrow)), b, len(b), out, C.byref(bad))
+    if rc != 0:
+        raise _error(rc, f"dx_pack_letters: position {bad.value} is not a letter of the kind", bad_pos=bad.value)
+    return out.raw[:(len(b) + 3) // 4]
+
+
+def place_where(rec, toff) -> np.ndarray:
+    """per record of Context.place's answer the target that holds gbeg (np.searchsorted over toff) and [tbeg, tend) = [gbeg,
+    min(gend, the target's end)) relative to it, as a PLACE_WHERE_DTYPE array; all UINT32_MAX where votes == 0.  Host only."""
+    r, toff = np.asarray(rec, PLACE_DTYPE), np.asarray(toff, np.uint64).astype(np.int64)
+    out = np.full(len(r), 0xffffffff, PLACE_WHERE_DTYPE)
+    ok = (r["votes"] > 0) & (r["gbeg"] < toff[-1])
+    t = np.searchsorted(toff, r["gbeg"][ok].astype(np.int64), side="right") - 1
+    out["target"][ok] = t
+    out["tbeg"][ok] = r["gbeg"][ok] - toff[t]
+    out["tend"][ok] = np.minimum(r["gend"][ok].astype(np.int64), toff[t + 1]) - toff[t]
+    return out
+
+
+def place_select(rec, toff, target=None, lo=0, hi=0xffffffff, min_votes=1, strands=3, drop=False) -> np.ndarray:
+    """dx_place_select: the records of Context.place's answer that lie on a locus -- votes >= max(min_votes, 1), the strand allowed
+    (strands: 1 = forward, 2 = reverse, 3 = both), the target that holds gbeg being `target` (None: any), and [gbeg, min(gend, the
+    target's end)) relative to the target meeting [lo, hi) --, or with drop the others, ascending, as the uint64 ids Context.subset
+    takes.  toff: KmerIndex.targets().  Host only."""
+    r = np.ascontiguousarray(np.asarray(rec, PLACE_DTYPE))
+    t = np.ascontiguousarray(np.asarray(toff, np.uint64))
+    n = C.c_uint64()
+    with _Outs(L.load(), 1) as (ids,):
+        rc = L.load().dx_place_select(r.ctypes.data if len(r) else None, len(r), t.ctypes.data if len(t) else None, max(len(t), 1) - 1,
+                                      0xffffffff if target is None else int(target), int(lo), int(hi), int(min_votes), int(strands),
+                                      L.DX_SCREEN_DROP if drop else L.DX_SCREEN_KEEP, C.byref(ids), C.byref(n))
+        if rc != 0:
+            raise L.DexGPUError(rc, "dx_place_select: strands is 1, 2 or 3, lo <= hi, target below the targets, toff ascending from 0")
+        return _take(ids, np.uint64, n.value)
 
 
 def screen_select(rec, rec_len, min_hits=1, min_permille=0, drop=False) -> np.ndarray:

@@ -78,6 +78,17 @@ __attribute__((visibility("hidden"))) int dx_spans_list_counted(dx_ctx *ctx, con
                                                                 const uint32_t *d_len, uint64_t n, const dx_kmer_set *set, uint32_t *d_count,
                                                                 dx_span *d_spans, uint64_t cap, uint64_t *listed);
 
+/* "<who>: <what>", defined in place/dx_kmer_index.hip, for the drivers of dx_file_place.c */
+__attribute__((visibility("hidden"))) int dx_place_fail(dx_ctx *ctx, int code, const char *who, const char *what);
+
+/* What dx_file_place wants of dx_code_kmer_seeds beyond the C-ABI (place/dx_place_seeds.hip): the list alone, for units whose counts a
+   counting call over the same arguments (d_beg NULL) has left in d_count -- the driver counts a slice first, to form its groups.
+   d_off (n + 1, may be NULL) gets the units' places; *listed (may be NULL) = the counts' sum. */
+__attribute__((visibility("hidden"))) int dx_seeds_list_counted(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_boff,
+                                                                const uint32_t *d_len, uint64_t n, const dx_kmer_index *index, uint32_t max_occ,
+                                                                uint32_t *d_count, uint64_t *d_off, dx_seed *d_seeds, uint64_t cap,
+                                                                uint64_t *listed);
+
 /* What dx_file_digest wants of the CRC kernels beyond the C-ABI (digest/dx_crc.hip).  dx_crc32_ranges with a stride through its three
    arrays: unit j is d_off[j * stride], d_len[j * stride] -> d_crc[j * stride] -- header lines and bodies lie in two buffers, and their
    (crc, length) pairs are wanted side by side in record order.  dx_crc32_pairs: units 2 k and 2 k + 1 joined into unit k of the

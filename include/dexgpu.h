@@ -1403,6 +1403,117 @@ int dx_file_screen_cut(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, cons
                        uint64_t **ids /* may be NULL */, uint32_t **beg /* may be NULL */, uint32_t **end /* may be NULL */, uint64_t *n_ids /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ *  place: WHERE ON A REFERENCE each read lies, and on which strand -- an index that keeps positions, seeds, a vote over diagonals
+ *         (csrc/place/, csrc/dx_file_place.c).  Seed-and-vote placement, not alignment: no chaining, no base-level alignment, no CIGAR.
+ * ------------------------------------------------------------------------------------------ */
+/* The reference is T targets of l_t symbols one behind the other: toff[0 .. T] = the exclusive sums of the lengths, G = toff[T] < 2^31.
+ * The window at global position g = toff[t] + p exists for 0 <= p <= l_t - k; a window never spans two targets.  Its code is
+ * dx_code_kmer_codes'; with canonical the code kept is min(fwd, rc) and flip = (rc < fwd), without canonical and for a k-mer that is
+ * its own reverse complement flip = 0.  A dx_kmer_index (opaque, on the device, the context's; freed with dx_kmer_index_free before
+ * the context is closed) holds a COUNTED dx_kmer_set of those windows -- codes ascending, count[i] = the occurrences --, start[0 .. n]
+ * (32-bit) = the exclusive sums of the counts, and pos[start[i] .. start[i + 1]) = the occurrences of code i as g << 1 | flip,
+ * ascending in g.  An index over 2^31 symbols or more is not built.                                                                 */
+typedef struct dx_kmer_index dx_kmer_index;
+typedef struct { uint64_t codes, windows, targets, symbols, device_bytes; uint32_t k, canonical, arrow, reserved; } dx_index_info;   /* 56 bytes */
+
+/* The targets are the units of a packed buffer, which are dx_code_kmer_codes' own (any byte offset and phase, d_beg in front).  The
+ * counted set is made by dx_code_kmer_codes, dx_sort_u64 and dx_kmer_set_from_sorted_counted (min_count 1); one kernel then writes a
+ * key place << 32 | g << 1 | flip a window, dx_sort_u64 orders them and the low words are kept: the same bytes on every call.  While
+ * it is built the index takes 16 bytes a window beside itself.  DX_E_ARG (dx_last_error says why) for k outside 1..32, canonical with
+ * arrow, n >= 2^31, a NULL pointer that is needed, G >= 2^31 (the size and the target are named); DX_E_FORMAT for a target that does
+ * not lie inside the in_bytes.  *index is NULL on any error, and no device memory stays behind.                                      */
+int dx_code_kmer_index(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                       const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                       uint32_t k /* 1..32 */, int canonical, int arrow, dx_kmer_index **index);
+
+/* The records of a .dexta / .dexar image are the targets (arrow = the image's kind): a read set, or an assembly written in the
+ * archive's header form, serves as the reference.  The image goes up whole.  The refusals are dx_file_kmer_set's and the above.     */
+int dx_file_kmer_index(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, uint32_t k, int canonical, dx_kmer_index **index);
+
+/* A plain reference: T sequences of lens[t] letters (acgtACGT, or 1234 with arrow; no terminator is looked for).  They are packed
+ * on the host, four symbols a byte with the first on top, every target at a byte of its own, and go through dx_code_kmer_index.
+ * DX_E_ARG for a letter that is not the kind's: dx_last_error names the target and the position.                                    */
+int dx_kmer_index_from_letters(dx_ctx *ctx, int arrow, const char *const *seqs, const uint32_t *lens, uint64_t T, uint32_t k, int canonical,
+                               dx_kmer_index **index);
+/* Host only, its packer: len letters into (len + 3) / 4 bytes at out, four symbols a byte, the first on top, the last byte's pad bits
+ * zero.  DX_E_ARG for a letter that is not the kind's, *bad_pos (may be NULL) = its position; out is then written up to there.        */
+int dx_pack_letters(int arrow, const char *seq, uint32_t len, uint8_t *out, uint32_t *bad_pos /* may be NULL */);
+
+int dx_kmer_index_info(const dx_kmer_index *index, dx_index_info *info);
+/* the counted set inside, the index's own (not to be freed): dx_code_kmer_screen, _spans and _depths and their file drivers take it  */
+const dx_kmer_set *dx_kmer_index_set(const dx_kmer_index *index);
+/* toff[0 .. *targets] (host, the index's own: valid until dx_kmer_index_free); *targets may be NULL                                 */
+const uint64_t *dx_kmer_index_targets(const dx_kmer_index *index, uint64_t *targets);
+/* start (codes + 1 words) and pos (windows words) back to the host; either may be NULL with its cap 0; DX_E_NOMEM when a cap is
+ * fewer than the index holds                                                                                                         */
+int dx_kmer_index_positions(dx_ctx *ctx, const dx_kmer_index *index, uint32_t *start /* host */, uint64_t start_cap,
+                            uint32_t *pos /* host */, uint64_t pos_cap);
+int dx_kmer_index_free(dx_ctx *ctx, dx_kmer_index *index /* may be NULL */);
+
+typedef struct { uint32_t unit, pos, gpos, strand; } dx_seed;       /* 16 bytes */
+
+/* The SEEDS of unit j.  Units are dx_code_kmer_codes' own: any byte offset and phase, d_beg in front of the unit, pad bits and
+ * foreign symbols part of no window, nothing outside [0, in_bytes) read.  The windows are taken with p ascending; a window's code is
+ * made with the index's k and canonical, f being its own flip.  If the index holds the code at place i and count[i] <= max_occ
+ * (>= 1), every r in [start[i], start[i + 1]), ascending, gives the seed {j, p, pos[r] >> 1, (pos[r] & 1) ^ f}; a code above max_occ
+ * gives none.  The list is in the order (unit, pos, gpos), the same bytes on every call: a counting launch, a prefix sum, a listing
+ * launch, no atomic cursor.  d_count[j] (may be NULL) = unit j's seeds; d_off[0 .. n] (device, 8-byte aligned; may be NULL) = their
+ * exclusive sums, unit j's seeds standing in d_seeds[d_off[j] .. d_off[j + 1]).  cap == 0 counts only; cap below the seeds is
+ * DX_E_NOMEM with nothing written (d_off neither), total still set.  total[0 .. 4) (host) = the windows, the windows with a seed, the
+ * seeds and the units with a seed, over the good units.  A unit of 2^32 seeds or more is DX_E_NOMEM, dx_last_error naming the
+ * smallest.  A unit that does not lie inside the in_bytes has no seed; the smallest such j goes back in *bad_unit (UINT64_MAX
+ * otherwise; may be NULL) with DX_E_FORMAT, the others' seeds are made all the same.  DX_E_ARG for a NULL index or another pointer
+ * that is needed, max_occ 0, n >= 2^31, an array that is not aligned.  n == 0 writes d_off[0] = 0 alone.                            */
+int dx_code_kmer_seeds(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes,
+                       const uint64_t *d_boff, const uint32_t *d_beg /* NULL: all 0 */, const uint32_t *d_len, uint64_t n,
+                       const dx_kmer_index *index, uint32_t max_occ /* >= 1 */,
+                       uint32_t *d_count /* n; may be NULL */, uint64_t *d_off /* n + 1, device; may be NULL */,
+                       dx_seed *d_seeds /* cap entries; may be NULL when cap == 0 */, uint64_t cap,
+                       uint64_t total[4] /* host: windows, windows with a seed, seeds, units with a seed */, uint64_t *bad_unit /* may be NULL */);
+
+typedef struct { uint32_t seeds, votes, strand, diag, rbeg, rend, gbeg, gend; } dx_place;   /* 32 bytes */
+
+/* The placement of unit j from its seeds d_seeds[d_off[j] .. d_off[j + 1]).  A seed's diagonal is 32 bits: gpos - pos + 2^31 for
+ * strand 0, gpos + pos for strand 1 (both modulo 2^32); its bin = diag >> band_bits, 0 <= band_bits <= 31.  With c(s, b) = the unit's
+ * seeds of strand s in bin b, the best (s, b), among those with c(s, b) > 0, has the largest c(s, b) + c(s, b + 1), a bin beyond the
+ * last counting 0; on a tie the smaller s wins, then the smaller b.  The voted seeds are those of strand s in bin b or b + 1.
+ * d_out[j] = {seeds: all the unit's; votes: the best sum; strand: s; diag: b << band_bits; rbeg / rend: min pos and max pos + k
+ * over the voted seeds, read coordinates as stored; gbeg / gend: min gpos and max gpos + k over them, global}; a unit without a seed
+ * gets {0, 0, 0, UINT32_MAX x 5}.  The positions are global: a band that runs from one target's end into the next target's start
+ * counts the seeds of both -- per-target bands are not built.  total[0 .. 3) (host) = the seeds, the votes and the units placed.
+ * The keys (8 bytes a seed) and the sort's second array (8 more) are made and freed here.  DX_E_FORMAT if d_off decreases or a
+ * seed's `unit` is not its stretch's: the smallest index goes into dx_last_error, and what d_out holds means nothing.  DX_E_ARG for
+ * k outside 1..32, band_bits > 31, a NULL pointer that is needed, an array that is not aligned, n >= 2^31, 2^36 seeds or more.
+ * n == 0 launches nothing.                                                                                                           */
+int dx_seeds_place(dx_ctx *ctx, const dx_seed *d_seeds, const uint64_t *d_off /* n + 1 */, uint64_t n, uint32_t k, uint32_t band_bits,
+                   dx_place *d_out /* n */, uint64_t total[3] /* host: seeds, votes, units placed */);
+
+typedef struct { uint64_t records, symbols, windows, hits, seeds, votes, records_placed, groups, reserved; uint32_t k, band_bits; } dx_place_report;   /* 80 bytes */
+
+/* The records of a .dexta / .dexar image placed on the index's reference, where they lie: walked and sliced as dx_file_screen_spans
+ * does it.  Per slice the seeds are counted and the per-record counts brought down; consecutive records are grouped greedily so that
+ * a group's seeds stay at or below seed_room (0: 0.8 x the free memory / 32 bytes); every group is listed (dx_code_kmer_seeds' list
+ * from the counts that are there), placed (dx_seeds_place), and 32 bytes a record come down.  A single record above the room is
+ * DX_E_NOMEM, dx_last_error naming it.  A record lies in one slice and one group: the answer depends neither on the slicing nor on
+ * the room.  *rec (may be NULL; malloc'd, dx_file_free) one dx_place a record, *rec_len (may be NULL; malloc'd) every record's
+ * symbols; out->hits = the windows with a seed, out->groups = the groups that were listed.  The refusals are dx_file_screen's:
+ * DX_KIND_QUIVA, an unknown kind, an index whose arrow is not the image's kind, a NULL pointer that is needed; and max_occ 0,
+ * band_bits > 31.  *out is untouched on any error, and no device memory stays behind.                                               */
+int dx_file_place(dx_ctx *ctx, int kind, const uint8_t *img, size_t m, const dx_kmer_index *index, uint32_t max_occ, uint32_t band_bits,
+                  uint64_t seed_room /* seeds a group; 0: chosen */, dx_place_report *out,
+                  dx_place **rec /* may be NULL; malloc'd, dx_file_free; one a record */, uint32_t **rec_len /* may be NULL */);
+
+/* Host only, no GPU: the records of dx_file_place's answer that lie on a locus.  A record's target t is the one that holds gbeg
+ * (toff[t] <= gbeg < toff[t + 1]; toff: T + 1 words, dx_kmer_index_targets').  The record matches when votes >= max(min_votes, 1), its
+ * strand is allowed (strands: 1 = strand 0, 2 = strand 1, 3 = both), target == UINT32_MAX or t == target, and
+ * [gbeg - toff[t], min(gend, toff[t + 1]) - toff[t]) meets [lo, hi).  mode DX_SCREEN_KEEP: the records that match, DX_SCREEN_DROP:
+ * the others.  *ids (malloc'd, dx_file_free; *n_ids of them, ascending) goes to dx_file_subset unchanged -- for the .dexta, the
+ * .dexar and the .dexqv of the same records.  *n_ids == 0 is DX_OK.  DX_E_ARG for strands outside 1..3, another mode, lo > hi, a
+ * target that is neither UINT32_MAX nor below T, a toff that decreases or does not begin at 0, a NULL pointer that is needed.         */
+int dx_place_select(const dx_place *rec, uint64_t records, const uint64_t *toff, uint64_t T, uint32_t target /* UINT32_MAX: any */,
+                    uint32_t lo, uint32_t hi, uint32_t min_votes, int strands /* 1, 2 or 3 */, int mode, uint64_t **ids, uint64_t *n_ids);
+
+/* ------------------------------------------------------------------------------------------
  *  in-memory entry API: QVcoding_Scan1 / Compress_Next_QVentry1 (QV.c:866-920, 1343-1379) as a batch
  * ------------------------------------------------------------------------------------------ */
 /* dex2DB.c:511-643 feeds entries one at a time through the *1 functions and writes the compressed
