@@ -13,7 +13,7 @@ HIPFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 CFLAGS   = -O2 -fPIC -Iinclude -Wall -Wextra
 
 # verify/, records/, reads/, digest/, census/, compare/, find/, kmers/, sort/, screen/, place/: device code that came after the evidence set of profiles/ was made (profiles/check.py hashes
-# $(CSRC)/*.hip and *.hpp only); units/dx_units.hpp is what four of them share, tiles/dx_tiles.hpp what the tile kernels do (dx_kmers, dx_kmer_runs, dx_kmer_set, dx_screen_spans), find/dx_find_edit.hpp the queries of the two edit-distance files, kmers/dx_kmer_windows.hpp the windows of a chunk (dx_kmer_codes, dx_kmer_codes_range, dx_kmer_bins, dx_screen), screen/dx_kmer_set.hpp the set of screen/'s files, screen/dx_screen_look.hpp the look-up and the cover mask of dx_screen and dx_screen_spans, place/dx_kmer_index.hpp the index of place/'s files, dx_words.h the names of the words of ctx->d_u64
+# $(CSRC)/*.hip and *.hpp only); units/dx_units.hpp is what four of them share, tiles/dx_tiles.hpp what the tile kernels do (dx_kmers, dx_kmer_runs, dx_kmer_set, dx_screen_spans), find/dx_find_edit.hpp the queries of the two edit-distance files, kmers/dx_kmer_windows.hpp the windows of a chunk and the walk over a unit's chunks (dx_kmers, dx_kmer_codes, dx_kmer_codes_range, dx_kmer_bins, dx_screen, dx_screen_spans, dx_screen_depth, dx_kmer_index, dx_place_seeds), screen/dx_kmer_set.hpp the set of screen/'s files, screen/dx_screen_look.hpp the look-up and the cover mask of screen/'s and place/'s kernels, place/dx_kmer_index.hpp the index of place/'s files, dx_words.h the names of the words of ctx->d_u64
 HIP_SRC  = dx_ctx dx_pack2 dx_qv dx_qv_decode dx_synth dx_index dx_qv_walk verify/dx_verify records/dx_qv_records reads/dx_reads reads/dx_lines reads/dx_repack digest/dx_crc census/dx_census compare/dx_diff find/dx_find find/dx_find_edit find/dx_find_span kmers/dx_kmers kmers/dx_kmer_codes kmers/dx_kmer_codes_range kmers/dx_kmer_bins kmers/dx_kmer_runs sort/dx_sort screen/dx_kmer_set screen/dx_screen screen/dx_screen_spans screen/dx_screen_depth place/dx_kmer_index place/dx_place_seeds place/dx_place_vote
 HIP_OBJ  = $(HIP_SRC:%=$(BUILD)/%.o)
 C_SRC    = dx_host dx_walk_host dx_crew dx_files dx_file_pack2 dx_file_qv dx_file_qv_shard dx_file_check dx_file_u2 dx_file_subset dx_file_extract dx_file_compare dx_file_find dx_file_find_edit dx_file_cut dx_file_kmers dx_file_kmers_wide dx_file_kmers_files dx_file_screen dx_file_screen_spans dx_file_depth dx_file_place dx_select dx_compat

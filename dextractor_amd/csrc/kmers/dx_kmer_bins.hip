@@ -9,10 +9,9 @@
 // range costs in device memory is its windows, 16 bytes each, and that is what the bins tell: 2^bits 64-bit words, ADDED to,
 // 1 <= bits <= min(2 k, 12).
 //
-// Units, the bounds check, *windows and *bad_unit are dx_code_kmer_codes'.  The walk is k_kc_codes': tickets (k_ticket_units), 64
-// units a round, a unit of up to KC_LANE chunks by its lane, of up to 16 by 16 lanes, the others by the wave; the chunk's words
-// and the windows' codes are kc_take's and kc_roll's (dx_kmer_windows.hpp), the canonical code the rolling one.  Nothing outside
-// [0, in_bytes) is read.
+// Units, the bounds check, *windows and *bad_unit are dx_code_kmer_codes'.  The walk is kc_walk, the chunk's words and the windows'
+// codes are kc_take's and kc_roll's (all in kmers/dx_kmer_windows.hpp), the canonical code the rolling one; what is done with a
+// chunk stands here (kb_count), and the walk's hook after every step does the sweeps.  Nothing outside [0, in_bytes) is read.
 //
 // Counting is k_kmers' LDS route: the bins stand in LDS as 32-bit cells, 16 KiB at most; below 4096 cells a cell stands several
 // times (4096 / 2^bits copies, 64 at most, side by side: copy lane & (copies - 1)); a lane merges equal consecutive bins into one
@@ -86,56 +85,27 @@ void k_kmer_bins(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bou
   for (uint32_t c = threadIdx.x; c < (cells << shift); c += DX_BLOCK) s_bin[c] = 0u;
   __syncthreads();
 
-  const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP;
+  const uint32_t lane = (uint32_t) lane_id();
   uint32_t *mine_bins = s_bin + (lane & ((1u << shift) - 1u));
   uint64_t win = 0, counted = 0;           // the windows of the units this lane has read; an upper bound of what the wave has taken since its last sweep
   units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
     { // unit u0 + lane is this lane's to read and to check
-      const uint64_t    i  = u0 + lane;
-      const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0;                     // its symbols in the buffer; its first chunk's place
-      uint32_t nch = 0;                                    // its chunks
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          win += pu.len - k + 1u;
-        }
-
-      // up to KC_LANE chunks: the lane's own, chunk after chunk
-      if (nch && nch <= KC_LANE)
-        for (uint32_t j = 0; j < nch; j++)
-          kb_count<CANON>(kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k), k, down, shift, mine_bins);
-      counted += 64u * KC_LANE * KC_CHUNK;                 // (at most: 64 lanes, KC_LANE chunks each)
-
-      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from);
-          const uint32_t gn  = __shfl(nch, from);
-          if (mine && sub < gn)
-            kb_count<CANON>(kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k), k, down, shift, mine_bins);
-          counted += 64u * KC_CHUNK;
-        });
-
-      // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
-          for (uint32_t base = 0; base < wn; base += 64u)
-            { const uint32_t j = base + lane;
-              if (j < wn)
-                kb_count<CANON>(kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k), k, down, shift, mine_bins);
-              counted += 64u * KC_CHUNK;
-              if (counted >= flush_at)
-                { kb_sweep(s_bin, cells, shift, bins, lane);
-                  counted = 0;
-                }
+      const packed_unit pu = packed_unit_take(boff, beg, len, u0 + lane, r1, bound, bad);
+      const kc_unit     e  = kc_unit_of(pu, k);
+      const kc_place    at = { 0ull, 0u };
+      if (e.nch) win += pu.len - k + 1u;
+      // The wave sweeps as soon as it has taken flush_at windows, and a step of the walk adds 64 KC_LANE KC_CHUNK = 2^14 at the most:
+      // a wave adds fewer than KB_FLUSH + 2^14 between two sweeps of its own, and what a cell holds was added since the last
+      // sweep of any wave, which is no earlier than any wave's own last -- below 4 (2^29 + 2^14) < 2^32 for the four waves.
+      kc_walk(e, at, [&](uint64_t a, const kc_unit &u, const kc_place &)
+        { kb_count<CANON>(kc_take(in, in_bytes, a, u.S0, u.S1, k), k, down, shift, mine_bins); },
+        [&](uint32_t chunks)
+        { counted += chunks * KC_CHUNK;
+          if (counted >= flush_at)
+            { kb_sweep(s_bin, cells, shift, bins, lane);
+              counted = 0;
             }
         });
-      if (counted >= flush_at)
-        { kb_sweep(s_bin, cells, shift, bins, lane);
-          counted = 0;
-        }
     });
 
   win = wave_sum64(win);
@@ -176,8 +146,7 @@ extern "C" int dx_code_kmer_bins(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_b
   long long      flush = dx_test_num("bins_flush", (long long) KB_FLUSH);    // (tests: the cells swept from this many windows on)
   if (flush < 1 || flush > (long long) KB_FLUSH) flush = (long long) KB_FLUSH;
   const int      grid  = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (canonical) hipLaunchKernelGGL(k_kmer_bins<true>, dim3(grid), dim3(DX_BLOCK), bytes, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg,
                                     d_len, n, k, bits, shift, (uint64_t) flush, (unsigned long long *) d_bins, f.out, f.bad, f.ticket);
   else           hipLaunchKernelGGL(k_kmer_bins<false>, dim3(grid), dim3(DX_BLOCK), bytes, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg,

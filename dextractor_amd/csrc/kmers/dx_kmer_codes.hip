@@ -10,11 +10,12 @@
 // window's code is its symbols as a base-4 number, the first on top, in the low 2 k bits of the word -- the top 2 k bits of the 64 bits
 // that dx_find.hip holds for a position, moved down.  With `canonical` it is min(code, rc), compared unsigned (at k = 32 the top bit is
 // in use).  Places: off = the exclusive sums of w_j = max(0, len_j - k + 1), a unit that does not lie inside the buffer counting 0:
-// k_kc_windows leaves the w_j, dx_scan_u32 the sums and the total, which the host holds against cap before anything is written.
+// kc_windows_places (kmers/dx_kmer_windows.hpp: k_kc_windows, dx_scan_u32) leaves the w_j, the sums and the total, which the host holds
+// against cap before anything is written.
 //
-// The walk is k_find's and k_kmers': tickets (k_ticket_units), 64 units a round, a lane reading one unit's parameters and checking its
-// bounds; a unit of up to KC_LANE chunks (16 packed bytes = 64 positions on 16-byte boundaries of the buffer) is its lane's, one of up
-// to 16 goes four a step by 16 lanes each, the others by the whole wave.  A lane holds its chunk and the 8 bytes behind it (a window of
+// The walk is kc_walk (kmers/dx_kmer_windows.hpp, which says how it goes): tickets, 64 units a round, a unit of up to KC_LANE chunks by
+// its lane, of up to 16 by 16 lanes, the others by the whole wave; what is done with a chunk stands here (kc_write), and the unit's
+// first window's place travels with it.  A lane holds its chunk and the 8 bytes behind it (a window of
 // up to 32 symbols that begins in the chunk ends there at the latest) as three 64-bit words in the read's bit order, moved up to the
 // first position that is the unit's and at which a window begins (kc_take, as fd_take); a position's code is one shift of the upper
 // word, and the words move up two bits a position.  The reverse strand rolls along in a second 64-bit register, as in k_kmers:
@@ -38,19 +39,6 @@
 
 extern "C" {
 #include "dx_host.h"
-}
-
-// ---------------------------------------------------------------------------------------------
-//  k_kc_windows
-// ---------------------------------------------------------------------------------------------
-// w[j] = the windows of unit j: max(0, len - k + 1), 0 for a unit that does not lie inside `bound` bytes (k_kc_codes reports those)
-__global__ __launch_bounds__(DX_BLOCK)
-void k_kc_windows(const uint64_t *__restrict__ boff, const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n,
-                  uint64_t bound, uint32_t k, uint32_t *__restrict__ w)
-{ const uint64_t j = (uint64_t) blockIdx.x * DX_BLOCK + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t l = len[j];
-  w[j] = packed_unit_ok(boff[j], beg != NULL ? beg[j] : 0u, l, bound) && l >= k ? l - k + 1u : 0u;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -82,49 +70,16 @@ void k_kc_codes(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t boun
                 const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n, uint32_t k,
                 const uint64_t *__restrict__ off, uint64_t *__restrict__ codes, unsigned long long *__restrict__ bad,
                 uint32_t *__restrict__ ticket)
-{ const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP;
+{ const uint32_t lane = (uint32_t) lane_id();
   units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
-    { // unit u0 + lane is this lane's to read and to check
+    { // unit u0 + lane is this lane's to read and to check; its first window's place travels with it
       const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0, to = 0;             // its symbols in the buffer; its first chunk's place; its first window's place
-      uint32_t nch = 0;                                    // its chunks
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          to = off[i];
-        }
-
-      // up to KC_LANE chunks: the lane's own, chunk after chunk
-      if (nch && nch <= KC_LANE)
-        for (uint32_t j = 0; j < nch; j++)
-          { const kc_part p = kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k);
-            kc_write<CANON>(p, k, codes + to + p.first);
-          }
-
-      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gto = __shfl(to, from);
-          const uint32_t gn  = __shfl(nch, from);
-          if (mine && sub < gn)
-            { const kc_part p = kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
-              kc_write<CANON>(p, k, codes + gto + p.first);
-            }
-        });
-
-      // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint64_t wto = uniform64(__shfl(to, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
-          for (uint32_t base = 0; base < wn; base += 64u)
-            { const uint32_t j = base + lane;
-              if (j < wn)
-                { const kc_part p = kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
-                  kc_write<CANON>(p, k, codes + wto + p.first);
-                }
-            }
+      const kc_unit     e  = kc_unit_of(pu, k);
+      const kc_place    at = { e.nch ? off[i] : 0ull, 0u };
+      kc_walk(e, at, [&](uint64_t a, const kc_unit &u, const kc_place &to)
+        { const kc_part p = kc_take(in, in_bytes, a, u.S0, u.S1, k);
+          kc_write<CANON>(p, k, codes + to.to + p.first);
         });
     });
 }
@@ -150,17 +105,13 @@ extern "C" int dx_code_kmer_codes(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_
   const uint64_t bound = in_bytes;
   int rc = units_list_begin(ctx, "dx_code_kmer_codes", n, d_boff && d_len && (d_in || !in_bytes), 1, 16, true, &d_in, &in_bytes, &f, &d_off, &d_win);
   if (rc != DX_OK) return rc;
-  hipLaunchKernelGGL(k_kc_windows, dim3((unsigned) ((n + DX_BLOCK - 1u) / DX_BLOCK)), dim3(DX_BLOCK), 0, ctx->stream, d_boff, d_beg, d_len, n,
-                     bound, k, d_win);
-  DX_HIP(ctx, hipGetLastError());                          // (no ticket has been drawn yet: the first is, after the scan)
-  if ((rc = dx_scan_u32(ctx, d_win, n, d_off, &total)) != DX_OK) return rc;
+  if ((rc = kc_windows_places(ctx, d_boff, d_beg, d_len, n, bound, k, d_win, d_off, &total)) != DX_OK) return rc;
   *windows = total;
   if (total > cap)
     return dx_fail(ctx, DX_E_NOMEM, "dx_code_kmer_codes: %llu windows, and room for %llu codes", (unsigned long long) total, (unsigned long long) cap);
 
   const int grid = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (canonical) hipLaunchKernelGGL(k_kc_codes<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len, n,
                                     k, (const uint64_t *) d_off, d_codes, f.bad, f.ticket);
   else           hipLaunchKernelGGL(k_kc_codes<false>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len, n,

@@ -15,7 +15,9 @@
 //      a lane carries its running place from chunk to chunk; on the 16-lane and the wave route a lane counts its chunk's kept
 //      codes first, a scan over the lanes' counts (wave_incl_scan) places the chunk -- on the 16-lane route less what the rows in
 //      front hold, on the wave route plus a carry across the wave's steps -- and the lane walks its chunk again and writes.
-// The walk and the code are the shared ones (kc_take, kc_roll, dx_kmer_windows.hpp; tickets and the three routes of k_kc_codes).
+// The code is the shared one (kc_take, kc_roll), and so are the unit's extent and its way to a group's lanes and to the wave
+// (kc_unit_of, kc_unit_from, kc_unit_uniform: kmers/dx_kmer_windows.hpp, which says how the walk goes); the three routes differ in how
+// they sum and place, so their bodies stand here.
 //
 // Cost, ESTIMATE: the counting launch is dx_code_kmer_bins' walk without the LDS (the same order as k_kmers' LDS route, 0.5 to 0.8
 // ms for 10^9 positions); the listing launch walks a chunk twice on two of its routes and stores what k_kc_codes stores for the
@@ -83,35 +85,28 @@ void k_kc_range(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t boun
     { // unit u0 + lane is this lane's to read and to check
       const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0, to = 0;             // its symbols in the buffer; its first chunk's place; its first kept code's place
-      uint32_t nch = 0;                                    // its chunks
-      if (pu.ok && pu.len >= k)
-        { bool any = true;
-          if (LIST) { to = off[i]; any = off[i + 1u] > to; }
-          if (any)
-            { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-              a0 = (S0 >> 2) & ~15ull;
-              nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-            }
-        }
+      uint64_t to = 0;                                     // its first kept code's place
+      bool     any = true;                                 // it keeps a window (LIST)
+      if (LIST && pu.ok && pu.len >= k) { to = off[i]; any = off[i + 1u] > to; }
+      const kc_unit e = kc_unit_of(pu, k, any);
 
       // up to KC_LANE chunks: the lane's own, chunk after chunk
       uint32_t own = 0;
-      if (nch && nch <= KC_LANE)
-        for (uint32_t j = 0; j < nch; j++)
-          { const kc_part p = kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k);
+      if (e.nch && e.nch <= KC_LANE)
+        for (uint32_t j = 0; j < e.nch; j++)
+          { const kc_part p = kc_take(in, in_bytes, e.a0 + 16u * j, e.S0, e.S1, k);
             if (LIST) to += kr_write<CANON>(p, k, K, codes + to);
             else      own += kr_count<CANON>(p, k, K);
           }
-      if (!LIST && i < r1 && nch <= KC_LANE) w[i] = own;   // (nch 0: no window, or no good unit)
+      if (!LIST && i < r1 && e.nch <= KC_LANE) w[i] = own; // (nch 0: no window, or no good unit)
 
       // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gto = __shfl(to, from);
-          const uint32_t gn  = __shfl(nch, from);
-          const bool     on  = mine && sub < gn;
+      units_by_fours(__ballot(e.nch > KC_LANE && e.nch <= KC_GROUP), [&](int from, bool mine)
+        { const kc_unit  g   = kc_unit_from(e, from);
+          const uint64_t gto = __shfl(to, from);
+          const bool     on  = mine && sub < g.nch;
           kc_part p = { 0ull, 0ull, 0ull, 0u, 0u };
-          if (on) p = kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
+          if (on) p = kc_take(in, in_bytes, g.a0 + 16u * sub, g.S0, g.S1, k);
           const uint32_t kept = kr_count<CANON>(p, k, K);
           if (LIST)
             { const uint32_t incl  = wave_incl_scan(kept);
@@ -125,15 +120,14 @@ void k_kc_range(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t boun
         });
 
       // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
+      units_each(__ballot(e.nch > KC_GROUP), [&](int from)
+        { const kc_unit  u   = kc_unit_uniform(e, from);
           const uint64_t wto = uniform64(__shfl(to, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
           uint64_t carry = 0;                              // the unit's kept codes in the steps before this one
-          for (uint32_t base = 0; base < wn; base += 64u)
+          for (uint32_t base = 0; base < u.nch; base += 64u)
             { const uint32_t j = base + lane;
               kc_part p = { 0ull, 0ull, 0ull, 0u, 0u };
-              if (j < wn) p = kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
+              if (j < u.nch) p = kc_take(in, in_bytes, u.a0 + 16ull * j, u.S0, u.S1, k);
               const uint32_t kept = kr_count<CANON>(p, k, K);
               const uint32_t incl = wave_incl_scan(kept);
               if (LIST && kept) kr_write<CANON>(p, k, K, codes + wto + carry + (incl - kept));
@@ -183,8 +177,7 @@ extern "C" int dx_code_kmer_codes_range(dx_ctx *ctx, const uint8_t *d_in, uint64
   if (rc != DX_OK) return rc;
   const kr_keep K    = { 2u * k - bits, bin_lo, bin_hi - bin_lo };
   const int     grid = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   kr_launch<false>(ctx, grid, canonical, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, K, d_win, (const uint64_t *) NULL, (uint64_t *) NULL, f);
   if ((rc = units_list_places(ctx, f, d_win, n, d_off, &total)) != DX_OK) return rc;
   *windows = total;

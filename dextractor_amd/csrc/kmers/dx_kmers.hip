@@ -9,10 +9,12 @@
 // a k-mer is its symbols as a base-4 number, the first on top -- the top 2 k bits of the 64 bits that dx_find.hip holds for a
 // position, and k <= 14 keeps it in the upper 32.  The table is addressed by it: 4^k cells of 64 bits, ADDED to.
 //
-// The walk is k_find's: the waves draw tickets (k_ticket_units) and take a ticket's units 64 a round, a lane reading one unit's
+// The walk is kc_walk (kmers/dx_kmer_windows.hpp, which says how it goes, with that header's geometry: KC_LANE, KC_GROUP, KC_CHUNK,
+// KC_TARGET, KC_BATCH): the waves draw tickets and take a ticket's units 64 a round, a lane reading one unit's
 // parameters and checking its bounds; a unit is walked in chunks of 16 packed bytes = 64 positions on 16-byte boundaries of the
-// buffer -- up to KM_LANE chunks by its lane, up to UNITS_GROUP four units a step by 16 lanes each, the others by the whole wave.
-// A lane holds its chunk and the 4 bytes behind it (a window that begins in the chunk ends there at the latest) as five 32-bit
+// buffer -- up to KC_LANE chunks by its lane, up to UNITS_GROUP four units a step by 16 lanes each, the others by the whole wave.
+// What is done with a chunk stands here (km_take, km_count: 32-bit words, k <= 14), and the walk's hook after every step does the
+// sweeps.  A lane holds its chunk and the 4 bytes behind it (a window that begins in the chunk ends there at the latest) as five 32-bit
 // words in the read's bit order, moved up to the first position that is the unit's.  It takes 8 positions at a time: a position's
 // window is one funnel shift of the two upper words, its code one shift down, and after the eight the words move up 16 bits.
 // Only positions p with beg <= p and p + k <= beg + len are taken, so the symbols in front of the unit, those behind it, the pad
@@ -67,18 +69,13 @@
 //
 // This file stands outside the evidence set of profiles/ (profiles/check.py hashes csrc/*.hip); its kernels have no entry in
 // the profiler's name table and are timed with events on the context's stream (tools/kmer_rate.py).
-#include "units/dx_units.hpp"
+#include "kmers/dx_kmer_windows.hpp"
 #include "tiles/dx_tiles.hpp"
 
 #define KM_KMAX    14u                     // 4^14 cells of 8 bytes: 2 GiB
 #define KM_LDS_K   7u                      // up to here the table stands in LDS
 #define KM_WORDS   4096u                   // LDS words a table takes at least: 4096 / 4^k copies of a cell ...
 #define KM_COPIES  64u                     // ... and so many at most
-#define KM_BATCH   1u                      // units a ticket at least
-#define KM_TARGET  (16u << 10)             // packed bytes a ticket
-#define KM_CHUNK   64u                     // positions a chunk (16 packed bytes)
-#define KM_LANE    4u                      // chunks: a unit of up to so many is its lane's
-#define KM_GROUP   UNITS_GROUP             // chunks: up to here 16 lanes take the unit, beyond the wave
 #define KM_BLOCK   8u                      // positions between two moves of the words
 #define KM_FLUSH   (1ull << 29)            // windows a wave takes between two sweeps of the workgroup's cells
 #define KM_BINS    4096u                   // bins of the spectrum that stand in LDS
@@ -102,7 +99,7 @@ struct km_part { uint32_t r0, r1, r2, r3, r4, n; };
 // the chunk at byte a < bytes of the buffer against the unit that is symbols [S0, S1) of the buffer; n == 0: no window begins here
 __device__ __forceinline__ km_part km_take(const uint8_t *in, uint64_t bytes, uint64_t a, uint64_t S0, uint64_t S1, uint32_t k)
 { km_part p = { 0u, 0u, 0u, 0u, 0u, 0u };
-  const uint64_t p0 = S0 > 4u * a ? S0 : 4u * a, p1 = S1 < 4u * a + KM_CHUNK ? S1 : 4u * a + KM_CHUNK;
+  const uint64_t p0 = S0 > 4u * a ? S0 : 4u * a, p1 = S1 < 4u * a + KC_CHUNK ? S1 : 4u * a + KC_CHUNK;
   if (p1 <= p0 || S1 - p0 < k) return p;
   const uint32_t most = (uint32_t) (S1 - p0) - k + 1u;                        // windows from p0 on (a unit has fewer than 2^31 symbols)
   p.n = most < (uint32_t) (p1 - p0) ? most : (uint32_t) (p1 - p0);
@@ -212,63 +209,31 @@ void k_kmers(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
       __syncthreads();
     }
 
-  const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP;
+  const uint32_t lane = (uint32_t) lane_id();
   km_sink S;
   S.lds = s_tab + (lane & ((1u << shift) - 1u)); S.table = table; S.shift = shift; S.each = each != 0u;
   uint64_t win = 0, counted = 0;           // the windows of the units this lane has read; (LDS) an upper bound of what the wave has taken since its last sweep
-  units_rounds<false>(ticket, ticket_units_of(ticket, KM_BATCH), n, [&](uint64_t u0, uint64_t r1)
+  units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
     { // unit u0 + lane is this lane's to read and to check
-      const uint64_t    i  = u0 + lane;
-      const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0;                     // its symbols in the buffer; its first chunk's place
-      uint32_t nch = 0;                                    // its chunks
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          win += pu.len - k + 1u;
-        }
-
-      // up to KM_LANE chunks: the lane's own, chunk after chunk
-      if (nch && nch <= KM_LANE)
-        for (uint32_t j = 0; j < nch; j++)
-          km_count<CANON, LDS>(km_take(in, in_bytes, a0 + 16u * j, S0, S1, k), k, S);
-      counted += 64u * KM_LANE * KM_CHUNK;                 // (at most: 64 lanes, KM_LANE chunks each)
-
-      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(nch > KM_LANE && nch <= KM_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from);
-          const uint32_t gn  = __shfl(nch, from);
-          km_part p = { 0u, 0u, 0u, 0u, 0u, 0u };
-          if (mine && sub < gn) p = km_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
-          km_count<CANON, LDS>(p, k, S);
-          counted += 64u * KM_CHUNK;
-        });
-
-      // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(nch > KM_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
-          for (uint32_t base = 0; base < wn; base += 64u)
-            { const uint32_t j = base + lane;
-              km_part p = { 0u, 0u, 0u, 0u, 0u, 0u };
-              if (j < wn) p = km_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
-              km_count<CANON, LDS>(p, k, S);
-              counted += 64u * KM_CHUNK;
-              if (LDS && counted >= flush_at)
-                { km_sweep(s_tab, cells, shift, table, lane);
-                  counted = 0;
-                }
+      const packed_unit pu = packed_unit_take(boff, beg, len, u0 + lane, r1, bound, bad);
+      const kc_unit     e  = kc_unit_of(pu, k);
+      const kc_place    at = { 0ull, 0u };
+      if (e.nch) win += pu.len - k + 1u;
+      // (LDS) the wave sweeps as soon as it has taken flush_at windows, and a step of the walk adds 64 KC_LANE KC_CHUNK = 2^14 at the
+      // most: a wave adds fewer than KM_FLUSH + 2^14 between two sweeps of its own, and what a cell holds was added since the last
+      // sweep of any wave, which is no earlier than any wave's own last -- below 4 (2^29 + 2^14) < 2^32 for the four waves.
+      kc_walk(e, at, [&](uint64_t a, const kc_unit &u, const kc_place &)
+        { km_count<CANON, LDS>(km_take(in, in_bytes, a, u.S0, u.S1, k), k, S); },
+        [&](uint32_t chunks)
+        { counted += chunks * KC_CHUNK;
+          if (LDS && counted >= flush_at)
+            { km_sweep(s_tab, cells, shift, table, lane);
+              counted = 0;
             }
         });
-      if (LDS && counted >= flush_at)
-        { km_sweep(s_tab, cells, shift, table, lane);
-          counted = 0;
-        }
     });
 
-  #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) win += (uint64_t) __shfl_xor((unsigned long long) win, d);
+  win = wave_sum64(win);
   if (lane == 0u && win) atomicAdd(windows, (unsigned long long) win);
   if (LDS)
     { __syncthreads();
@@ -386,8 +351,7 @@ extern "C" int dx_code_kmers(dx_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes
   long long      flush  = dx_test_num("kmer_flush", (long long) KM_FLUSH);   // (tests: the cells swept from this many windows on)
   if (flush < 1 || flush > (long long) KM_FLUSH) flush = (long long) KM_FLUSH;
   const int      grid   = dx_grid_waves(ctx, n, bytes > (32u << 10) ? 8 : 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KM_TARGET, KM_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (canonical) rc = lds ? km_launch<true, true>(ctx, grid, bytes, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, shift, each, (uint64_t) flush, d_table, f)
                           : km_launch<true, false>(ctx, grid, bytes, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, shift, each, (uint64_t) flush, d_table, f);
   else           rc = lds ? km_launch<false, true>(ctx, grid, bytes, d_in, in_bytes, bound, d_boff, d_beg, d_len, n, k, shift, each, (uint64_t) flush, d_table, f)

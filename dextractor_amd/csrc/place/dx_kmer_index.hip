@@ -13,7 +13,8 @@
 //
 // The build, all by calls that exist: dx_code_kmer_codes writes every window's code, dx_sort_u64 (2 k bits) sorts them,
 // dx_kmer_set_from_sorted_counted (min_count 1) makes the set, dx_scan_u32 sums its counts and k_ix_narrow keeps the low words as
-// start.  New is k_ix_keys: k_depths' walk over the targets (screen/dx_screen_depth.hip), sc_places for the place of every window's
+// start.  New is k_ix_keys: kc_walk over the targets (kmers/dx_kmer_windows.hpp, as k_depths; a unit's first
+// window's place and its first symbol's global position travel with it), sc_places for the place of every window's
 // code in the set that was just made, and one 8-byte store a window at off[t] + p -- the place where dx_code_kmer_codes put its code,
 // the array is used again -- of the key  place << 32 | g << 1 | flip.  A second kc_roll over the same part gives the flip: after
 // code() kc_roll<true> holds the reverse strand's code in rcw and the forward one in w0 >> down (kmers/dx_kmer_windows.hpp is not
@@ -78,45 +79,16 @@ void k_ix_keys(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound
                const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n, sc_set s,
                const uint64_t *__restrict__ off, const uint64_t *__restrict__ toff, uint64_t *__restrict__ key,
                unsigned long long *__restrict__ bad, uint32_t *__restrict__ ticket)
-{ const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP, k = s.k;
+{ const uint32_t lane = (uint32_t) lane_id();
   units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
-    { const uint64_t    i  = u0 + lane;
+    { // unit u0 + lane is this lane's to read and to check; its first window's place and its first symbol's global position travel with it
+      const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0, to = 0;             // its symbols in the buffer; its first chunk's place; its first window's place
-      uint32_t nch = 0, g = 0;                             // its chunks; its first symbol's global position
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          to = off[i]; g = (uint32_t) toff[i];
-        }
-
-      if (nch && nch <= KC_LANE)
-        for (uint32_t j = 0; j < nch; j++)
-          { const kc_part p = kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k);
-            ix_write<CANON>(p, s, g + p.first, key + to + p.first);
-          }
-
-      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gto = __shfl(to, from);
-          const uint32_t gn  = __shfl(nch, from), gg = __shfl(g, from);
-          if (mine && sub < gn)
-            { const kc_part p = kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
-              ix_write<CANON>(p, s, gg + p.first, key + gto + p.first);
-            }
-        });
-
-      units_each(__ballot(nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint64_t wto = uniform64(__shfl(to, from));
-          const uint32_t wn  = uniform(__shfl(nch, from)), wg = uniform(__shfl(g, from));
-          for (uint32_t base = 0; base < wn; base += 64u)
-            { const uint32_t j = base + lane;
-              if (j < wn)
-                { const kc_part p = kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
-                  ix_write<CANON>(p, s, wg + p.first, key + wto + p.first);
-                }
-            }
+      const kc_unit     e  = kc_unit_of(pu, s.k);
+      const kc_place    at = { e.nch ? off[i] : 0ull, e.nch ? (uint32_t) toff[i] : 0u };
+      kc_walk(e, at, [&](uint64_t a, const kc_unit &u, const kc_place &to)
+        { const kc_part p = kc_take(in, in_bytes, a, u.S0, u.S1, s.k);
+          ix_write<CANON>(p, s, to.g + p.first, key + to.to + p.first);
         });
     });
 }
@@ -194,10 +166,9 @@ static int kx_keys(dx_ctx *ctx, const char *who, const uint8_t *d_in, uint64_t i
         const uint64_t bound = in_bytes;
         int r = units_begin(ctx, who, pieces, true, NULL, 0, 16, &d_in, &in_bytes, &f);
         if (r != DX_OK) return r;
-        const sc_set s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
+        const sc_set s = sc_set_of(set);
         const int grid = dx_grid_waves(ctx, pieces, 16);
-        hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (pieces - 1), (const uint32_t *) NULL, pieces,
-                           KC_TARGET, KC_BATCH, f.ticket);
+        kc_tickets(ctx, d_boff, pieces, f);
         if (set->canonical) hipLaunchKernelGGL(k_ix_keys<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg,
                                                d_len, pieces, s, d_off, d_toff, d_key, f.bad, f.ticket);
         else                hipLaunchKernelGGL(k_ix_keys<false>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg,

@@ -4,7 +4,8 @@
 //   dx_code_kmer_seeds   per unit the seeds {unit, pos, gpos, strand}, 16 bytes each, in the order (unit, pos, gpos)   (k_seeds)
 //
 // Units, windows and codes are dx_code_kmer_codes' with the index's k and canonical; the walk and its three paths are k_screen's
-// (screen/dx_screen.hip), the look-up is sc_places (screen/dx_screen_look.hpp): SC_BATCH = 8 positions a lane in flight.  A window
+// (screen/dx_screen.hip; the unit's extent and its way to a group's lanes and to the wave are kc_unit_of, kc_unit_from and
+// kc_unit_uniform of kmers/dx_kmer_windows.hpp), the look-up is sc_places (screen/dx_screen_look.hpp): SC_BATCH = 8 positions a lane in flight.  A window
 // p of unit j whose code stands at place i of the index with count[i] <= max_occ gives, for every r in [start[i], start[i + 1])
 // ascending, the seed {j, p, pos[r] >> 1, (pos[r] & 1) ^ f}, f the window's own flip (the code that was looked up is the reverse
 // strand's; a second kc_roll over the part gives it, as in k_ix_keys).  A code above max_occ gives none: repeats are dropped by a
@@ -104,14 +105,6 @@ __device__ __forceinline__ uint64_t ps_list(const kc_part &p, const sc_set &s, c
   return n;
 }
 
-// the sum along a row of 16 lanes of a 64-bit value, in every lane of the row
-__device__ __forceinline__ uint64_t ps_row_sum64(uint64_t v)
-{
-  #pragma unroll
-  for (int d = 8; d > 0; d >>= 1) v += (uint64_t) __shfl_xor((unsigned long long) v, d);
-  return v;
-}
-
 // in holds in_bytes bytes and 16 at least; the units are checked against `bound` (as in k_screen).
 // LIST false: count (n, or NULL) gets every unit's seeds, saturated at 2^32 - 1 with the unit's number to *big; total: windows,
 //   windows with a seed, seeds, units with a seed.
@@ -141,25 +134,20 @@ void k_seeds(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
   units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
     { const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0, st = 0;             // its symbols in the buffer; its first chunk's place; its first place in the list
-      uint32_t nch = 0;                                    // its chunks
+      const kc_unit     e  = kc_unit_of(pu, k);
+      uint64_t st = 0;                                     // its first place in the list
       bool     act = i < r1;                               // it is this launch's
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          if (!LIST) t_win += pu.len - k + 1u;
-        }
+      if (!LIST && e.nch) t_win += pu.len - k + 1u;
       if (LIST)
         { st  = i < r1 ? start[i] : 0ull;
-          act = i < r1 && nch != 0u && count[i] != 0u;
+          act = i < r1 && e.nch != 0u && count[i] != 0u;
         }
 
       // no window, or up to KC_LANE chunks: the lane's own, chunk after chunk
-      if (act && nch <= KC_LANE)
+      if (act && e.nch <= KC_LANE)
         { uint64_t c = 0;
-          for (uint32_t j = 0; j < nch; j++)
-            { const kc_part p = kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k);
+          for (uint32_t j = 0; j < e.nch; j++)
+            { const kc_part p = kc_take(in, in_bytes, e.a0 + 16u * j, e.S0, e.S1, k);
               if (LIST) c += ps_list<CANON>(p, s, x, (uint32_t) i, out + st + c);
               else
                 { uint32_t w;
@@ -171,13 +159,13 @@ void k_seeds(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
         }
 
       // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(act && nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gst = __shfl(st, from);
-          const uint32_t gn  = __shfl(nch, from);
-          const bool     on  = mine && sub < gn;
+      units_by_fours(__ballot(act && e.nch > KC_LANE && e.nch <= KC_GROUP), [&](int from, bool mine)
+        { const kc_unit  g   = kc_unit_from(e, from);
+          const uint64_t gst = __shfl(st, from);
+          const bool     on  = mine && sub < g.nch;
           kc_part  p = { 0ull, 0ull, 0ull, 0u, 0u };
           uint32_t w = 0u;
-          if (on) p = kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
+          if (on) p = kc_take(in, in_bytes, g.a0 + 16u * sub, g.S0, g.S1, k);
           const uint64_t c = on ? ps_count<CANON>(p, s, x, w) : 0ull;
           if (LIST)
             { const uint32_t incl = wave_incl_scan((uint32_t) c);              // (the unit's seeds fit 32 bits: the host has seen to it)
@@ -185,23 +173,22 @@ void k_seeds(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
               if (on && c) (void) ps_list<CANON>(p, s, x, (uint32_t) (u0 + (uint64_t) from), out + gst + (incl - (uint32_t) c - (grp ? low : 0u)));
             }
           else
-            { const uint64_t all = ps_row_sum64(c);
+            { const uint64_t all = row_sum64(c);
               t_hit += w; t_seed += c;
               if (mine && sub == 0u) leave(u0 + (uint64_t) from, all);
             }
         });
 
       // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(act && nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
+      units_each(__ballot(act && e.nch > KC_GROUP), [&](int from)
+        { const kc_unit u = kc_unit_uniform(e, from);
           uint64_t run = uniform64(__shfl(st, from)), mine = 0;           // LIST: the step's first place; else: this lane's seeds
-          for (uint32_t base = 0; base < wn; base += 64u)
+          for (uint32_t base = 0; base < u.nch; base += 64u)
             { const uint32_t j  = base + lane;
-              const bool     on = j < wn;
+              const bool     on = j < u.nch;
               kc_part  p = { 0ull, 0ull, 0ull, 0u, 0u };
               uint32_t w = 0u;
-              if (on) p = kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
+              if (on) p = kc_take(in, in_bytes, u.a0 + 16ull * j, u.S0, u.S1, k);
               const uint64_t c = on ? ps_count<CANON>(p, s, x, w) : 0ull;
               if (LIST)
                 { const uint32_t incl = wave_incl_scan((uint32_t) c);
@@ -267,11 +254,10 @@ static int seeds_run(dx_ctx *ctx, const char *who, const uint8_t *d_in, uint64_t
   int rc = units_list_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), 5, 16, places, &d_in, &in_bytes, &f, &d_start, &d_count);
   if (rc != DX_OK) return rc;
   DX_HIP(ctx, hipMemsetAsync(f.out + 4, 0xff, 8, ctx->stream));
-  const sc_set   s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
+  const sc_set   s = sc_set_of(set);
   const ps_index x = { set->d_count, index->d_start, index->d_pos, max_occ };
   const int grid = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (!counted)
     { if (set->canonical) PS_LAUNCH(true, false, d_count, (const uint64_t *) NULL, (u32x4_u *) NULL);
       else                PS_LAUNCH(false, false, d_count, (const uint64_t *) NULL, (u32x4_u *) NULL);

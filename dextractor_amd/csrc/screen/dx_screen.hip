@@ -7,9 +7,11 @@
 // unit, hits = the windows whose code is in the set, covered = the symbols that lie in one such window at least, first / last = the
 // smallest and the largest position of such a window (UINT32_MAX: none).
 //
-// The walk is k_kc_codes': tickets, 64 units a round, a lane reading one unit's parameters and checking its bounds; a unit of up to
-// KC_LANE chunks (16 packed bytes = 64 positions on 16-byte boundaries of the buffer) is its lane's, one of up to 16 goes four a step
-// by 16 lanes each -- one step: the group has a lane a chunk --, the others by the whole wave, 64 chunks a step.
+// The walk is the one kmers/dx_kmer_windows.hpp describes: tickets, 64 units a round, a lane reading one unit's parameters and checking
+// its bounds; a unit of up to KC_LANE chunks (16 packed bytes = 64 positions on 16-byte boundaries of the buffer) is its lane's, one
+// of up to 16 goes four a step by 16 lanes each -- one step: the group has a lane a chunk --, the others by the whole wave, 64 chunks
+// a step.  The unit's extent and its way to the group and to the wave are that header's (kc_unit_of, kc_unit_from, kc_unit_uniform);
+// the three tiers join a unit's chunks differently, so their bodies stand here.
 //
 // The look-up (sc_mask).  b = code >> (2 k - p) chooses the bucket; first[b] and first[b + 1] come from ONE 8-byte load at a 4-byte
 // boundary (gfx950 runs with unaligned access); then codes[lo .. hi) is searched: by bisection while more than SC_LINEAR codes are
@@ -99,23 +101,17 @@ void k_screen(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound,
     { // unit u0 + lane is this lane's to read and to check
       const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0;                     // its symbols in the buffer; its first chunk's place
-      uint32_t nch = 0;                                    // its chunks
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          t_win += pu.len - k + 1u;
-        }
+      const kc_unit     e  = kc_unit_of(pu, k);
+      if (e.nch) t_win += pu.len - k + 1u;
       const sc_acc none = { 0u, 0u, SC_NONE, SC_NONE };
 
       // no window (too short, or not in the buffer), or up to KC_LANE chunks: the lane's own, chunk after chunk
-      if (i < r1 && nch <= KC_LANE)
+      if (i < r1 && e.nch <= KC_LANE)
         { sc_acc   x = none;
           uint64_t prev = 0ull;
-          for (uint32_t j = 0; j < nch; j++)
-            { const uint64_t a = a0 + 16u * j, m = sc_chunk_mask<CANON>(in, in_bytes, a, S0, S1, s);
-              sc_add(x, m, prev, (int64_t) (4u * a) - (int64_t) S0, k);
+          for (uint32_t j = 0; j < e.nch; j++)
+            { const uint64_t a = e.a0 + 16u * j, m = sc_chunk_mask<CANON>(in, in_bytes, a, e.S0, e.S1, s);
+              sc_add(x, m, prev, (int64_t) (4u * a) - (int64_t) e.S0, k);
               prev = m;
             }
           t_hit += x.hits; t_cov += x.covered; t_unit += x.hits ? 1u : 0u;
@@ -123,15 +119,14 @@ void k_screen(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound,
         }
 
       // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from);
-          const uint32_t gn  = __shfl(nch, from);
-          const bool     on  = mine && sub < gn;
-          const uint64_t a   = ga0 + 16u * sub;
-          const uint64_t m   = on ? sc_chunk_mask<CANON>(in, in_bytes, a, gS0, gS1, s) : 0ull;
+      units_by_fours(__ballot(e.nch > KC_LANE && e.nch <= KC_GROUP), [&](int from, bool mine)
+        { const kc_unit  g   = kc_unit_from(e, from);
+          const bool     on  = mine && sub < g.nch;
+          const uint64_t a   = g.a0 + 16u * sub;
+          const uint64_t m   = on ? sc_chunk_mask<CANON>(in, in_bytes, a, g.S0, g.S1, s) : 0ull;
           const uint64_t up  = (uint64_t) __shfl_up((unsigned long long) m, 1u);
           sc_acc x = none;
-          if (on) sc_add(x, m, sub ? up : 0ull, (int64_t) (4u * a) - (int64_t) gS0, k);
+          if (on) sc_add(x, m, sub ? up : 0ull, (int64_t) (4u * a) - (int64_t) g.S0, k);
           t_hit += x.hits; t_cov += x.covered;
           #pragma unroll
           for (uint32_t d = 1; d < UNITS_GROUP; d <<= 1) sc_join(x, d);
@@ -142,17 +137,16 @@ void k_screen(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound,
         });
 
       // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
+      units_each(__ballot(e.nch > KC_GROUP), [&](int from)
+        { const kc_unit w = kc_unit_uniform(e, from);
           sc_acc   x = none;
           uint64_t carry = 0ull;                                         // lane 63's mask of the step before (wave-uniform)
-          for (uint32_t base = 0; base < wn; base += 64u)
+          for (uint32_t base = 0; base < w.nch; base += 64u)
             { const uint32_t j = base + lane;
-              const uint64_t a = wa0 + 16ull * j;
-              const uint64_t m = j < wn ? sc_chunk_mask<CANON>(in, in_bytes, a, wS0, wS1, s) : 0ull;
+              const uint64_t a = w.a0 + 16ull * j;
+              const uint64_t m = j < w.nch ? sc_chunk_mask<CANON>(in, in_bytes, a, w.S0, w.S1, s) : 0ull;
               const uint64_t up = (uint64_t) __shfl_up((unsigned long long) m, 1u);
-              if (j < wn) sc_add(x, m, lane ? up : carry, (int64_t) (4u * a) - (int64_t) wS0, k);
+              if (j < w.nch) sc_add(x, m, lane ? up : carry, (int64_t) (4u * a) - (int64_t) w.S0, k);
               carry = uniform64((uint64_t) __shfl((unsigned long long) m, 63));
             }
           t_hit += x.hits; t_cov += x.covered;
@@ -195,10 +189,9 @@ extern "C" int dx_code_kmer_screen(dx_ctx *ctx, const uint8_t *d_in, uint64_t in
   const uint64_t bound = in_bytes;
   int rc = units_begin(ctx, "dx_code_kmer_screen", n, d_boff && d_len && (d_in || !in_bytes), NULL, 4, 16, &d_in, &in_bytes, &f);
   if (rc != DX_OK) return rc;
-  const sc_set s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
+  const sc_set s = sc_set_of(set);
   const int grid = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (set->canonical) hipLaunchKernelGGL(k_screen<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len,
                                          n, s, d_out, f.out, f.bad, f.ticket);
   else                hipLaunchKernelGGL(k_screen<false>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len,

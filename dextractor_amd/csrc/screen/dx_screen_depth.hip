@@ -5,14 +5,14 @@
 //   dx_depth_stats        per stretch [off[j], off[j + 1]) of such a profile: windows, hits, sum, min, q1, median, q3, max     (k_depth_stats)
 //
 // A unit, a window and its code are what they are for dx_code_kmer_screen (screen/dx_screen.hip), the places are dx_code_kmer_codes'
-// (kmers/dx_kmer_codes.hip): off = the exclusive sums of w_j = max(0, len_j - k + 1), a unit outside the buffer counting 0; k_kc_windows'
-// statement of w_j is made here once more (k_depth_windows: that kernel is its file's own), dx_scan_u32 sums it, and the host holds the
-// total against cap before anything is written.  A depth is min(count, 65535) of the window's code, 0 for a code the set does not hold,
+// (kmers/dx_kmer_codes.hip): off = the exclusive sums of w_j = max(0, len_j - k + 1), a unit outside the buffer counting 0;
+// kc_windows_places (kmers/dx_kmer_windows.hpp: k_kc_windows, dx_scan_u32) states and sums the w_j, and the host holds the total
+// against cap before anything is written.  A depth is min(count, 65535) of the window's code, 0 for a code the set does not hold,
 // and 1 for every code of an uncounted set.
 //
-// k_depths.  The walk is k_kc_codes' and k_screen's: tickets, 64 units a round, a lane reading one unit's parameters and checking its
-// bounds; a unit of up to KC_LANE chunks is its lane's, one of up to 16 goes four a step by 16 lanes each, the others by the whole
-// wave; kc_take and kc_roll make the codes.  The look-up is sc_places (screen/dx_screen_look.hpp), sc_mask's sibling: SC_BATCH = 8
+// k_depths.  The walk is kc_walk (kmers/dx_kmer_windows.hpp, which says how it goes): tickets, 64 units a round, a unit of up to
+// KC_LANE chunks by its lane, of up to 16 by 16 lanes, the others by the whole wave; what is done with a chunk stands here
+// (sd_write), and the unit's first window's place travels with it; kc_take and kc_roll make the codes.  The look-up is sc_places (screen/dx_screen_look.hpp), sc_mask's sibling: SC_BATCH = 8
 // positions in flight, the 8 first[] loads asked for before any is waited for, then the buckets' first codes, then the few that need
 // more -- and for a code that is found ONE more dependent 4-byte load, count[place], asked for under the lane's own condition so that
 // a miss costs no request.
@@ -77,19 +77,6 @@ extern "C" {
 typedef uint16_t u16_u __attribute__((aligned(1)));
 
 // ---------------------------------------------------------------------------------------------
-//  k_depth_windows
-// ---------------------------------------------------------------------------------------------
-// w[j] = the windows of unit j: max(0, len - k + 1), 0 for a unit that does not lie inside `bound` bytes (k_depths reports those)
-__global__ __launch_bounds__(DX_BLOCK)
-void k_depth_windows(const uint64_t *__restrict__ boff, const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n,
-                     uint64_t bound, uint32_t k, uint32_t *__restrict__ w)
-{ const uint64_t j = (uint64_t) blockIdx.x * DX_BLOCK + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t l = len[j];
-  w[j] = packed_unit_ok(boff[j], beg != NULL ? beg[j] : 0u, l, bound) && l >= k ? l - k + 1u : 0u;
-}
-
-// ---------------------------------------------------------------------------------------------
 //  k_depths
 // ---------------------------------------------------------------------------------------------
 // the part's depths, one behind the other from out[0] on (a 2-byte boundary); count NULL: an uncounted set, 1 a code it holds
@@ -121,56 +108,23 @@ __device__ __forceinline__ void sd_write(const kc_part &p, const sc_set &s, cons
 }
 
 // in holds in_bytes bytes and 16 at least; the units are checked against `bound` (as in k_kc_codes).  off: the exclusive sums of
-// k_depth_windows' counts; depth holds off[n] words at least.
+// k_kc_windows' counts; depth holds off[n] words at least.
 template <bool CANON>
 __global__ __launch_bounds__(DX_BLOCK)
 void k_depths(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, const uint64_t *__restrict__ boff,
               const uint32_t *__restrict__ beg, const uint32_t *__restrict__ len, uint64_t n, sc_set s, const uint32_t *__restrict__ count,
               const uint64_t *__restrict__ off, uint16_t *__restrict__ depth, unsigned long long *__restrict__ bad,
               uint32_t *__restrict__ ticket)
-{ const uint32_t lane = (uint32_t) lane_id(), sub = lane % UNITS_GROUP, k = s.k;
+{ const uint32_t lane = (uint32_t) lane_id();
   units_rounds<false>(ticket, ticket_units_of(ticket, KC_BATCH), n, [&](uint64_t u0, uint64_t r1)
-    { // unit u0 + lane is this lane's to read and to check
+    { // unit u0 + lane is this lane's to read and to check; its first window's place travels with it
       const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0, to = 0;             // its symbols in the buffer; its first chunk's place; its first window's place
-      uint32_t nch = 0;                                    // its chunks
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-          to = off[i];
-        }
-
-      // up to KC_LANE chunks: the lane's own, chunk after chunk
-      if (nch && nch <= KC_LANE)
-        for (uint32_t j = 0; j < nch; j++)
-          { const kc_part p = kc_take(in, in_bytes, a0 + 16u * j, S0, S1, k);
-            sd_write<CANON>(p, s, count, depth + to + p.first);
-          }
-
-      // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gto = __shfl(to, from);
-          const uint32_t gn  = __shfl(nch, from);
-          if (mine && sub < gn)
-            { const kc_part p = kc_take(in, in_bytes, ga0 + 16u * sub, gS0, gS1, k);
-              sd_write<CANON>(p, s, count, depth + gto + p.first);
-            }
-        });
-
-      // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint64_t wto = uniform64(__shfl(to, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
-          for (uint32_t base = 0; base < wn; base += 64u)
-            { const uint32_t j = base + lane;
-              if (j < wn)
-                { const kc_part p = kc_take(in, in_bytes, wa0 + 16ull * j, wS0, wS1, k);
-                  sd_write<CANON>(p, s, count, depth + wto + p.first);
-                }
-            }
+      const kc_unit     e  = kc_unit_of(pu, s.k);
+      const kc_place    at = { e.nch ? off[i] : 0ull, 0u };
+      kc_walk(e, at, [&](uint64_t a, const kc_unit &u, const kc_place &to)
+        { const kc_part p = kc_take(in, in_bytes, a, u.S0, u.S1, s.k);
+          sd_write<CANON>(p, s, count, depth + to.to + p.first);
         });
     });
 }
@@ -330,19 +284,15 @@ extern "C" int dx_code_kmer_depths(dx_ctx *ctx, const uint8_t *d_in, uint64_t in
   const uint64_t bound = in_bytes;
   int rc = units_list_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), 1, 16, true, &d_in, &in_bytes, &f, &d_start, &d_win);
   if (rc != DX_OK) return rc;
-  hipLaunchKernelGGL(k_depth_windows, dim3((unsigned) ((n + DX_BLOCK - 1u) / DX_BLOCK)), dim3(DX_BLOCK), 0, ctx->stream, d_boff, d_beg, d_len, n,
-                     bound, set->k, d_win);
-  DX_HIP(ctx, hipGetLastError());                          // (no ticket has been drawn yet: the first is, after the scan)
-  if ((rc = dx_scan_u32(ctx, d_win, n, d_start, &total)) != DX_OK) return rc;
+  if ((rc = kc_windows_places(ctx, d_boff, d_beg, d_len, n, bound, set->k, d_win, d_start, &total)) != DX_OK) return rc;
   *windows = total;
   if (total > cap)
     return dx_fail(ctx, DX_E_NOMEM, "%s: %llu windows, and room for %llu depths", who, (unsigned long long) total, (unsigned long long) cap);
   if (d_off) DX_HIP(ctx, hipMemcpyAsync(d_off, d_start, (size_t) (n + 1u) * 8u, hipMemcpyDeviceToDevice, ctx->stream));
 
-  const sc_set s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
+  const sc_set s = sc_set_of(set);
   const int grid = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (set->canonical) hipLaunchKernelGGL(k_depths<true>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len,
                                          n, s, (const uint32_t *) set->d_count, (const uint64_t *) d_start, d_depth, f.bad, f.ticket);
   else                hipLaunchKernelGGL(k_depths<false>, dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff, d_beg, d_len,

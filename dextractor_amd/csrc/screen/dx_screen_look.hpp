@@ -1,6 +1,6 @@
 // dx_screen_look.hpp -- the look-up of a chunk's windows in a dx_kmer_set and the cover mask of its hits: what k_screen
 // (screen/dx_screen.hip) and k_spans (screen/dx_screen_spans.hip) share.  dx_screen.hip's header says how the look-up (sc_mask) and
-// the coverage (sc_cover) work and what they cost.  (Outside the evidence set of profiles/, as the files that include it are.)
+// the coverage (sc_cover) work and what they cost; the walk over a unit's chunks is kmers/dx_kmer_windows.hpp's.  (Outside the evidence set of profiles/, as the files that include it are.)
 #pragma once
 
 #include "kmers/dx_kmer_windows.hpp"
@@ -12,6 +12,11 @@
 
 // what a kernel needs of a dx_kmer_set
 struct sc_set { const uint64_t *code; const uint32_t *first; uint32_t k, shift; };     // shift = 2 k - p
+
+static sc_set sc_set_of(const dx_kmer_set *set)
+{ const sc_set s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
+  return s;
+}
 
 // the part's hit mask: bit bit0 + i = window i of the part is in the set (bit0 + p.n <= 64)
 template <bool CANON>

@@ -4,7 +4,8 @@
 //   dx_spans_join        consecutive spans of a record joined across gaps of at most max_gap, the short ones dropped
 //                        (k_join_heads, k_join)
 //
-// Units, windows, codes and the three paths are k_screen's (screen/dx_screen.hip); the look-up and the cover word of a chunk are its
+// Units, windows, codes and the three paths are k_screen's (screen/dx_screen.hip; the unit's extent and its way to a group's lanes
+// and to the wave are kc_unit_of, kc_unit_from and kc_unit_uniform of kmers/dx_kmer_windows.hpp); the look-up and the cover word of a chunk are its
 // own functions (screen/dx_screen_look.hpp).  What is new is the step from a chunk's cover word D_c (bit j: position j of the chunk
 // lies in a hit window) to intervals.  With t = the top bit of D_{c-1} (0 at the unit's first chunk):
 //     the begins          B_c = D_c & ~(D_c << 1 | t)
@@ -104,30 +105,25 @@ void k_spans(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
     { // unit u0 + lane is this lane's to read and to check
       const uint64_t    i  = u0 + lane;
       const packed_unit pu = packed_unit_take(boff, beg, len, i, r1, bound, bad);
-      uint64_t S0 = 0, S1 = 0, a0 = 0, st = 0;             // its symbols in the buffer; its first chunk's place; its first place in the list
-      uint32_t nch = 0;                                    // its chunks
+      const kc_unit     U  = kc_unit_of(pu, k);
+      uint64_t st = 0;                                     // its first place in the list
       bool     act = i < r1;                               // it is this launch's
-      if (pu.ok && pu.len >= k)
-        { S0 = 4u * pu.at + pu.beg; S1 = S0 + pu.len;
-          a0 = (S0 >> 2) & ~15ull;
-          nch = (uint32_t) ((((S1 - 1u) >> 2) - a0) >> 4) + 1u;
-        }
       if (LIST)
         { st  = i < r1 ? start[i] : 0ull;
-          act = i < r1 && nch != 0u && count[i] != 0u && st < cap;
+          act = i < r1 && U.nch != 0u && count[i] != 0u && st < cap;
         }
 
       // no window (too short, or not in the buffer), or up to KC_LANE chunks: the lane's own, chunk after chunk
-      if (act && nch <= KC_LANE)
+      if (act && U.nch <= KC_LANE)
         { uint64_t prev = 0ull, at = st;
           uint32_t t = 0u, c = 0u, cov = 0u;
-          for (uint32_t j = 0; j < nch; j++)
-            { const uint64_t a = a0 + 16u * j, m = sc_chunk_mask<CANON>(in, in_bytes, a, S0, S1, s);
+          for (uint32_t j = 0; j < U.nch; j++)
+            { const uint64_t a = U.a0 + 16u * j, m = sc_chunk_mask<CANON>(in, in_bytes, a, U.S0, U.S1, s);
               const uint64_t D = sc_cover(m, prev, k);
-              const sp_edges e = sp_take(D, t, S1 - 4u * a);
+              const sp_edges e = sp_take(D, t, U.S1 - 4u * a);
               const uint32_t nb = (uint32_t) __popcll((unsigned long long) e.B);
               if (LIST)
-                { sp_list(e, t, i, (int64_t) (4u * a) - (int64_t) S0, (uint32_t) (S1 - S0), out, at, cap);
+                { sp_list(e, t, i, (int64_t) (4u * a) - (int64_t) U.S0, (uint32_t) (U.S1 - U.S0), out, at, cap);
                   at += nb;
                 }
               else { c += nb; cov += (uint32_t) __popcll((unsigned long long) D); }
@@ -140,22 +136,22 @@ void k_spans(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
         }
 
       // up to 16 chunks: lanes 16 g .. 16 g + 15 take unit k + g, a chunk each
-      units_by_fours(__ballot(act && nch > KC_LANE && nch <= KC_GROUP), [&](int from, bool mine)
-        { const uint64_t gS0 = __shfl(S0, from), gS1 = __shfl(S1, from), ga0 = __shfl(a0, from), gst = __shfl(st, from);
-          const uint32_t gn  = __shfl(nch, from);
-          const bool     on  = mine && sub < gn;
-          const uint64_t a   = ga0 + 16u * sub;
-          const uint64_t m   = on ? sc_chunk_mask<CANON>(in, in_bytes, a, gS0, gS1, s) : 0ull;
+      units_by_fours(__ballot(act && U.nch > KC_LANE && U.nch <= KC_GROUP), [&](int from, bool mine)
+        { const kc_unit  g   = kc_unit_from(U, from);
+          const uint64_t gst = __shfl(st, from);
+          const bool     on  = mine && sub < g.nch;
+          const uint64_t a   = g.a0 + 16u * sub;
+          const uint64_t m   = on ? sc_chunk_mask<CANON>(in, in_bytes, a, g.S0, g.S1, s) : 0ull;
           const uint64_t upm = (uint64_t) __shfl_up((unsigned long long) m, 1u);
           const uint64_t D   = on ? sc_cover(m, sub ? upm : 0ull, k) : 0ull;
           const uint64_t upd = (uint64_t) __shfl_up((unsigned long long) D, 1u);
           const uint32_t t   = sub ? (uint32_t) (upd >> 63) : 0u;
-          const sp_edges e   = on ? sp_take(D, t, gS1 - 4u * a) : none;
+          const sp_edges e   = on ? sp_take(D, t, g.S1 - 4u * a) : none;
           const uint32_t nb  = (uint32_t) __popcll((unsigned long long) e.B);
           if (LIST)
             { const uint32_t incl = wave_incl_scan(nb);
               const uint32_t low  = __shfl(incl, (int) (grp ? UNITS_GROUP * grp - 1u : 0u));           // what the groups below have
-              if (on) sp_list(e, t, u0 + (uint64_t) from, (int64_t) (4u * a) - (int64_t) gS0, (uint32_t) (gS1 - gS0), out,
+              if (on) sp_list(e, t, u0 + (uint64_t) from, (int64_t) (4u * a) - (int64_t) g.S0, (uint32_t) (g.S1 - g.S0), out,
                               gst + (incl - nb - (grp ? low : 0u)), cap);
             }
           else
@@ -169,28 +165,27 @@ void k_spans(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t bound, 
         });
 
       // the others: the whole wave, 64 chunks a step
-      units_each(__ballot(act && nch > KC_GROUP), [&](int from)
-        { const uint64_t wS0 = uniform64(__shfl(S0, from)), wS1 = uniform64(__shfl(S1, from)), wa0 = uniform64(__shfl(a0, from));
-          const uint32_t wn  = uniform(__shfl(nch, from));
+      units_each(__ballot(act && U.nch > KC_GROUP), [&](int from)
+        { const kc_unit  w   = kc_unit_uniform(U, from);
           uint64_t run = uniform64(__shfl(st, from)), mine = 0;           // LIST: the step's first place; else: this lane's spans
           uint64_t carry = 0ull;                                         // lane 63's mask of the step before (wave-uniform)
           uint32_t open = 0u;                                            // ... and the top bit of its cover word
-          for (uint32_t base = 0; base < wn; base += 64u)
+          for (uint32_t base = 0; base < w.nch; base += 64u)
             { const uint32_t j  = base + lane;
-              const bool     on = j < wn;
-              const uint64_t a   = wa0 + 16ull * j;
-              const uint64_t m   = on ? sc_chunk_mask<CANON>(in, in_bytes, a, wS0, wS1, s) : 0ull;
+              const bool     on = j < w.nch;
+              const uint64_t a   = w.a0 + 16ull * j;
+              const uint64_t m   = on ? sc_chunk_mask<CANON>(in, in_bytes, a, w.S0, w.S1, s) : 0ull;
               const uint64_t upm = (uint64_t) __shfl_up((unsigned long long) m, 1u);
               const uint64_t D   = on ? sc_cover(m, lane ? upm : carry, k) : 0ull;
               const uint64_t upd = (uint64_t) __shfl_up((unsigned long long) D, 1u);
               const uint32_t t   = lane ? (uint32_t) (upd >> 63) : open;
-              const sp_edges e   = on ? sp_take(D, t, wS1 - 4u * a) : none;
+              const sp_edges e   = on ? sp_take(D, t, w.S1 - 4u * a) : none;
               const uint32_t nb  = (uint32_t) __popcll((unsigned long long) e.B);
               carry = uniform64((uint64_t) __shfl((unsigned long long) m, 63));
               open  = uniform((uint32_t) __shfl((int) (uint32_t) (D >> 63), 63));
               if (LIST)
                 { const uint32_t incl = wave_incl_scan(nb);
-                  if (on) sp_list(e, t, u0 + (uint64_t) from, (int64_t) (4u * a) - (int64_t) wS0, (uint32_t) (wS1 - wS0), out,
+                  if (on) sp_list(e, t, u0 + (uint64_t) from, (int64_t) (4u * a) - (int64_t) w.S0, (uint32_t) (w.S1 - w.S0), out,
                                   run + (incl - nb), cap);
                   run += wave_total(incl);
                   if (run >= cap + open) break;                          // (a span that is open at the seam still wants its end)
@@ -243,10 +238,9 @@ static int spans_run(dx_ctx *ctx, const char *who, const uint8_t *d_in, uint64_t
   const uint64_t bound = in_bytes;
   int rc = units_list_begin(ctx, who, n, d_boff && d_len && (d_in || !in_bytes), 3, 16, cap != 0, &d_in, &in_bytes, &f, &d_start, &d_count);
   if (rc != DX_OK) return rc;
-  const sc_set s = { set->d_codes, set->d_first, set->k, 2u * set->k - set->bits };
+  const sc_set s = sc_set_of(set);
   const int grid = dx_grid_waves(ctx, n, 16);
-  hipLaunchKernelGGL(k_ticket_units, dim3(1), dim3(1), 0, ctx->stream, d_boff, d_boff + (n - 1), (const uint32_t *) NULL, n,
-                     KC_TARGET, KC_BATCH, f.ticket);
+  kc_tickets(ctx, d_boff, n, f);
   if (!counted)
     { if (set->canonical) hipLaunchKernelGGL((k_spans<true, false>), dim3(grid), dim3(DX_BLOCK), 0, ctx->stream, d_in, in_bytes, bound, d_boff,
                                              d_beg, d_len, n, s, d_count, (const uint64_t *) NULL, (dx_span *) NULL, cap, f.out, f.bad, f.ticket);

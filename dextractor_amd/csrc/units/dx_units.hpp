@@ -109,6 +109,14 @@ __device__ __forceinline__ void chunk_words(const uint8_t *in, uint64_t bytes, u
   else                 { w0 = l << (8u * (back - 8u)); w1 = 0ull; w2 = 0ull; }
 }
 
+// the sum along a row of 16 lanes of a 64-bit value, in every lane of the row
+__device__ __forceinline__ uint64_t row_sum64(uint64_t v)
+{
+  #pragma unroll
+  for (int d = 8; d > 0; d >>= 1) v += (uint64_t) __shfl_xor((unsigned long long) v, d);
+  return v;
+}
+
 // the sum of a 64-bit value over the wave, in every lane
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
 {

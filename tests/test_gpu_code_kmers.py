@@ -18,9 +18,9 @@ pytestmark = pytest.mark.gpu
 
 # csrc/kmers/dx_kmers.hip
 CUT = 7               # KM_LDS_K: up to here the table stands in LDS, beyond the adds are global
-CHUNK = 64            # KM_CHUNK: positions of one 16-byte chunk, which stands on a 16-byte boundary of the BUFFER
-LANE = 4 * CHUNK      # KM_LANE: a unit of up to four chunks is its lane's
-GROUP = 16 * CHUNK    # KM_GROUP: up to 16 chunks 16 lanes take the unit, beyond the wave
+CHUNK = 64            # KC_CHUNK: positions of one 16-byte chunk, which stands on a 16-byte boundary of the BUFFER
+LANE = 4 * CHUNK      # KC_LANE: a unit of up to four chunks is its lane's
+GROUP = 16 * CHUNK    # KC_GROUP: up to 16 chunks 16 lanes take the unit, beyond the wave
 STEP = 64 * CHUNK     # what the wave takes of a long unit a step
 KS = [1, 2, CUT, CUT + 1, 13, 14]
 E_ARG, E_FORMAT = -1, -3          # DX_E_*

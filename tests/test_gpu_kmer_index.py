@@ -26,7 +26,7 @@ def ctx():
 
 def targets_of(k, seed):
     rng = np.random.default_rng(seed)
-    t = [rng.integers(0, 4, n).astype(np.uint8) for n in (0, k - 1, k, 70, 300)]
+    t = [rng.integers(0, 4, n).astype(np.uint8) for n in (0, k - 1, k, 70, 300, 1100, 5003)]   # (1100: 17 to 64 chunks; 5003: two pieces, two wave steps)
     t.append(np.zeros(90, np.uint8))                                         # poly-A: one code, every position
     if k % 2 == 0:                                                           # h + rc(h): a k-mer that is its own reverse complement
         h = rng.integers(0, 4, k // 2).astype(np.uint8)

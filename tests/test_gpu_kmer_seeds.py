@@ -36,7 +36,8 @@ def reference(seed):
 
 
 def lengths(k):
-    return sorted({0, k - 1, k, k + 1, 63, 64, 65, 255, 256, 257, LANE * CHUNK - 1, LANE * CHUNK + 1, GROUP * CHUNK - k, GROUP * CHUNK + 1, 2300})
+    return sorted({0, k - 1, k, k + 1, 63, 64, 65, 255, 256, 257, LANE * CHUNK - 1, LANE * CHUNK + 1, GROUP * CHUNK - k, GROUP * CHUNK + 1, 2300,
+                   4097, 5003})                                               # (more than 64 chunks: a second step of the wave path)
 
 
 def reads_of(targets, k, seed, piece=None):
@@ -45,7 +46,8 @@ def reads_of(targets, k, seed, piece=None):
     rng, b = np.random.default_rng(seed), P.Buffer()
     for j, n in enumerate(lengths(k) * 2):
         t = targets[j % 2 * 2 if n > 1000 else j % 3]                        # (the long ones from the long targets)
-        n = min(n, len(t))
+        if n > len(t):
+            t = np.concatenate([t] * (n // len(t) + 1))                       # (a read longer than its target: the target over and over)
         at = int(rng.integers(0, len(t) - n + 1))
         s = np.array(t[at:at + n], np.uint8)
         hit = rng.random(n) < 0.02
